@@ -1,6 +1,8 @@
 """Benchmark: device-resident FedAvg weighted reduction on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--scaling strong|weak]
+    python bench.py --full [...]  # the same, plus every side measurement and check (below)
+    python bench.py --dump-outputs DIR [...]  # the last timed step's result as DIR/<name>.npy
     python bench.py --e2e [...]   # host state_dicts in/out vs the CPU loop (scripts/bench_e2e.py)
     python bench.py --fpf [...]   # FPF2 bookkeeping per round (scripts/bench_fpf.py)
 
@@ -29,9 +31,23 @@ Inputs: ``mfl_amd.synthetic`` -- every value a pure function of (client,
 global column), so the model does not depend on N and any window of the
 gathered model is re-derived on the host by numpy + the oracle.
 
+A plain run sets up, warms up, times the steps, writes its outputs when
+``--dump-outputs`` is given and prints the line; whatever takes runs of its
+own after the timed region (cpu_baseline, parity, the shader clock,
+round_with_distances, the N > 1 overlap diagnostics) runs under ``--full``.
+
+``--dump-outputs DIR``: after the timed steps, the averaged model the last
+step left with its caller -- the gathered model, the host copy, or this
+rank's own columns -- as ``DIR/model.npy`` (float32; ``model_rank<r>.npy``
+per rank when no rank holds the whole model).  A model of more than
+DUMP_MAX_VALUES values is written as a fixed, seeded sample of column
+blocks (the first and last block included).  The inputs are a pure function
+of the arguments, so two builds can be compared file for file.
+
 Rank 0 prints ONE JSON line.  Besides the contract keys it carries:
   roofline      : the reduce kernel's algorithmic HBM bytes / its average
                   launch time (HIP events on the launch stream), vs 8 TB/s;
+and under ``--full``:
   cpu_baseline  : the reference's torch CPU loop (oracle restatement, the
                   same expression as fedavg_trainer.py:450-457) on bounded
                   samples, rank 0, N = 1 only: one flat key and the
@@ -534,6 +550,58 @@ def _clock_entry(fn) -> dict:
         return {"clock_mhz": None, "clock": {"error": f"{type(e).__name__}: {e}"}}
 
 
+DUMP_MAX_VALUES = 8 << 20  # values per run written by --dump-outputs (32 MB of fp32)
+DUMP_BLOCK = 4096  # a sampled model is written as whole blocks of this many columns
+
+
+def output_sample(t, max_values: int = DUMP_MAX_VALUES, block: int = DUMP_BLOCK, seed: int = 0):
+    """``t`` itself while it holds <= ``max_values`` values; else the values of
+    ``max_values // block`` column blocks: the first, the last and a seeded
+    draw of the block-aligned ones between, in column order.  A function of
+    (len(t), max_values, block, seed) only."""
+    import numpy as np
+    import torch
+
+    n = t.numel()
+    if n <= max_values:
+        return t
+    nblocks = max(3, max_values // block)
+    rng = np.random.default_rng(seed)
+    mid = np.sort(rng.choice(n // block, size=nblocks - 2, replace=False)).astype(np.int64) * block
+    starts = torch.from_numpy(np.concatenate([[0], mid, [n - block]]).astype(np.int64))
+    idx = (starts[:, None] + torch.arange(block, dtype=torch.int64)[None, :]).reshape(-1)
+    return t.reshape(-1)[idx.to(t.device)]
+
+
+def dump_outputs(dirpath: str, red, *, passes: int, rank: int, world: int) -> list:
+    """``--dump-outputs``: what the last timed step left with its caller, as
+    float32 ``.npy`` files under ``dirpath``; returns the files written by
+    this rank.  The gathered model is the same on every rank (rank 0 writes
+    it); without a gather every rank writes the columns it owns, in global
+    column order."""
+    import numpy as np
+    import torch
+
+    plan = red.plan
+    if red.gather:
+        if rank != 0:
+            return []
+        name, model = "model", red.full[:plan.P]
+    else:
+        name = "model" if world == 1 else f"model_rank{rank}"
+        if red.host_out is not None:
+            model = red.host_out[:plan.P]
+        else:  # the valid columns only: the plan's padding columns are never filled
+            outs = ([red.pass_out[p * plan.local_cols:(p + 1) * plan.local_cols] for p in range(passes)]
+                    if passes > 1 else [red.local_out])
+            model = torch.cat([o[l:l + n] for o in outs for l, _, n in plan.local_segments()])
+    arr = output_sample(model, DUMP_MAX_VALUES // (1 if red.gather else world)).detach().float().cpu().numpy()
+    os.makedirs(dirpath, exist_ok=True)
+    path = os.path.join(dirpath, name + ".npy")
+    np.save(path, np.ascontiguousarray(arr, dtype=np.float32))
+    return [path]
+
+
 def launch_check(args):
     """``--launch-check``: the multi-rank launch path alone, on CPU (gloo) --
     every rank joins the group and all-reduces its rank; rank 0 prints one
@@ -631,7 +699,13 @@ def main(argv=None):
                     help="run the RCCL all-gather even at N=1 (world-size-1 nccl group)")
     ap.add_argument("--unroll", type=int, default=0, help="kernel variant: loads in flight per thread")
     ap.add_argument("--nt", type=int, default=-1, help="kernel variant: 1 = nontemporal loads")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the side measurements and checks: cpu_baseline, parity vs "
+                         "the oracle, the shader clock, round_with_distances, the N>1 overlap diagnostics")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the averaged model of the last timed step as DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of column blocks when it is larger than 32 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--graph", action="store_true", help="N=1: replay each step from a captured hipGraph")
     ap.add_argument("--traffic-json", default="", help="PMC traffic summary (profiles/*.json) to attach")
     ap.add_argument("--host-out", action="store_true",
@@ -905,21 +979,26 @@ def main(argv=None):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         kernel_ms_max = float(t[0])
 
-    diagnostics = None
-    if world > 1 and red.gather:
-        diagnostics = overlap_diagnostics(red, w_dev, args.steps, elapsed_max)
-        if chunk_sweep is not None:
-            diagnostics["chunk_sweep"] = chunk_sweep
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, red, passes=passes, rank=rank, world=world)
 
-    parity = sampled_parity(red, weights, passes=passes, pass_cols=red.plan.local_cols if passes > 1 else 0)
-    if red.gather:
-        parity["reassembly_checksums_ok"] = reassembly_checksums(red, dist, dev)
-        parity["ok"] = parity["ok"] and parity["reassembly_checksums_ok"]
-    if use_pg:
-        ok = torch.tensor([1.0 if parity["ok"] else 0.0], device=dev)
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-        parity["ok"] = bool(ok.item() == 1.0)
-        parity["ranks"] = world
+    diagnostics = None
+    if args.full and world > 1 and red.gather:
+        diagnostics = overlap_diagnostics(red, w_dev, args.steps, elapsed_max)
+    if chunk_sweep is not None:  # the warm-up's own record: nothing more is run for it
+        diagnostics = {**(diagnostics or {}), "chunk_sweep": chunk_sweep}
+
+    parity = None
+    if args.full:
+        parity = sampled_parity(red, weights, passes=passes, pass_cols=red.plan.local_cols if passes > 1 else 0)
+        if red.gather:
+            parity["reassembly_checksums_ok"] = reassembly_checksums(red, dist, dev)
+            parity["ok"] = parity["ok"] and parity["reassembly_checksums_ok"]
+        if use_pg:
+            ok = torch.tensor([1.0 if parity["ok"] else 0.0], device=dev)
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+            parity["ok"] = bool(ok.item() == 1.0)
+            parity["ranks"] = world
 
     if rank == 0:
         P_done = P_pass * passes if passes > 1 else P_global
@@ -987,8 +1066,13 @@ def main(argv=None):
             # the whole step against the node's HBM-read roofline (N x 8 TB/s):
             # north_star's "fraction of the HBM-read roofline" at N GPUs
             "step_frac_of_node_hbm": round(value / (world * HBM_PEAK_GBS), 4),
-            "parity": parity,
         }
+        if parity is not None:
+            out["parity"] = parity
+        if args.dump_outputs:
+            out["outputs"] = {"dir": args.dump_outputs, "dtype": "float32",
+                              "sample": f"whole model up to {DUMP_MAX_VALUES} values per run, else seeded blocks of "
+                                        f"{DUMP_BLOCK} columns (bench.output_sample)"}
         if rehearsal:
             out["rehearsal"] = ("CPU + gloo with a torch stand-in for the HIP kernel: exercises the multi-rank "
                                 "machinery only; NOT a measurement")
@@ -1000,26 +1084,27 @@ def main(argv=None):
         if world > 1 or plan_world > 1:
             out["north_star"] = north_star_block(args.workload, plan_world, roofline, out["step_frac_of_node_hbm"],
                                                  args.scaling, measured_world=world)
-        if not rehearsal and world == 1 and passes == 1:
+        if args.full and not rehearsal and world == 1 and passes == 1:
             # the shader clock the chip held under the timed kernel's load (same launches, after
             # the timed region): box-to-box spread in GB/s vs DVFS, by measurement
             clk = _clock_entry(lambda: red_step(w_dev))
             out["clock_mhz"] = clk["clock_mhz"]
             if roofline is not None:
                 roofline["clock"] = clk["clock"]
-        if (not rehearsal and world == 1 and passes == 1 and plan_world == 1 and K <= 1024
+        if (args.full and not rehearsal and world == 1 and passes == 1 and plan_world == 1 and K <= 1024
                 and red.plan.chunks == 1):
             try:  # a side measurement: never the reason the bench line is missing
                 out["round_with_distances"] = fused_round(red, w_dev)
             except Exception as e:  # noqa: BLE001
                 out["round_with_distances"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu_baseline and world > 1:
+        want_cpu_baseline = args.full and not args.no_cpu_baseline
+        if want_cpu_baseline and world > 1:
             # the bench contract times the CPU baseline on rank 0 at N = 1 only:
             # an N-GPU line points at that run instead of spending 10-30 s of
             # the job's host time on the same number again
             out["cpu_baseline"] = {"value": None, "n_gpus_in_run": world,
                                    "note": "timed at N = 1 only (rank 0 of the 1-GPU run's line)"}
-        elif not args.no_cpu_baseline:
+        elif want_cpu_baseline:
             # on rank 0 after the timed region and the parity checks: the
             # workload's own K x P while its rows fit a bounded host sample
             # (<= 10 GB: the target); cfg5's 400 GB is timed on a P-slice

@@ -18,7 +18,7 @@ if [[ "${SKIP_TESTS:-0}" != 1 ]]; then
   echo "[gpu_check] smoke ok" | tee -a "$OUT/progress.log"
 fi
 
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "[gpu_check] bench ok: $(cat "$OUT/bench.json")" | tee -a "$OUT/progress.log"
 
 if [[ "${E2E:-0}" == 1 ]]; then

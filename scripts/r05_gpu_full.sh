@@ -13,7 +13,7 @@ if [[ "${SKIP_TESTS:-0}" != 1 ]]; then
   log "pytest -m gpu ok: $(tail -1 "$OUT/pytest_gpu.log")"
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
   log "smoke ok: $(tail -1 "$OUT/smoke.log")"
-  timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   log "bench ok: $(cut -c1-200 "$OUT/bench.json")"
 fi
 for MPW in 16 1; do

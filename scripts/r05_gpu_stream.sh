@@ -23,7 +23,7 @@ if [[ "${SKIP_PROBES:-0}" != 1 ]]; then
   log "stream shards ok: $(tail -1 "$OUT/stream_shards.jsonl")"
 fi
 if [[ "${SKIP_BENCH:-0}" != 1 ]]; then
-  timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   log "bench ok: $(cut -c1-300 "$OUT/bench.json")"
 fi
 if [[ "${SKIP_PMC:-0}" != 1 ]]; then

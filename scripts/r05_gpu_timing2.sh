@@ -10,12 +10,12 @@ log() { echo "[r05] $(date -u +%T) $*" | tee -a "$OUT/progress.log"; }
 summ() { python -c "import json,sys;d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{\"metric')][0]);r=d['roofline'];print(d['value'],d['ms_per_step'],r['frac'],r['avg_launch_ms'],d.get('clock_mhz'))" "$1"; }
 log start
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline > "$OUT/bench_n1_$i.json" 2> "$OUT/bench_n1_$i.err"
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$OUT/bench_n1_$i.json" 2> "$OUT/bench_n1_$i.err"
   log "bench n1 #$i: $(summ "$OUT/bench_n1_$i.json")"
 done
 for SC in "8 4" "8 2" "4 4" "2 8" "8 8"; do
   set -- $SC
-  timeout -k 10 180 python bench.py --shard-of $1 --chunks $2 --no-cpu-baseline > "$OUT/bench_s$1_c$2.json" 2> "$OUT/bench_s$1_c$2.err"
+  timeout -k 10 180 python bench.py --full --shard-of $1 --chunks $2 --no-cpu-baseline > "$OUT/bench_s$1_c$2.json" 2> "$OUT/bench_s$1_c$2.err"
   log "bench shard-of $1 chunks $2: $(summ "$OUT/bench_s$1_c$2.json")"
 done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_n1" -o run \

@@ -191,7 +191,7 @@ def test_cpu_rehearsal_line_has_chunk_sweep(n):
     the candidates) and the parity checks of the gathered model -- the same
     line the driver's N-GPU run prints.  The CPU baseline is timed at N = 1
     only (the bench contract); the N-GPU line says so."""
-    r = _run_bench("--gpus", str(n), "--cpu-rehearsal", "--steps", "2", "--warmup", "1", timeout=300)
+    r = _run_bench("--gpus", str(n), "--cpu-rehearsal", "--full", "--steps", "2", "--warmup", "1", timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -229,15 +229,60 @@ def test_north_star_block_carries_the_written_prediction():
 
 
 def test_cpu_rehearsal_one_rank_times_the_cpu_baseline():
-    """At N = 1 rank 0 times the reference's CPU loop after the timed region:
-    both layouts, the affinity-thread value and the value at the job's share."""
-    r = _run_bench("--gpus", "1", "--cpu-rehearsal", "--steps", "2", "--warmup", "1", timeout=300)
+    """At N = 1 rank 0 times the reference's CPU loop after the timed region
+    (``--full``): both layouts, the affinity-thread value and the value at the
+    job's share."""
+    r = _run_bench("--gpus", "1", "--cpu-rehearsal", "--full", "--steps", "2", "--warmup", "1", timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
     cb = json.loads(lines[0])["cpu_baseline"]
     assert cb["value"] > 0 and cb["n_gpus_in_run"] == 1 and cb["value_at_share"] > 0
     assert {lay["layout"] for lay in cb["layouts"]} >= {"flat", "model-shaped (mnist_lr)"}
+
+
+def test_plain_run_is_lean_and_dumps_the_model(tmp_path):
+    """A plain run prints the contract keys and none of the ``--full`` side
+    measurements; ``--steps`` is the number of timed steps; ``--dump-outputs``
+    writes the averaged model of the last step (float32), the same bits on a
+    second run and equal to the oracle on host-regenerated inputs."""
+    import mfl_amd
+    outs = []
+    for d in ("a", "b"):
+        r = _run_bench("--gpus", "1", "--cpu-rehearsal", "--steps", "3", "--warmup", "1",
+                       "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert out["metric"] == bench.METRIC and out["unit"] == "GB/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32"
+    K, P, _ = bench.WORKLOADS["rehearsal_small"]
+    # value and ms_per_step are one measurement: bytes of `steps` steps over their time
+    assert out["rehearsal_value"] == pytest.approx(bench.algorithmic_bytes(K, P) / out["ms_per_step"] / 1e6,
+                                                  rel=1e-3 + 0.5e-4 / out["ms_per_step"],
+                                                  abs=0.006)  # ms_per_step is rounded to 1e-4 ms, value to 0.01 GB/s
+    for key in ("cpu_baseline", "parity", "round_with_distances", "clock_mhz", "diagnostics"):
+        assert key not in out, key
+    a, b = np.load(tmp_path / "a" / "model.npy"), np.load(tmp_path / "b" / "model.npy")
+    assert a.dtype == np.float32 and a.shape == (P,)
+    assert a.tobytes() == b.tobytes()
+    w = mfl_amd.sample_weights(synthetic.sample_counts(K))
+    assert a.tobytes() == bench._oracle_window(K, w, 0, P).tobytes()
+
+
+def test_output_sample_is_fixed_and_bounded():
+    t = torch.arange(1_000_003, dtype=torch.float32)
+    assert bench.output_sample(t, max_values=1_000_003) is t
+    s = bench.output_sample(t, max_values=64 * 100, block=64)
+    assert s.numel() == 64 * 100 and torch.equal(s, bench.output_sample(t.clone(), max_values=64 * 100, block=64))
+    assert s[0] == 0 and s[-1] == 1_000_002  # the first and the last column
+    rows = s.view(100, 64)
+    assert torch.equal(rows[:, 1:] - rows[:, :-1], torch.ones(100, 63))  # whole blocks
+    assert bool((rows[1:-1, 0] % 64 == 0).all()) and bool((rows[2:-1, 0] > rows[1:-2, 0]).all())
+    assert bench.DUMP_MAX_VALUES * 4 + 128 <= 64 * 2**20
 
 
 def test_chunk_candidates():

@@ -167,10 +167,40 @@ def test_cfg5_full_size_single_gpu_passes():
     torch.cuda.empty_cache()
     root = Path(__file__).resolve().parents[1]
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--workload", "synthetic_1000x100m", "--steps", "1",
-                        "--warmup", "0", "--no-cpu-baseline"], capture_output=True, text=True, timeout=110,
+                        "--warmup", "0", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=110,
                        env=dict(os.environ), cwd=str(root))
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["config"]["passes"] == 2 and line["config"]["P_per_gpu"] == 100_000_000, line["config"]
     assert line["parity"]["ok"], line["parity"]
     assert line["parity"]["columns_checked"] >= 2 * 3 * 2048
+
+
+def test_bench_plain_run_dumps_the_timed_model(tmp_path):
+    """A plain ``bench.py`` run (cfg2: 10 x 1,206,590, the whole model fits the
+    dump) carries none of the ``--full`` side measurements, times exactly
+    ``--steps`` steps, and ``--dump-outputs`` writes the averaged model of the
+    last timed step: float32, bit for bit the oracle's on host-regenerated
+    inputs."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parents[1]
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--workload", "femnist_cnn",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True,
+                       text=True, timeout=110, env=dict(os.environ), cwd=str(root))
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    K, P = 10, 1_206_590
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "f32" and line["unit"] == "GB/s"
+    # value and ms_per_step are one measurement (ms_per_step is rounded to 1e-4 ms, value to 0.01 GB/s)
+    assert line["value"] == pytest.approx((4 * K * P + 4 * P + 4 * K) / line["ms_per_step"] / 1e6,
+                                          rel=1e-3 + 0.5e-4 / line["ms_per_step"], abs=0.006)
+    for key in ("cpu_baseline", "parity", "round_with_distances", "clock_mhz"):
+        assert key not in line, key
+    got = np.load(tmp_path / "model.npy")
+    assert got.dtype == np.float32 and got.shape == (P,)
+    w = mfl_amd.sample_weights(synthetic.sample_counts(K))
+    _bits(got, O.reduce_f32(synthetic.client_columns_numpy(K, 0, P), w), "bench.py --dump-outputs model")
