@@ -436,6 +436,58 @@ int fedavg_device_round_f32(const int64_t* client_ptrs, int64_t ptr_ld, const in
                             int64_t partial_elems, double* sumsq, float* int_scratch, int64_t scratch_elems,
                             void* host_ws, void* dev_ws, int64_t ws_bytes, void* stream);
 
+/*
+ * The client's per-iteration statistics (Client.train, client.py:52-86) in one
+ * pass per tensor list.  `cur` is a list of device tensors -- a model's
+ * params (client.py:52, :76) or their grads (:57, :69) -- given as a HOST key
+ * table: cur_ptrs[j] the device address of tensor j (fp32, 4-B aligned),
+ * key_numel[j] its elements, key_offset[j] its element offset in `snap`, a
+ * multiple of 4 (FEDAVG_EALIGN otherwise).  snap : [P] fp32 DEVICE, 16-B
+ * aligned, the flattened list as it was one step earlier (last_w / last_grads,
+ * :86).  Per element the pass forms d = fl32(cur - snap), the fp32 difference
+ * of `w - last_w` (:78) and `grads - last_grads` (:82), and
+ *   stats[0] = the number of NaN elements of cur (torch.isnan(grads).sum(), :71)
+ *   stats[1] = sum cur^2   (norm(grads), norm(last_w) of :71 = fl32(sqrt()))
+ *   stats[2] = sum d^2     (norm(w - last_w), norm(grads - last_grads))
+ *   stats[3] = 0
+ * with the squares (exact) and the sums in fp64, added in a fixed order
+ * (per-workgroup partials, then one finalize launch; no floating-point
+ * atomics: the same bits run to run), and stores snap = cur (:86).
+ * has_snap == 0: there is no earlier step (:52, :57): snap is written only,
+ * stats[2] = 0.  A 16-B aligned tensor is read with 16-B loads, any other
+ * element by element, with identical results.  stats : 4 doubles, DEVICE;
+ * partials : fedavg_client_stats_partials doubles of device scratch; the key
+ * table with its unit prefix sum is staged through host_ws (pinned) into dev_ws
+ * (device), both fedavg_client_stats_workspace(n_keys) bytes and 16-B aligned;
+ * host_ws must not be rewritten until `stream` has passed the call.  P == 0
+ * (or no elements) writes stats = 0.  Stream-ordered and asynchronous.
+ */
+int64_t fedavg_client_stats_workspace(int64_t n_keys);
+int64_t fedavg_client_stats_partials(const int64_t* key_numel, int64_t n_keys);
+int fedavg_client_stats_f32(const int64_t* cur_ptrs, const int64_t* key_numel, const int64_t* key_offset,
+                            int64_t n_keys, float* snap, int64_t P, int has_snap, double* partials,
+                            int64_t partial_elems, double* stats, void* host_ws, void* dev_ws, int64_t ws_bytes,
+                            void* stream);
+/*
+ * The running rho / beta of client.py:78-84 kept on the device, no host sync.
+ *   state   : {rho, beta, has_rho, has_beta} doubles, DEVICE, zero-initialised
+ *             (has_* = 0: still None, :46); rho and beta hold fp32 values;
+ *   w_stats : the record of this iteration's weight pass (:76 against last_w);
+ *   g_stats : the record of this iteration's gradient pass (:69 against last_grads);
+ *   abs_dloss = |loss - last_loss| of :78, the Python double.
+ * With n_w = fl32(sqrt(w_stats[2])) and n_g = fl32(sqrt(g_stats[2])):
+ *   rho_tmp  = fl32(fl32(1 / n_w) * fl32(abs_dloss))
+ *              (python_float / fp32_tensor is Tensor.__rtruediv__ =
+ *              self.reciprocal() * other, the scalar rounded to fp32)       :78
+ *   beta_tmp = fl32(n_g / n_w)                                              :82
+ * each operation rounded once to fp32, then the reference's
+ * `if not x or tmp > x: x = tmp` (:79, :83): x = tmp when x is unset, x == 0
+ * or tmp > x.  A NaN tmp therefore replaces an unset or zero x and then
+ * stays; it never replaces a set non-zero x.
+ */
+int fedavg_client_track(double* state, const double* w_stats, const double* g_stats, double abs_dloss,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ Layers:
   distributed              P-sharded multi-GPU reduce + RCCL all-gather
   multi                    one process, N GPUs: host rounds by columns over N PCIe links
   fpf                      FPF2 bookkeeping (local_w_diffs / A_mat / G_mat) in HBM
+  client_stats             Client.train's rho / beta / guard statistics, one fused pass per step
 """
 from ._lib import FedAvgLibraryError, library_path
 from .aggregate import (
@@ -32,6 +33,8 @@ from .reduce import ALIGN_ELEMS, client_sqdist, reduce_packed, reduce_tensors, r
 from .session import RoundSession
 from .multi import ShardedAggregator, ShardedRoundSession, sharded_aggregator
 from .fpf import FPFTracker
+from . import client_stats
+from .client_stats import ClientStepStats, client_train
 
 __all__ = [
     "FedAvgLibraryError",
@@ -59,4 +62,7 @@ __all__ = [
     "ShardedRoundSession",
     "sharded_aggregator",
     "FPFTracker",
+    "client_stats",
+    "ClientStepStats",
+    "client_train",
 ]

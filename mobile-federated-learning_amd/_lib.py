@@ -69,6 +69,11 @@ SIGNATURES = {
     "fedavg_upload_shard": (_c_int, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _vp]),
     "fedavg_f32_schedule": (_c_int, [_c_i64, _c_i64, _vp, _vp, _vp, _vp]),
     "fedavg_f32_schedule_ld": (_c_int, [_c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp]),
+    "fedavg_client_stats_workspace": (_c_i64, [_c_i64]),
+    "fedavg_client_stats_partials": (_c_i64, [_vp, _c_i64]),
+    "fedavg_client_stats_f32": (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp,
+                                         _c_i64, _vp]),
+    "fedavg_client_track": (_c_int, [_vp, _vp, _vp, ctypes.c_double, _vp]),
 }
 
 # exported only by libfedavg_amd_probe.so (include/fedavg_amd_tuning.h)

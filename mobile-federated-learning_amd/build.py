@@ -4,7 +4,8 @@
 
 Compiles the HIP translation units in ``csrc/`` (``fedavg_reduce.hip``:
 production kernels + C ABI; ``fedavg_dist.hip``: the distance pass; FPF,
-transfer, device packing and zero-copy segment kernels) and
+transfer, device packing, zero-copy segment kernels and the client's
+per-iteration statistics) and
 ``csrc/fedavg_host.cpp`` (native host packer) in parallel with hipcc for
 ``--offload-arch=gfx950`` and links them into ``lib/libfedavg_amd.so`` inside
 the package (in-tree, so the built library travels with the repo snapshot to
@@ -31,7 +32,7 @@ CSRC_DIR = PKG_DIR / "csrc"
 # translation units of libfedavg_amd.so, compiled in parallel then linked
 HIP_SOURCES = [CSRC_DIR / "fedavg_reduce.hip", CSRC_DIR / "fedavg_dist.hip",
                CSRC_DIR / "fedavg_fpf.hip", CSRC_DIR / "fedavg_xfer.hip", CSRC_DIR / "fedavg_pack.hip",
-               CSRC_DIR / "fedavg_segments.hip"]
+               CSRC_DIR / "fedavg_segments.hip", CSRC_DIR / "fedavg_client.hip"]
 PROBE_SOURCES = [CSRC_DIR / "fedavg_variants.hip"]  # probe library only
 CSRC_HOST = CSRC_DIR / "fedavg_host.cpp"
 CSRC_COMMON = CSRC_DIR / "common.hpp"

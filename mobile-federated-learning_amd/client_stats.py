@@ -1,0 +1,321 @@
+"""The client's per-iteration statistics (``Client.train``, client.py:52-86) on the GPU.
+
+Next to forward and backward the reference's local loop flattens the
+gradients and the weights every iteration (``torch.cat``, :69, :76), tests
+them (:71: NaN count, ``norm(grads)`` against ``lr * ratio * norm(last_w)``)
+and tracks ``rho`` and ``beta`` (:78-84) from ``norm(w - last_w)`` and
+``norm(grads - last_grads)``: about a dozen passes over the model and six to
+eight blocking tensor truth tests.  :class:`ClientStepStats` does the same
+bookkeeping with one fused pass over the gradients and one over the weights
+(``fedavg_client_stats_f32``: NaN count, sum of squares, squared distance to
+the previous step's snapshot, snapshot update) and keeps rho / beta on the
+device (``fedavg_client_track``), with ONE host sync per local iteration (the
+:71 guard, which decides whether the optimizer steps).
+
+The norms are fl32(sqrt()) of fp64 sums of exact squares, i.e. the exactly
+rounded values of what the reference's fp32 ``torch.norm`` approximates; rho
+and beta then follow in the reference's fp32 arithmetic.
+
+``stats="torch"`` computes the same quantities with the reference's own torch
+expressions on whatever device the parameters are on; it is what CPU
+parameters and models with a non-fp32 parameter get under ``stats="auto"``.
+
+:func:`client_train` is ``Client.train`` written against this class and
+:func:`patch` binds it to a ``Client`` class (opt in; ``install()`` does not).
+"""
+from __future__ import annotations
+
+import math
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib
+
+ALIGN = 4  # snapshot key offsets are multiples of 4 elements (16 B)
+
+# rec: one device record of doubles, read back in one D2H
+_W, _G, _STATE, _LOSS, _REC = 0, 4, 8, 12, 16
+
+
+def _fused_ok(params) -> bool:
+    return bool(params) and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in params) and \
+        len({p.device for p in params}) == 1
+
+
+class ClientStepStats:
+    """Snapshots, key tables, workspaces and the running rho / beta of one
+    ``Client.train`` call.
+
+    ``begin()`` after the prologue's backward (:52-57), then per local
+    iteration ``after_backward()`` (:69-71, the one sync; ``True`` = the guard
+    trips) and ``after_step()`` (:76-86, no sync); ``result()`` at the end.
+    ``trace(stage, w, g, loss)`` receives clones of the flattened weights and
+    gradients at every call (``g`` is ``None`` where there is none yet).
+    """
+
+    def __init__(self, params, *, stream=None, stats="auto", trace=None):
+        self.params = list(params)
+        if stats not in ("auto", "hip", "torch"):
+            raise ValueError(f"stats must be 'auto', 'hip' or 'torch', not {stats!r}")
+        fused = _fused_ok(self.params)
+        if stats == "hip" and not fused:
+            raise TypeError("stats='hip' needs contiguous fp32 parameters on one GPU")
+        self.mode = "hip" if (fused and stats != "torch") else "torch"
+        self.trace = trace
+        self.stream = stream
+        self.host_syncs = 0
+        self.loss = None  # the current iteration's loss as a Python float (after after_backward)
+        self._begun = False
+        if self.mode == "hip":
+            self._init_hip()
+        else:
+            self._last_w = self._last_grads = self._grads = None
+            self._rho = self._beta = None
+
+    # ------------------------------------------------------------------ fused
+    def _init_hip(self):
+        self.lib = _lib.load()
+        self.device = self.params[0].device
+        n = len(self.params)
+        self._numel = np.array([p.numel() for p in self.params], dtype=np.int64)
+        padded = (self._numel + (ALIGN - 1)) // ALIGN * ALIGN
+        self._offset = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
+        self.P = int(padded.sum())
+        self._ptrs = {"w": np.array([p.data_ptr() for p in self.params], dtype=np.int64),
+                      "g": np.zeros(n, dtype=np.int64)}
+        with torch.cuda.device(self.device):
+            nparts = int(self.lib.fedavg_client_stats_partials(self._numel.ctypes.data, n))
+            self._ws_bytes = int(self.lib.fedavg_client_stats_workspace(n))
+            self._snap = {k: torch.zeros(max(self.P, ALIGN), dtype=torch.float32, device=self.device) for k in "wg"}
+            self._partials = {k: torch.empty(max(nparts, 1), dtype=torch.float64, device=self.device) for k in "wg"}
+            self._host_ws = {k: torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, pin_memory=True) for k in "wg"}
+            self._dev_ws = {k: torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, device=self.device)
+                            for k in "wg"}
+            self._rec = torch.zeros(_REC, dtype=torch.float64, device=self.device)
+            self._rec_host = torch.zeros(_REC, dtype=torch.float64, pin_memory=True)
+            self._ws_free = {k: None for k in "wg"}  # event: the stream has passed the last use of host_ws[k]
+            self._staged = {k: None for k in "wg"}   # the pointer table host_ws[k] holds
+        self._nparts = nparts
+
+    def _torch_stream(self):
+        return self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
+
+    def _grad_ptrs(self):
+        out = self._ptrs["g"]
+        for j, p in enumerate(self.params):
+            g = p.grad
+            if g is None:
+                raise RuntimeError(f"parameter {j} has no grad (client.py:57 / :69 read every param.grad)")
+            if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.device == self.device
+                    and g.numel() == self._numel[j]):
+                raise TypeError(f"parameter {j}: the fused statistics need a contiguous fp32 grad on {self.device}")
+            out[j] = g.data_ptr()
+        return out
+
+    def _pass(self, which: str, has_snap: int):
+        """One fused pass over the weights ('w') or the gradients ('g') on the stream."""
+        ptrs = self._ptrs["w"] if which == "w" else self._grad_ptrs()
+        st = self._torch_stream()
+        ev = self._ws_free[which]
+        table = ptrs.tobytes()
+        if ev is not None and table != self._staged[which]:
+            ev.synchronize()  # host_ws gets new bytes below (already passed after an iteration's sync)
+        self._staged[which] = table
+        with torch.cuda.device(self.device):
+            rc = self.lib.fedavg_client_stats_f32(
+                ptrs.ctypes.data, self._numel.ctypes.data, self._offset.ctypes.data, len(self.params),
+                self._snap[which].data_ptr(), self.P, has_snap, self._partials[which].data_ptr(),
+                self._partials[which].numel(), self._rec.data_ptr() + 8 * (_W if which == "w" else _G),
+                self._host_ws[which].data_ptr(), self._dev_ws[which].data_ptr(), self._host_ws[which].numel(),
+                st.cuda_stream)
+            _lib.check(rc, "fedavg_client_stats_f32", self.lib)
+            if ev is None:
+                ev = self._ws_free[which] = torch.cuda.Event()
+            ev.record(st)
+
+    def _read_record(self):
+        st = self._torch_stream()
+        with torch.cuda.stream(st):
+            self._rec_host.copy_(self._rec, non_blocking=True)
+        st.synchronize()
+        self.host_syncs += 1
+        return self._rec_host.numpy()
+
+    # ----------------------------------------------------------------- common
+    def _flat(self, grads: bool):
+        ts = []
+        for j, p in enumerate(self.params):
+            t = p.grad if grads else p
+            if t is None:
+                raise RuntimeError(f"parameter {j} has no grad (client.py:57 / :69 read every param.grad)")
+            ts.append(t.view(-1))
+        return torch.cat(ts)
+
+    def _emit(self, stage, loss, with_grads=True):
+        if self.trace is not None:
+            with torch.no_grad():
+                self.trace(stage, self._flat(False).detach().clone(),
+                           self._flat(True).detach().clone() if with_grads else None, loss)
+
+    def begin(self, loss=None):
+        """client.py:52-57: the first snapshots of the weights and, after the
+        caller's first backward, of the gradients."""
+        if self.mode == "hip":
+            self._pass("w", 0)
+            self._pass("g", 0)
+        else:
+            self._last_w = self._flat(False)
+            self._last_grads = self._flat(True)
+        self._begun = True
+        self._emit("begin", loss)
+
+    def after_backward(self, loss_tensor, lr, ratio) -> bool:
+        """client.py:69-71: the gradient pass and the guard.  ``True`` when the
+        reference would give up: a NaN in the gradients, a NaN loss, or
+        ``norm(grads) > lr * ratio * norm(last_w)``."""
+        if not self._begun:
+            raise RuntimeError("begin() first")
+        if self.mode == "hip":
+            self._pass("g", 1)
+            st = self._torch_stream()
+            with torch.cuda.stream(st), torch.no_grad():
+                self._rec[_LOSS:_LOSS + 1].copy_(loss_tensor.detach().reshape(1))
+            rec = self._read_record()
+            self.loss = float(rec[_LOSS])
+            n_g = np.float32(math.sqrt(rec[_G + 1])) if not math.isnan(rec[_G + 1]) else np.float32("nan")
+            n_w = np.float32(math.sqrt(rec[_W + 1])) if not math.isnan(rec[_W + 1]) else np.float32("nan")
+            self.grad_norm, self.weight_norm = float(n_g), float(n_w)
+            with np.errstate(all="ignore"):
+                bound = np.float32(lr * ratio) * n_w  # python_float * fp32 tensor: the scalar rounded to fp32
+            trip = bool(rec[_G] > 0 or math.isnan(self.loss) or n_g > bound)
+        else:
+            with torch.no_grad():
+                grads = self._grads = self._flat(True)
+                trip = bool(torch.isnan(grads).sum() > 0 or torch.isnan(loss_tensor)
+                            or torch.norm(grads) > lr * ratio * torch.norm(self._last_w))
+            self.loss = None if trip else loss_tensor.item()
+        self._emit("after_backward", self.loss)
+        return trip
+
+    def after_step(self, loss, last_loss):
+        """client.py:76-86 after ``optimizer.step()``: the weight pass and the
+        running rho / beta; ``loss`` and ``last_loss`` are the Python floats of
+        :75 and :56 / :86."""
+        if self.mode == "hip":
+            self._pass("w", 1)
+            base = self._rec.data_ptr()
+            with torch.cuda.device(self.device):
+                rc = self.lib.fedavg_client_track(base + 8 * _STATE, base + 8 * _W, base + 8 * _G,
+                                                  abs(loss - last_loss), self._torch_stream().cuda_stream)
+            _lib.check(rc, "fedavg_client_track", self.lib)
+        else:
+            with torch.no_grad():
+                w = self._flat(False)
+                rho_tmp = abs(loss - last_loss) / torch.norm(w - self._last_w)
+                if not self._rho or rho_tmp > self._rho:
+                    self._rho = rho_tmp
+                beta_tmp = torch.norm(self._grads - self._last_grads) / torch.norm(w - self._last_w)
+                if not self._beta or beta_tmp > self._beta:
+                    self._beta = beta_tmp
+                self._last_w, self._last_grads = w, self._grads
+        self._emit("after_step", loss)
+
+    def result(self):
+        """``(beta, rho)`` as Python floats (``None`` where no step was taken)."""
+        if self.mode == "hip":
+            rec = self._read_record()
+            rho = float(rec[_STATE]) if rec[_STATE + 2] else None
+            beta = float(rec[_STATE + 1]) if rec[_STATE + 3] else None
+            return beta, rho
+        return (None if self._beta is None else self._beta.item(),
+                None if self._rho is None else self._rho.item())
+
+
+def client_train(self, net, local_iteration, *, keep_on_device=False, stats="auto", trace=None):
+    """``Client.train(self, net, local_iteration)`` (client.py:38-96) with the
+    bookkeeping of :52-86 done by :class:`ClientStepStats`.
+
+    Returns ``(state_dict, loss, beta, rho, acc, cycles)``, or the state_dict
+    and five ``None`` when the :71 guard trips.  ``count`` / ``count_end`` and
+    ``THRESHOLD_GRADS_RATIO`` are the ones of the module that defines
+    ``type(self)`` (the reference's ``client`` module).  ``keep_on_device``
+    returns ``net.state_dict()`` without the ``.cpu()`` of :73 / :96.
+    """
+    mod = sys.modules[type(self).__module__]
+    count, count_end, ratio = mod.count, mod.count_end, mod.THRESHOLD_GRADS_RATIO
+    if self.args.client_optimizer == "sgd":
+        optimizer = torch.optim.SGD(net.parameters(), lr=self.args.lr)
+    else:
+        optimizer = torch.optim.Adam(filter(lambda p: p.requires_grad, net.parameters()), lr=self.args.lr,
+                                     weight_decay=self.args.wd, amsgrad=True)
+    cycles = []
+    x, labels = next(iter(self.local_training_data))
+    x, labels = x.to(self.device), labels.to(self.device)
+    net.train()
+    tracker = ClientStepStats(net.parameters(), stats=stats, trace=trace)
+    last_loss = self.criterion(net(x), labels)
+    torch.nn.utils.clip_grad_norm_(net.parameters(), self.args.clip)
+    last_loss.backward()
+    last_loss = last_loss.item()
+    tracker.begin(last_loss)
+    done = lambda: net.state_dict() if keep_on_device else net.cpu().state_dict()  # noqa: E731
+    for epoch in range(local_iteration):
+        start = count()
+        net.zero_grad()
+        log_probs = net(x)
+        loss = self.criterion(log_probs, labels)
+        torch.nn.utils.clip_grad_norm_(net.parameters(), self.args.clip)
+        loss.backward()
+        cycles.append(count_end() - start)
+        if tracker.after_backward(loss, self.args.lr, ratio):
+            logger = getattr(mod, "logger", None)
+            if logger is not None:
+                logger.warning("grads too large than weights or meets nan with epoch {}".format(epoch))
+            return done(), None, None, None, None, None
+        optimizer.step()
+        loss = tracker.loss
+        tracker.after_step(loss, last_loss)
+        last_loss = loss
+    # local_iteration == 0 leaves log_probs unbound, as in the reference (:93)
+    _, predicted = torch.max(log_probs, -1)
+    correct = predicted.eq(labels).sum()
+    beta, rho = tracker.result()
+    return done(), loss, beta, rho, correct.item() / labels.size(0), sum(cycles) / len(cycles)
+
+
+class _Patch:
+    """Undo handle of :func:`patch` (also a context manager)."""
+
+    def __init__(self, cls, had, old):
+        self.cls, self._had, self._old, self.active = cls, had, old, True
+
+    def undo(self):
+        if self.active:
+            if self._had:
+                setattr(self.cls, "train", self._old)
+            else:
+                delattr(self.cls, "train")
+            self.active = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.undo()
+        return False
+
+
+def patch(cls, *, keep_on_device=False, stats="auto"):
+    """Replace ``cls.train`` (the reference's ``Client.train``) with
+    :func:`client_train`; returns a handle whose ``undo()`` restores the class."""
+    had = "train" in vars(cls)
+    old = vars(cls).get("train")
+
+    def train(self, net, local_iteration):
+        return client_train(self, net, local_iteration, keep_on_device=keep_on_device, stats=stats)
+
+    train.__wrapped_by__ = "mfl_amd.client_stats"
+    setattr(cls, "train", train)
+    return _Patch(cls, had, old)
