@@ -974,21 +974,24 @@ __device__ __forceinline__ double win_sq(typename WinVec<VEC>::T d) {
   return s;
 }
 
+// A tuning knob: an integer the probe library (-DFEDAVG_TUNING) reads from
+// the environment; a caller keeps it in a function-local static, so it is
+// read once, at first use.  The product library is built without
+// FEDAVG_TUNING: there a knob IS its default, a constant, and neither the
+// lookup nor the variable's name is compiled in -- the product chooses no
+// kernel, grid or band edge by environment.
+#ifdef FEDAVG_TUNING
+inline int64_t tuning_knob(const char* name, int64_t dflt) {
+  const char* e = std::getenv(name);
+  return e && e[0] ? static_cast<int64_t>(std::atoll(e)) : dflt;
+}
+#else
+constexpr int64_t tuning_knob(const char*, int64_t dflt) { return dflt; }
+#endif
+
 // __launch_bounds__'s second argument is waves per SIMD: the window's KMAX x
 // VEC registers (+ a quarter more at VEC 1: one square per row per lane
 // before the folds) and ~40 others within 512 / waves
-// rows of the next window the split-row window kernel on packed rows
-// prefetches while the chain runs (reduce_sqdist_winn_kernel; the zero-copy
-// form gained nothing from it); FEDAVG_SPLIT_PREFETCH=0 turns it
-// off and gives 161-368 rows back to the tiles (A/B)
-inline int split_prefetch_rows() {
-  static const int v = [] {
-    const char* e = std::getenv("FEDAVG_SPLIT_PREFETCH");
-    return e && e[0] == '0' ? 0 : 8;
-  }();
-  return v;
-}
-
 constexpr int win_min_waves(int kmax, int vec) {
   const int regs = kmax * vec + (vec == 1 ? kmax / 4 : 0);
   return regs <= 88 ? 4 : (regs <= 128 ? 3 : (regs <= 216 ? 2 : 1));

@@ -1213,6 +1213,7 @@ int launch_fused_win(const float* clients, int64_t K, int64_t P, int64_t ld, con
 // s_waitcnt vmcnt(0) expcnt(7) lgkmcnt(15) (gfx9 encoding: vmcnt in [3:0] and [15:14])
 constexpr int kWaitVmcnt0 = 0x0F70;
 
+#ifdef FEDAVG_TUNING  // probe library only: production runs the hand-off form below (reduce_sqdist_winf_kernel)
 template <int KH, int VEC, int NSMAX, int PF = 0, int LE = 0, int MODE = 0>
 __global__ __launch_bounds__(64 * NSMAX, win_min_waves(KH, VEC)) void reduce_sqdist_winn_kernel(
     const float* __restrict__ X, int K, int64_t ld, int64_t P, int64_t nwin, const float* __restrict__ W,
@@ -1478,7 +1479,7 @@ int launch_fused_winn(const float* clients, int64_t K, int64_t P, int64_t ld, co
                      grid, sumsq);
   return launch_status(what);
 }
-
+#endif  // FEDAVG_TUNING
 
 // ---------------------------------------------------------------------------
 // Split-row windows with point-to-point hand-offs (round 6).  The same work as
@@ -1956,14 +1957,15 @@ constexpr int64_t kFusedRowsMaxK = 1024;
 // workgroup to 512 rows, 16 beyond (640 x 3M 1.77 vs 2.46 for the two
 // passes; 1000 x 12.5M 9.99 vs 15.05; 520 x 5M 2.71 vs 3.34)
 constexpr int64_t kFusedWinnMinK = 369;
-// (round 5: the barrier form with 8 prefetched rows, split_prefetch_rows)
+// (round 5: the barrier form with 8 prefetched rows, reduce_sqdist_winn_kernel:
+// probe library only since)
 // Round 6: the split windows run reduce_sqdist_winf_kernel (point-to-point
 // hand-offs, broadcast weights) with 8 prefetched rows at <= 8 waves and 16
 // beyond (profiles/r06/winf/, ms, barrier form vs winf: 1000 x 12.5M 9.06 vs
 // 8.02; 999 x 10M+3 7.75 vs 6.44; 600 x 10M 5.13 vs 4.28; 513 x 3M 1.48 vs
 // 1.26; 500 x 11.2M 3.66 vs 3.57; 400 x 10M 2.73 vs 2.60; 370 x 5M 1.25 vs
-// 1.18; every output bit-identical).  FEDAVG_SPLIT_PREFETCH=0 keeps the
-// barrier form without prefetch (A/B).
+// 1.18; every output bit-identical).  The barrier form is a variant of the
+// probe library (fedavg_reduce_sqdist_f32_variant), never a production plan.
 constexpr int kWinfPF8 = 8, kWinfPF16 = 16;
 // With the prefetch the split windows also beat the register-staged tiles at
 // 161-256 and 289-368 rows on long rows (profiles/r05/prefetch/, ms, tiles vs
@@ -1971,8 +1973,8 @@ constexpr int kWinfPF8 = 8, kWinfPF16 = 16;
 // 0.822; 256 x 12M 2.53 vs 2.19; 290 x 5M 1.026 vs 0.998; 310 x 5M 1.092 vs
 // 1.033; 352 x 5M 1.347 vs 1.178; 368 x 5M 1.427 vs 1.228), not at 140 x 5M
 // (0.493 vs 0.529) or 270 x 5M (0.933 vs 0.981), and tie at 200 x 1.2M (18
-// windows per workgroup): below 369 rows they take rounds of >= 24 windows
-// per workgroup, and only with the prefetch on
+// windows per workgroup): below 369 rows they took rounds of >= 24 windows
+// per workgroup
 // Round 6, the hand-off kernel (profiles/r06/winf_bands/, ms, plan then vs
 // winf): 160 x 5M 0.615 vs 0.547; 260 x 5M 0.913 vs 0.851; 270 x 5M 0.939 vs
 // 0.876; 288 x 5M 0.983 vs 0.923 (the old 257-288 gap); 200 x 1.2M (18
@@ -2031,8 +2033,7 @@ inline FusedPlan fused_plan(int64_t K, int64_t P) {
   if (K <= 48) return {kFusedLds, 256, 0};
   if (K <= 64) return {kFusedLds, 128, 0};
   if (K <= 128) return {kFusedLds, 64, 0};
-  if (K >= kFusedWinnLowMinK && K < kFusedWinnMinK &&
-      split_prefetch_rows() > 0) {
+  if (K >= kFusedWinnLowMinK && K < kFusedWinnMinK) {
     const int64_t grid = fused_winf_grid<8, kWinfPF8>(K, P);
     if (grid > 0 && (P + 63) / 64 >= kFusedWinnLowMinPerBlock * grid) return {kFusedWinn, 64, 8};
   }
@@ -2223,6 +2224,12 @@ int sqdist_buf_impl(const float* clients, int64_t K, int64_t P, int64_t ld, cons
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int k = static_cast<int>(K);
   switch (unroll * 100 + cols) {
+    // production (fedavg_client_sqdist_f32, dist_cols): 4 chains at U2 x C16, U4 x C8, U4 x C4; 2 at U8 x C2
+    case 4000216: launch_sqdist<2, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+    case 4000408: launch_sqdist<4, 8, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+    case 4000404: launch_sqdist<4, 4, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+    case 4000802: launch_sqdist<8, 2, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+#ifdef FEDAVG_TUNING  // every other shape: fedavg_client_sqdist_buf, probe library only
     case 408: launch_sqdist<4, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 804: launch_sqdist<8, 4, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 216: launch_sqdist<2, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
@@ -2238,9 +2245,7 @@ int sqdist_buf_impl(const float* clients, int64_t K, int64_t P, int64_t ld, cons
     case 808: launch_sqdist<8, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     // 2 / 4 interleaved fp64 chains per row (codes + 1,000,000 x ACC)
     case 2000216: launch_sqdist<2, 16, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000216: launch_sqdist<2, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 2000408: launch_sqdist<4, 8, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000408: launch_sqdist<4, 8, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 8000216: launch_sqdist<2, 16, true, 1, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 16000216: launch_sqdist<2, 16, true, 1, 16>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     // U = 0: row k + 1 loads while row k is summed (one row of registers each)
@@ -2254,14 +2259,11 @@ int sqdist_buf_impl(const float* clients, int64_t K, int64_t P, int64_t ld, cons
     case 4040208: launch_sqdist<2, 8, true, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 4030308: launch_sqdist<3, 8, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     // narrow column groups for small models (more workgroups per launch)
-    case 4000404: launch_sqdist<4, 4, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 4000804: launch_sqdist<8, 4, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 4000402: launch_sqdist<4, 2, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000802: launch_sqdist<8, 2, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 4000801: launch_sqdist<8, 1, true, 1, 1>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 4001601: launch_sqdist<16, 1, true, 1, 1>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 4000116: launch_sqdist<1, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-#ifdef FEDAVG_TUNING
     // interleaved loads and squares, L loads in flight: + 100000000 x L
     case 204000216: launch_sqdist<2, 16, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 404000216: launch_sqdist<2, 16, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
@@ -2270,7 +2272,7 @@ int sqdist_buf_impl(const float* clients, int64_t K, int64_t P, int64_t ld, cons
     case 404000404: launch_sqdist<4, 4, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 204000408: launch_sqdist<4, 8, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
     case 404000408: launch_sqdist<4, 8, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-#endif
+#endif  // FEDAVG_TUNING
     default: return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", what, unroll, cols);
   }
   rc = launch_status(what);
@@ -2357,9 +2359,7 @@ int64_t fedavg_reduce_sqdist_workspace(int64_t K, int64_t P) {
     if (pl.S == 128) fused = K * fused_grid<128>(K, P, 0);
     if (pl.S == 256) fused = K * fused_grid<256>(K, P, 0);
   } else if (pl.kind == kFusedWinn) {
-    const bool pf = split_prefetch_rows() > 0;
-    fused = K * (pl.slots == 8 ? (pf ? fused_winf_grid<8, kWinfPF8>(K, P) : fused_winn_grid<64, 1, 8>(K, P, 0))
-                               : (pf ? fused_winf_grid<16, kWinfPF16>(K, P) : fused_winn_grid<64, 1, 16>(K, P, 0)));
+    fused = K * (pl.slots == 8 ? fused_winf_grid<8, kWinfPF8>(K, P) : fused_winf_grid<16, kWinfPF16>(K, P));
   } else if (pl.kind == kFusedRs) {
     switch (pl.S * 100 + pl.slots) {
       case 25608: fused = K * fused_rs_grid<256, 8, 0>(K, P, 0); break;
@@ -2410,25 +2410,21 @@ int fedavg_reduce_sqdist_f32(const float* clients, int64_t K, int64_t P, int64_t
       }
     }
     if (pl.kind == kFusedWinn) {
-      const bool pf = split_prefetch_rows() > 0;
-      if (pl.slots == 8 && pf)
+      if (pl.slots == 8)
         return launch_fused_winf<8, kWinfPF8>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, s,
                                               what);
-      if (pl.slots == 8)
-        return launch_fused_winn<64, 1, 8>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s,
-                                           what);
-      if (pf)
-        return launch_fused_winf<16, kWinfPF16>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, s,
-                                                what);
-      return launch_fused_winn<64, 1, 16>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s,
-                                          what);
+      return launch_fused_winf<16, kWinfPF16>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, s,
+                                              what);
     }
-    if (pl.kind == kFusedLds) {
+    if (pl.kind == kFusedLds) {  // K <= 128: one row per thread in the squares (RM 1; launch_fused's RM 2 is the variants')
       if (pl.S == 64)
-        return launch_fused<64>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s, what);
+        return launch_fused_rm<64, false, 0, false, 1>(clients, K, P, ld, weights, out, workspace, workspace_elems,
+                                                       sumsq, 0, s, what);
       if (pl.S == 256)
-        return launch_fused<256>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s, what);
-      return launch_fused<128>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s, what);
+        return launch_fused_rm<256, false, 0, false, 1>(clients, K, P, ld, weights, out, workspace, workspace_elems,
+                                                        sumsq, 0, s, what);
+      return launch_fused_rm<128, false, 0, false, 1>(clients, K, P, ld, weights, out, workspace, workspace_elems,
+                                                      sumsq, 0, s, what);
     }
     switch (pl.S * 100 + pl.slots) {
       case 25608:

@@ -559,14 +559,8 @@ void launch_production_f32(const float* clients, int K, int64_t ld, int64_t P, c
       default: launch_split_ev<8, 1, true>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
     }
   }
-  switch (key) {
-    case 408: launch_split_ev<4, 8, false>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-    case 804: launch_split_ev<8, 4, false>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-    case 802: launch_split_ev<8, 2, false>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-    case 1604: launch_split_ev<16, 4, false>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-    case 1601: launch_split_ev<16, 1, false>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-    default: launch_split_ev<8, 1, false>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-  }
+  // default-policy loads: the Infinity-Cache band, always U16 x C4 (choose_schedule)
+  launch_split_ev<16, 4, false>(clients, K, ld, P, W, out, bpl, s, e0, e1);
 }
 
 // fp32 buffers that are not all 16-B aligned (or an odd row stride): the
@@ -725,17 +719,34 @@ inline int half_key(int key) {
 template <class Op, bool NT>
 void launch_vec_nt(const Schedule& sc, const void* clients, int K, int64_t ld, int64_t P, const void* W, void* out,
                    hipStream_t s) {
-  int key = sc.unroll * 100 + sc.cols;
-  if constexpr (Op::kLanes == 8) key = half_key(key);
-  switch (key) {
-    case 408: launch_vec_split<Op, 4, 8, NT>(clients, K, ld, P, W, out, sc.blocks_per_launch, s); break;
-    case 208: launch_vec_split<Op, 2, 8, NT>(clients, K, ld, P, W, out, sc.blocks_per_launch, s); break;
-    case 804: launch_vec_split<Op, 8, 4, NT>(clients, K, ld, P, W, out, sc.blocks_per_launch, s); break;
-    case 404: launch_vec_split<Op, 4, 4, NT>(clients, K, ld, P, W, out, sc.blocks_per_launch, s); break;
-    case 802: launch_vec_split<Op, 8, 2, NT>(clients, K, ld, P, W, out, sc.blocks_per_launch, s); break;
-    case 801: launch_vec_split<Op, 8, 1, NT>(clients, K, ld, P, W, out, sc.blocks_per_launch, s); break;
-    case 1604: launch_vec_split<Op, 16, 4, NT>(clients, K, ld, P, W, out, sc.blocks_per_launch, s); break;
-    default: launch_vec_split<Op, 16, 1, NT>(clients, K, ld, P, W, out, sc.blocks_per_launch, s); break;
+  // Only what choose_schedule can ask for is instantiated.  Its keys: 801
+  // (K <= 4), 408, 804, 802, 1601 and 1604 with nontemporal loads; the
+  // Infinity-Cache band's default-policy loads come with 1604 alone.  The
+  // packed 16-bit types take them through half_key.
+  const int bpl = sc.blocks_per_launch;
+  const int key = sc.unroll * 100 + sc.cols;
+  if constexpr (Op::kLanes == 8) {
+    if constexpr (!NT) {
+      launch_vec_split<Op, 4, 4, false>(clients, K, ld, P, W, out, bpl, s);
+    } else {
+      switch (half_key(key)) {
+        case 804: launch_vec_split<Op, 8, 4, true>(clients, K, ld, P, W, out, bpl, s); break;
+        case 404: launch_vec_split<Op, 4, 4, true>(clients, K, ld, P, W, out, bpl, s); break;
+        case 802: launch_vec_split<Op, 8, 2, true>(clients, K, ld, P, W, out, bpl, s); break;
+        default: launch_vec_split<Op, 8, 1, true>(clients, K, ld, P, W, out, bpl, s); break;
+      }
+    }
+  } else if constexpr (!NT) {
+    launch_vec_split<Op, 16, 4, false>(clients, K, ld, P, W, out, bpl, s);
+  } else {
+    switch (key) {
+      case 408: launch_vec_split<Op, 4, 8, true>(clients, K, ld, P, W, out, bpl, s); break;
+      case 804: launch_vec_split<Op, 8, 4, true>(clients, K, ld, P, W, out, bpl, s); break;
+      case 802: launch_vec_split<Op, 8, 2, true>(clients, K, ld, P, W, out, bpl, s); break;
+      case 801: launch_vec_split<Op, 8, 1, true>(clients, K, ld, P, W, out, bpl, s); break;
+      case 1604: launch_vec_split<Op, 16, 4, true>(clients, K, ld, P, W, out, bpl, s); break;
+      default: launch_vec_split<Op, 16, 1, true>(clients, K, ld, P, W, out, bpl, s); break;
+    }
   }
 }
 

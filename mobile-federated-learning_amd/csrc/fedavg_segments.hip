@@ -498,7 +498,8 @@ constexpr int kSegFusedRowsPerThread = 8;  // ceil(K * S / 4 / 256) slots per th
 // loads at 350 keys) and, at a key change, for its client addresses before
 // its data loads can start: four dependent latencies per tile, and a small
 // model's tiles change key almost every time.
-// LADDR (round 5, with MAP): the current key's K client addresses live in
+// LADDR (round 5, always and only with MAP; the register form with a map
+// measured slower, HISTORY): the current key's K client addresses live in
 // LDS (after the tile and its average) instead of 8 + 8 int64 registers per
 // thread (this slot's row address and the next key's): each slot reads its
 // row's address with one ds_read_b64 when it issues the tile's loads, and at
@@ -533,19 +534,15 @@ __global__ __launch_bounds__(kBlock, LADDR && S != 32 ? 6 : 1) void reduce_sqdis
   int64_t u = blockIdx.x;
   int64_t j = 0;
   SegKey key{};
-  static_assert(!LADDR || MAP, "LDS addresses come with the unit map");
+  static_assert(LADDR == MAP, "the unit map and the LDS addresses come together");
   int64_t* addr = reinterpret_cast<int64_t*>(gs + S);  // LADDR: [K] client addresses of the current key
   if constexpr (MAP) {
     if (u < units) {
       j = umap[u];
       key = keys[j];
       if (key.kind == kRaw) {
-        if constexpr (LADDR) {
-          if (threadIdx.x < K) addr[threadIdx.x] = ptrs[j * K + threadIdx.x];
-          __syncthreads();
-        } else {
-          load_src(ptrs + j * K, src);
-        }
+        if (threadIdx.x < K) addr[threadIdx.x] = ptrs[j * K + threadIdx.x];
+        __syncthreads();
         cur_key = j;
       }
     }
@@ -608,7 +605,6 @@ __global__ __launch_bounds__(kBlock, LADDR && S != 32 ? 6 : 1) void reduce_sqdis
     int64_t jn = j;
     SegKey keyn = key;
     bool fresh = false;
-    int64_t srcn[LADDR ? 1 : kSegFusedRowsPerThread];
     int64_t addr_next = 0;
     if constexpr (MAP) {
       const int64_t un = u + gridDim.x;
@@ -616,11 +612,7 @@ __global__ __launch_bounds__(kBlock, LADDR && S != 32 ? 6 : 1) void reduce_sqdis
         jn = umap[un];
         keyn = keys[jn];
         if (keyn.kind == kRaw && jn != cur_key) {
-          if constexpr (LADDR) {
-            if (threadIdx.x < K) addr_next = ptrs[jn * K + threadIdx.x];
-          } else {
-            load_src(ptrs + jn * K, srcn);
-          }
+          if (threadIdx.x < K) addr_next = ptrs[jn * K + threadIdx.x];
           fresh = true;
         }
       }
@@ -636,13 +628,7 @@ __global__ __launch_bounds__(kBlock, LADDR && S != 32 ? 6 : 1) void reduce_sqdis
     if constexpr (MAP) {
       j = jn;
       key = keyn;
-      if (fresh) {
-        if constexpr (!LADDR) {
-#pragma unroll
-          for (int m = 0; m < kSegFusedRowsPerThread; ++m) src[m] = srcn[m];
-        }
-        cur_key = jn;
-      }
+      if (fresh) cur_key = jn;
     }
   }
   fused_finish(lds, acc, K, partials);
@@ -967,173 +953,18 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_segwin_kernel(
   }
 }
 
-// Zero-copy split-row windows (round 5): fedavg_dist.hip's
-// reduce_sqdist_winn_kernel on the key / pointer tables, for 257-1024
+// Zero-copy split-row windows (rounds 5-6): fedavg_dist.hip's
+// reduce_sqdist_winf_kernel on the key / pointer tables, for 129-1024
 // device-resident clients (the tiles stop at 256).  A workgroup of ns =
 // ceil(K / 64) waves owns a window of 64 columns of one key; wave h holds
 // clients 64h .. 64h + 63 in registers, one dword per lane.  The chain runs
 // wave by wave in client order, handed over LDS; the last wave stores the
 // average, then every wave squares its rows against it and reloads them from
 // the next window (its 64 client addresses: one vector load per wave, read
-// per row with v_readlane, as the pointer form of the one-wave windows).  A
-// key's ragged last window loads element by element through descriptors
-// ranged to the key.  fp32 keys only (integer keys arrive as fp32 scratch).
-// ---------------------------------------------------------------------------
-template <int NSMAX>
-__global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdist_segwinn_kernel(
-    const SegKey* __restrict__ keys, const int64_t* __restrict__ ptrs, int64_t n_keys, int64_t units, int K,
-    const float* __restrict__ W, float* __restrict__ out, double* __restrict__ partials) {
-  constexpr int KH = 64, WC = 64, NB = 8;
-  const int lane = threadIdx.x & 63;
-  const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ns = __builtin_amdgcn_readfirstlane(static_cast<int>(blockDim.x >> 6));
-  const int r0 = h * KH;
-  const int G = static_cast<int>(gridDim.x);
-  const uint32_t voff = static_cast<uint32_t>(lane) * 4;
-  const bool upper = (lane & 8) != 0;
-  __shared__ __attribute__((aligned(16))) float wl[NSMAX][KH];
-  __shared__ double accl[NSMAX][NB][64];
-  __shared__ float xa[64];
-  for (int i = threadIdx.x; i < ns * KH; i += blockDim.x) wl[i / KH][i % KH] = i < K ? W[i] : -0.0f;
-  double* acc = &accl[h][0][lane];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) acc[64 * b] = 0.0;
-  __syncthreads();
-
-  float x[KH];
-  int64_t pv = 0;  // lane l: client r0 + l's address of the window's key
-  const auto load_ptrs = [&](const int64_t* P) __attribute__((always_inline)) {
-    const gptr<int64_t> q = to_global<int64_t>(P);
-    pv = r0 + lane < K ? q[r0 + lane] : 0;
-  };
-  const auto ptr_of = [&](int i) __attribute__((always_inline)) {
-    int li = i;
-    asm volatile("" : "+s"(li));
-    const uint32_t lo = __builtin_amdgcn_readlane(static_cast<uint32_t>(pv), li);
-    const uint32_t hi = __builtin_amdgcn_readlane(static_cast<uint32_t>(static_cast<uint64_t>(pv) >> 32), li);
-    return reinterpret_cast<const float*>((static_cast<uint64_t>(hi) << 32) | lo);
-  };
-  // a full window: the client's address as the base, the window's start in
-  // soffset, the window's end byte as the record count (0: client >= K)
-  const auto load_fast = [&](int i, uint32_t soff, uint32_t nrec, int Kw) __attribute__((always_inline)) {
-    x[i] = __builtin_bit_cast(
-        float, __builtin_amdgcn_raw_buffer_load_b32(
-                   __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptr_of(i)), 0,
-                                                     r0 + i < Kw ? static_cast<int>(nrec) : 0, 0x00020000),
-                   static_cast<int>(voff), static_cast<int>(soff), 2));
-  };
-  // a key's ragged last window: the descriptor's range is the client's part of it
-  const auto load_slow = [&](int64_t c0, int n, int Kw) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < KH; ++i) {
-      const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptr_of(i) + c0), 0,
-                                                                         r0 + i < Kw ? n * 4 : 0, 0x00020000);
-      x[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, static_cast<int>(voff), 0, 2));
-    }
-  };
-  const int units32 = static_cast<int>(units), nkeys32 = static_cast<int>(n_keys);
-  const auto cols_of = [&](int64_t numel, int w) __attribute__((always_inline)) {
-    const int64_t left = numel - static_cast<int64_t>(w) * WC;
-    return (left >> 31) != 0 ? WC : (static_cast<int>(left) < WC ? static_cast<int>(left) : WC);
-  };
-  int u = static_cast<int>(blockIdx.x), j = 0, n = 0;
-  int64_t c0 = 0;
-  if (u < units32) {
-    j = __builtin_amdgcn_readfirstlane(static_cast<int>(find_key(keys, n_keys, u)));
-    const SegKey key = keys[j];
-    const int w = u - static_cast<int>(key.unit_start);
-    c0 = static_cast<int64_t>(w) * WC;
-    n = cols_of(key.numel, w);
-    load_ptrs(ptrs + static_cast<int64_t>(j) * K);
-    if (n == WC) {
-#pragma unroll
-      for (int i = 0; i < KH; ++i) load_fast(i, static_cast<uint32_t>(c0 * 4), static_cast<uint32_t>((c0 + WC) * 4), K);
-    } else {
-      load_slow(c0, n, K);
-    }
-  }
-  for (; u < units32; u += G) {
-    const int64_t out_off = keys[j].out_offset;
-    const int un = u + G;
-    int jn = j, nn = 0;
-    int64_t c0n = 0;
-    if (un < units32) {
-      while (jn + 1 < nkeys32 && static_cast<int>(keys[jn + 1].unit_start) <= un) ++jn;
-      const SegKey kn = keys[jn];
-      const int w = un - static_cast<int>(kn.unit_start);
-      c0n = static_cast<int64_t>(w) * WC;
-      nn = cols_of(kn.numel, w);
-    }
-    const bool fastn = un < units32 && nn == WC;
-    const uint32_t soffn = static_cast<uint32_t>(c0n * 4), nrecn = static_cast<uint32_t>((c0n + WC) * 4);
-    int Kwn = fastn ? K : 0;
-    asm volatile("" : "+s"(Kwn));
-    if (un < units32) load_ptrs(ptrs + static_cast<int64_t>(jn) * K);  // this window's rows are loaded
-    float a = 0.f;
-    for (int st = 0; st < ns; ++st) {  // the chain, wave by wave in client order
-      if (h == st) {
-        int wo = h * KH;
-        asm volatile("" : "+v"(wo));
-        const float* wp = &wl[0][0] + wo;
-        if (st > 0) a = xa[lane];
-#pragma unroll
-        for (int q = 0; q < KH / 4; ++q) {
-          const f32x4 w4 = *reinterpret_cast<const f32x4*>(wp + 4 * q);
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const int i = 4 * q + jj;
-            if (st == 0 && i == 0) {
-              a = x[0] * w4[0];
-            } else {
-              const float t = x[i] * w4[jj];
-              a = a + t;
-            }
-          }
-        }
-        xa[lane] = a;
-        if (st == ns - 1 && lane < n) out[out_off + c0 + lane] = a;
-      }
-      __syncthreads();
-    }
-    if (h != ns - 1) a = xa[lane];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      double p[8];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const int i = 8 * b + r;
-        const double d = static_cast<double>(x[i] - a);  // fp32 difference, as the reference forms it
-        p[r] = d * d;
-        load_fast(i, soffn, nrecn, Kwn);
-      }
-      const double q01 = fold32(p[0], p[1]), q23 = fold32(p[2], p[3]);
-      const double q45 = fold32(p[4], p[5]), q67 = fold32(p[6], p[7]);
-      acc[64 * b] += fold8(fold16(q01, q23), fold16(q45, q67), upper);
-    }
-    if (un < units32 && !fastn) {
-      int Ks = K;
-      asm volatile("" : "+s"(Ks));
-      load_slow(c0n, nn, Ks);
-    }
-    __syncthreads();  // every wave has read xa before the next window's chain rewrites it
-    j = jn;
-    c0 = c0n;
-    n = nn;
-  }
-  const int row_in = win_batch_row(lane);
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    double sm = acc[64 * b];
-    sm += dpp_move_f64<0xB1, 0xF>(sm);
-    sm += dpp_move_f64<0x4E, 0xF>(sm);
-    sm += dpp_move_f64<0x141, 0xF>(sm);
-    const int row = 8 * b + row_in;
-    if ((lane & 7) == 0 && r0 + row < K) partials[static_cast<int64_t>(r0 + row) * G + blockIdx.x] = sm;
-  }
-}
-
-// Zero-copy split-row windows with point-to-point hand-offs (round 6): the
-// segwinn work on fedavg_dist.hip's reduce_sqdist_winf_kernel protocol -- no
+// per row with v_readlane, as the pointer form of the one-wave windows).
+// fp32 keys only (integer keys arrive as fp32 scratch).
+// Point-to-point hand-offs (round 6; round 5's barrier form measured slower,
+// HISTORY), the rows kernel's protocol -- no
 // workgroup barrier in the window loop (wave h > 0 takes wave h - 1's partial
 // from LDS behind a flag, the last wave publishes the average behind another),
 // a wave waits for its own rows at its turn, the weights come by row
@@ -1144,18 +975,21 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
 // flight (vmcnt counts in issue order); the key table is read through the
 // constant address space (scalar loads: the key walk never waits on vmcnt).
 // Hand-off safety and the bounded polls: see the rows kernel.
-// UNI: every row load takes the client's address + the window's first column
-// as its base and the window's columns as its range, so a key's ragged last
+// Every row load takes the client's address + the window's first column as
+// its base and the window's columns as its range, so a key's ragged last
 // window loads through the same instructions as a full one (lanes past it
-// read 0).  Without it a ragged window reloads every row again after the
-// squares (round 5's form), and the compiler, merging the two load paths,
-// waits for all of a wave's rows at the start of its turn.
+// read 0).  (UNI = false was round 5's separate reload of a ragged window
+// after the squares: the compiler, merging the two load paths, waited for all
+// of a wave's rows at the start of its turn.  The parameter stays for the
+// instances' names.)
+// MODE 8 (probe library only): the rows kernel's timeline stamps.
 template <int NSMAX, int PF, bool UNI = true, int MODE = 0>
 __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdist_segwinf_kernel(
     const SegKey* __restrict__ keys, const int64_t* __restrict__ ptrs, int64_t n_keys, int64_t units, int K,
     const float* __restrict__ W, float* __restrict__ out, double* __restrict__ partials) {
   constexpr int KH = 64, WC = 64, NB = 8, NWV = 4;
   static_assert(PF >= 1 && PF <= KH, "prefetched rows");
+  static_assert(UNI, "one load path for full and ragged windows");
   constexpr int kSpinMax = 1 << 20;  // tight polls, as the rows kernel's
   const int lane = threadIdx.x & 63;
   const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1214,13 +1048,6 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
     const uint32_t hi = __builtin_amdgcn_readlane(static_cast<uint32_t>(static_cast<uint64_t>(pv) >> 32), li);
     return reinterpret_cast<const float*>((static_cast<uint64_t>(hi) << 32) | lo);
   };
-  const auto load_fast = [&](int64_t pv, int i, uint32_t soff, uint32_t nrec, int Kw) __attribute__((always_inline)) {
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_raw_buffer_load_b32(
-                   __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptr_of(pv, i)), 0,
-                                                     r0 + i < Kw ? static_cast<int>(nrec) : 0, 0x00020000),
-                   static_cast<int>(voff), static_cast<int>(soff), 2));
-  };
   const auto load_row = [&](int64_t pv, int i, int64_t c0_, int n_, int Kw) __attribute__((always_inline)) {
     return __builtin_bit_cast(
         float, __builtin_amdgcn_raw_buffer_load_b32(
@@ -1230,14 +1057,6 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   };
   float x[KH];
   float xp[PF];
-  const auto load_slow = [&](int64_t pv, int64_t c0, int n, int Kw) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < KH; ++i) {
-      const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ptr_of(pv, i) + c0), 0,
-                                                                         r0 + i < Kw ? n * 4 : 0, 0x00020000);
-      x[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, static_cast<int>(voff), 0, 2));
-    }
-  };
   const int units32 = static_cast<int>(units), nkeys32 = static_cast<int>(n_keys);
   const auto cols_of = [&](int64_t numel, int w) __attribute__((always_inline)) {
     const int64_t left = numel - static_cast<int64_t>(w) * WC;
@@ -1267,16 +1086,8 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
       locate(u + G, jn, c0n, nn);
       pvn = load_ptrs(ptrs + static_cast<int64_t>(jn) * K);
     }
-    if constexpr (UNI) {
 #pragma unroll
-      for (int i = 0; i < KH; ++i) x[i] = load_row(pv0, i, c0, n, K);
-    } else if (n == WC) {
-#pragma unroll
-      for (int i = 0; i < KH; ++i)
-        x[i] = load_fast(pv0, i, static_cast<uint32_t>(c0 * 4), static_cast<uint32_t>((c0 + WC) * 4), K);
-    } else {
-      load_slow(pv0, c0, n, K);
-    }
+    for (int i = 0; i < KH; ++i) x[i] = load_row(pv0, i, c0, n, K);
   }
   // the first window's rows in: without this wait the compiler merges the
   // prologue's pending row loads into the loop's state and waits for ALL of
@@ -1286,13 +1097,11 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   for (; u < units32; u += G, ++seq) {
     const int64_t out_off = kc[j].out_offset;
     const int un = u + G, unn = un + G;
-    const bool fastn = un < units32 && nn == WC;
-    const uint32_t soffn = static_cast<uint32_t>(c0n * 4), nrecn = static_cast<uint32_t>((c0n + WC) * 4);
-    int Kwn = (UNI ? un < units32 : fastn) ? K : 0;
+    int Kwn = un < units32 ? K : 0;
     asm volatile("" : "+s"(Kwn));
     stamp(0);
 #pragma unroll
-    for (int i = 0; i < PF; ++i) xp[i] = UNI ? load_row(pvn, i, c0n, nn, Kwn) : load_fast(pvn, i, soffn, nrecn, Kwn);
+    for (int i = 0; i < PF; ++i) xp[i] = load_row(pvn, i, c0n, nn, Kwn);
     // the turn
     float a = -0.0f;  // fl32(-0.0 + p) is p, bit for bit
     if (h > 0) {
@@ -1347,16 +1156,11 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
         if (i < PF)
           x[i] = xp[i < PF ? i : 0];
         else
-          x[i] = UNI ? load_row(pvn, i, c0n, nn, Kwn) : load_fast(pvn, i, soffn, nrecn, Kwn);
+          x[i] = load_row(pvn, i, c0n, nn, Kwn);
       }
       const double q01 = fold32(p[0], p[1]), q23 = fold32(p[2], p[3]);
       const double q45 = fold32(p[4], p[5]), q67 = fold32(p[6], p[7]);
       acc[64 * b] += fold8(fold16(q01, q23), fold16(q45, q67), upper);
-    }
-    if (!UNI && un < units32 && !fastn) {
-      int Ks = K;
-      asm volatile("" : "+s"(Ks));
-      load_slow(pvn, c0n, nn, Ks);
     }
     __builtin_amdgcn_s_setprio(0);
     stamp(4);
@@ -1386,82 +1190,46 @@ constexpr int64_t kSegSplitMaxK = 1024;  // the split-row windows' reach (16 wav
 // workgroups of the split-row window launch over `units` windows (0: not resident)
 constexpr int kSegWinfPF8 = 8, kSegWinfPF16 = 16;  // prefetched rows at <= 8 / 16 waves
 
-// FEDAVG_SEGWINN_BARRIER=1 keeps round 5's barrier form of the zero-copy
-// split windows (A/B); the hand-off form is the default
-inline bool seg_barrier_windows() {
-  static const bool on = [] {
-    const char* e = std::getenv("FEDAVG_SEGWINN_BARRIER");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
-// FEDAVG_SEGWINF_TWO_PATHS=1: the hand-off kernel with round 5's separate
-// ragged-window reload (A/B against the uniform row loads)
-inline bool seg_split_two_paths() {
-  static const bool on = [] {
-    const char* e = std::getenv("FEDAVG_SEGWINF_TWO_PATHS");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
-// FEDAVG_SEGWINF_STAMPS=1: the hand-off kernel's timeline build (MODE 8;
-// the partials grow by winn_stamp_elems)
+// Probe library only (tuning_knob, common.hpp): FEDAVG_SEGWINF_STAMPS=1
+// launches the hand-off kernel's timeline build (MODE 8; the partials grow by
+// winn_stamp_elems)
 inline bool seg_split_stamps() {
-  static const bool on = [] {
-    const char* e = std::getenv("FEDAVG_SEGWINF_STAMPS");
-    return e && e[0] == '1';
-  }();
+  static const bool on = tuning_knob("FEDAVG_SEGWINF_STAMPS", 0) == 1;
   return on;
 }
 
 inline int64_t segwinn_blocks(int64_t K, int64_t units) {
   const int ns = static_cast<int>((K + 63) / 64);
-  const bool bar = seg_barrier_windows();
-  int64_t res = ns <= 8 ? (bar ? resident_blocks(reduce_sqdist_segwinn_kernel<8>, 64 * ns)
-                               : resident_blocks(reduce_sqdist_segwinf_kernel<8, kSegWinfPF8>, 64 * ns))
-                        : (bar ? resident_blocks(reduce_sqdist_segwinn_kernel<16>, 64 * ns)
-                               : resident_blocks(reduce_sqdist_segwinf_kernel<16, kSegWinfPF16>, 64 * ns));
+  int64_t res = ns <= 8 ? resident_blocks(reduce_sqdist_segwinf_kernel<8, kSegWinfPF8>, 64 * ns)
+                        : resident_blocks(reduce_sqdist_segwinf_kernel<16, kSegWinfPF16>, 64 * ns);
   // workgroups per CU: the resident ones rounded down to a power of two, as
-  // the rows kernel's grid (round 6, the hand-off kernel, resnet18_gn-shaped
-  // rounds, profiles/r06/zc_percu/, ms: 257 clients 3 per CU 2.70 vs 2 2.32;
-  // 300 2.83 vs 2.47; 129 clients 5 per CU 1.53 vs 4 1.47; 500 equal; the
-  // barrier form's rule was 3 at 5 waves); FEDAVG_SEGWINN_PER_CU caps it
-  static const int64_t per_cu_env = [] {
-    const char* e = std::getenv("FEDAVG_SEGWINN_PER_CU");
-    return e && e[0] ? static_cast<int64_t>(std::atoll(e)) : int64_t(0);
-  }();
+  // the rows kernel's grid (round 6, resnet18_gn-shaped rounds,
+  // profiles/r06/zc_percu/, ms: 257 clients 3 per CU 2.70 vs 2 2.32; 300 2.83
+  // vs 2.47; 129 clients 5 per CU 1.53 vs 4 1.47; 500 equal); the probe
+  // library's FEDAVG_SEGWINN_PER_CU caps it instead
+  static const int64_t per_cu_knob = tuning_knob("FEDAVG_SEGWINN_PER_CU", 0);
   const int64_t cus = cu_count();
-  int64_t per_cu = per_cu_env;
-  if (per_cu <= 0 && !bar) {
+  int64_t per_cu = per_cu_knob;
+  if (per_cu <= 0) {
     const int64_t r = res / cus;
     per_cu = 0;
     if (r >= 1)
       for (per_cu = 1; per_cu * 2 <= r;) per_cu *= 2;
-  } else if (per_cu <= 0) {
-    per_cu = ns == 5 ? 3 : 0;  // the barrier form's rule (round 5)
   }
   if (per_cu > 0 && per_cu * cus < res) res = per_cu * cus;
   return units < res ? units : res;
 }
 
 // windows per wave below which the LDS-DMA tiles keep the round
-// (kSegWinMinPerWave; FEDAVG_SEGWIN_MIN_PER_WAVE overrides it for probes)
+// (kSegWinMinPerWave; the probe library's FEDAVG_SEGWIN_MIN_PER_WAVE overrides it)
 inline int64_t segwin_min_per_wave() {
-  static const int64_t v = [] {
-    const char* e = std::getenv("FEDAVG_SEGWIN_MIN_PER_WAVE");
-    return e && e[0] ? static_cast<int64_t>(std::atoll(e)) : kSegWinMinPerWave;
-  }();
+  static const int64_t v = tuning_knob("FEDAVG_SEGWIN_MIN_PER_WAVE", kSegWinMinPerWave);
   return v;
 }
 
-// FEDAVG_SEGWIN=0 keeps the LDS-DMA tiles for every device round (probes, A/B)
+// the probe library's FEDAVG_SEGWIN=0 keeps the LDS-DMA tiles for every device round
 inline bool segwin_disabled() {
-  static const bool off = [] {
-    const char* e = std::getenv("FEDAVG_SEGWIN");
-    return e && e[0] == '0';
-  }();
+  static const bool off = tuning_knob("FEDAVG_SEGWIN", 1) == 0;
   return off;
 }
 
@@ -1506,16 +1274,10 @@ inline int64_t seg_fused_lds_bytes(int64_t K, int S, bool laddr = false) {
   return b > kBlock * 8 ? b : kBlock * 8;
 }
 
-// FEDAVG_SEG_LADDR=0 keeps the tiles' client addresses in registers (probes, A/B)
-inline bool seg_laddr_disabled() {
-  static const bool off = [] {
-    const char* e = std::getenv("FEDAVG_SEG_LADDR");
-    return e && e[0] == '0';
-  }();
-  return off;
-}
-
-template <int S, bool MAP = false, bool LADDR = false>
+// The tile kernel's two forms: MAP = false (the key of a unit by search, the
+// client addresses in registers) without a unit map, MAP = true (unit map,
+// client addresses in LDS) with one
+template <int S, bool MAP>
 int seg_fused_per_cu(int64_t K) {
   static std::mutex mu;
   static std::map<std::pair<int, int64_t>, int> cache;
@@ -1524,8 +1286,8 @@ int seg_fused_per_cu(int64_t K) {
   std::lock_guard<std::mutex> lk(mu);
   auto it = cache.find({dev, K});
   if (it != cache.end()) return it->second;
-  const auto kern = reduce_sqdist_segments_f32_kernel<S, MAP, LADDR>;
-  const int64_t lds = seg_fused_lds_bytes(K, S, LADDR);
+  const auto kern = reduce_sqdist_segments_f32_kernel<S, MAP, MAP>;
+  const int64_t lds = seg_fused_lds_bytes(K, S, MAP);
   int per_cu = 0;
   if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                          hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1540,19 +1302,17 @@ int seg_fused_per_cu(int64_t K) {
   return per_cu;
 }
 
-template <int S, bool MAP = false, bool LADDR = false>
+template <int S, bool MAP>
 int64_t seg_fused_grid(int64_t K, int64_t units) {
-  const int64_t g = static_cast<int64_t>(seg_fused_per_cu<S, MAP, LADDR>(K)) * cu_count();
+  const int64_t g = static_cast<int64_t>(seg_fused_per_cu<S, MAP>(K)) * cu_count();
   return units < g ? units : g;
 }
 
-// resident workgroups per CU of any tile kernel form (the partials' bound)
+// resident workgroups per CU of either tile kernel form (the partials' bound)
 template <int S>
 int seg_fused_per_cu_max(int64_t K) {
-  const int a = seg_fused_per_cu<S, false>(K), b = seg_fused_per_cu<S, true>(K),
-            c = seg_fused_per_cu<S, true, true>(K);
-  const int ab = a > b ? a : b;
-  return ab > c ? ab : c;
+  const int a = seg_fused_per_cu<S, false>(K), b = seg_fused_per_cu<S, true>(K);
+  return a > b ? a : b;
 }
 
 int64_t units_of(const int64_t* numel, int64_t n_keys, int64_t span = kSegSpan) {
@@ -1644,19 +1404,15 @@ inline bool seg_split_ok(const int64_t* numel, int64_t n_keys) {
 // 1.46; 150 2.29 vs 1.49; 160 2.44 vs 1.43; 200 2.90 vs 1.71; 256 4.12 vs
 // 2.10; the one-wave windows keep <= 128: 100 0.79 vs 1.06, 120 0.97 vs 1.11)
 constexpr int64_t kSegSplitMinK = 129, kSegSplitMinPerBlock = 8;
-// FEDAVG_SEG_SPLIT_MIN_K overrides kSegSplitMinK (probes)
+// the probe library's FEDAVG_SEG_SPLIT_MIN_K overrides kSegSplitMinK
 inline int64_t seg_split_min_k() {
-  static const int64_t v = [] {
-    const char* e = std::getenv("FEDAVG_SEG_SPLIT_MIN_K");
-    return e && e[0] ? static_cast<int64_t>(std::atoll(e)) : kSegSplitMinK;
-  }();
+  static const int64_t v = tuning_knob("FEDAVG_SEG_SPLIT_MIN_K", kSegSplitMinK);
   return v;
 }
 
 SegFusedPlan seg_fused_plan(const int64_t* numel, int64_t n_keys, int64_t K, bool all_raw) {
   SegFusedPlan p{false, segwin_kmax(K), seg_fused_cols(K), 0};
-  if (K >= seg_split_min_k() && K >= 2 && K <= kSegFusedMaxK && all_raw && !seg_barrier_windows() &&
-      seg_split_ok(numel, n_keys)) {
+  if (K >= seg_split_min_k() && K >= 2 && K <= kSegFusedMaxK && all_raw && seg_split_ok(numel, n_keys)) {
     const int64_t units = units_of(numel, n_keys, 64);
     const int64_t blocks = segwinn_blocks(K, units);
     if (blocks > 0 && units >= kSegSplitMinPerBlock * blocks) {
@@ -1715,14 +1471,8 @@ int launch_seg_fused(const SegFusedPlan& p, const SegKey* keys, const int64_t* t
     const dim3 grid(static_cast<unsigned>(p.waves)), block(static_cast<unsigned>(64 * ns));
     if (K < 2)
       return set_error(FEDAVG_EMODE, "%s: the split windows take K >= 2", what);
-    if (seg_barrier_windows()) {
-      if (ns <= 8)
-        hipLaunchKernelGGL((reduce_sqdist_segwinn_kernel<8>), grid, block, 0, s, keys, tptrs, n_keys, units, k32,
-                           weights, out, partials);
-      else
-        hipLaunchKernelGGL((reduce_sqdist_segwinn_kernel<16>), grid, block, 0, s, keys, tptrs, n_keys, units, k32,
-                           weights, out, partials);
-    } else if (seg_split_stamps()) {  // timeline probe
+#ifdef FEDAVG_TUNING
+    if (seg_split_stamps()) {  // timeline probe
       if (partial_elems < K * p.waves + winn_stamp_elems(16))
         return set_error(FEDAVG_EINVAL, "%s: the timeline needs %lld more doubles", what, (long long)winn_stamp_elems(16));
       if (ns <= 8)
@@ -1731,14 +1481,9 @@ int launch_seg_fused(const SegFusedPlan& p, const SegKey* keys, const int64_t* t
       else
         hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<16, kSegWinfPF16, true, 8>), grid, block, 0, s, keys, tptrs,
                            n_keys, units, k32, weights, out, partials);
-    } else if (seg_split_two_paths()) {  // A/B: ragged windows reloaded after the squares
-      if (ns <= 8)
-        hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<8, kSegWinfPF8, false>), grid, block, 0, s, keys, tptrs,
-                           n_keys, units, k32, weights, out, partials);
-      else
-        hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<16, kSegWinfPF16, false>), grid, block, 0, s, keys, tptrs,
-                           n_keys, units, k32, weights, out, partials);
-    } else if (ns <= 8) {
+    } else
+#endif
+    if (ns <= 8) {
       hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<8, kSegWinfPF8>), grid, block, 0, s, keys, tptrs, n_keys, units,
                          k32, weights, out, partials);
     } else {
@@ -1768,33 +1513,24 @@ int launch_seg_fused(const SegFusedPlan& p, const SegKey* keys, const int64_t* t
     nparts = p.waves;
   } else {
     const int S = static_cast<int>(p.span);
-#define FEDAVG_SEG_FUSED(C)                                                                                        \
-  if (S == C) {                                                                                                    \
-    const bool la = umap && !seg_laddr_disabled();                                                                 \
-    if ((la ? seg_fused_per_cu<C, true, true>(K) : (umap ? seg_fused_per_cu<C, true>(K) : seg_fused_per_cu<C>(K))) \
-        <= 0)                                                                                                      \
-      return set_error(FEDAVG_EMODE, "%s: tile does not fit LDS", what);                                           \
-    nparts = la ? seg_fused_grid<C, true, true>(K, units)                                                          \
-                : (umap ? seg_fused_grid<C, true>(K, units) : seg_fused_grid<C>(K, units));                        \
+#define FEDAVG_SEG_FUSED(C, MAP)                                                                                   \
+  if (S == C && (umap != nullptr) == MAP) {                                                                        \
+    if (seg_fused_per_cu<C, MAP>(K) <= 0) return set_error(FEDAVG_EMODE, "%s: tile does not fit LDS", what);       \
+    nparts = seg_fused_grid<C, MAP>(K, units);                                                                     \
     if (partial_elems < K * nparts)                                                                                \
       return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)(K * nparts));             \
-    if (la)                                                                                                        \
-      hipLaunchKernelGGL((reduce_sqdist_segments_f32_kernel<C, true, true>), dim3(static_cast<unsigned>(nparts)),   \
-                         dim3(kBlock), static_cast<unsigned>(seg_fused_lds_bytes(K, C, true)), s, keys, tptrs,      \
-                         n_keys, units, k32, weights, out, partials, umap);                                         \
-    else if (umap)                                                                                                 \
-      hipLaunchKernelGGL((reduce_sqdist_segments_f32_kernel<C, true>), dim3(static_cast<unsigned>(nparts)),         \
-                         dim3(kBlock), static_cast<unsigned>(seg_fused_lds_bytes(K, C)), s, keys, tptrs, n_keys,    \
-                         units, k32, weights, out, partials, umap);                                                 \
-    else                                                                                                           \
-      hipLaunchKernelGGL((reduce_sqdist_segments_f32_kernel<C>), dim3(static_cast<unsigned>(nparts)), dim3(kBlock),  \
-                         static_cast<unsigned>(seg_fused_lds_bytes(K, C)), s, keys, tptrs, n_keys, units, k32,      \
-                         weights, out, partials, nullptr);                                                          \
+    hipLaunchKernelGGL((reduce_sqdist_segments_f32_kernel<C, MAP, MAP>), dim3(static_cast<unsigned>(nparts)),       \
+                       dim3(kBlock), static_cast<unsigned>(seg_fused_lds_bytes(K, C, MAP)), s, keys, tptrs, n_keys, \
+                       units, k32, weights, out, partials, umap);                                                   \
   }
-    FEDAVG_SEG_FUSED(32)
-    FEDAVG_SEG_FUSED(64)
-    FEDAVG_SEG_FUSED(128)
-    FEDAVG_SEG_FUSED(256)
+    FEDAVG_SEG_FUSED(32, false)
+    FEDAVG_SEG_FUSED(32, true)
+    FEDAVG_SEG_FUSED(64, false)
+    FEDAVG_SEG_FUSED(64, true)
+    FEDAVG_SEG_FUSED(128, false)
+    FEDAVG_SEG_FUSED(128, true)
+    FEDAVG_SEG_FUSED(256, false)
+    FEDAVG_SEG_FUSED(256, true)
 #undef FEDAVG_SEG_FUSED
   }
   int rc = launch_status(what);
@@ -1820,15 +1556,6 @@ int launch_seg_fused(const SegFusedPlan& p, const SegKey* keys, const int64_t* t
 // (IntKey, RoundWs / round_ws, the unit map's and the descriptor table's
 // limits: staging.hpp; a tile round of more than kSegUnitMapMax units at
 // 17-128 clients takes the windows)
-
-// FEDAVG_SEGWIN_DESC=0 keeps the windows' pointer form (probes, A/B)
-inline bool segwin_desc_disabled() {
-  static const bool off = [] {
-    const char* e = std::getenv("FEDAVG_SEGWIN_DESC");
-    return e && e[0] == '0';
-  }();
-  return off;
-}
 
 
 // a fused round's integer / bool keys as fp32 columns of the [K, S] scratch:
@@ -2088,7 +1815,7 @@ int fedavg_device_round_f32(const int64_t* client_ptrs, int64_t ptr_ld, const in
   };
   const fedavg_staging::RoundIn rin{client_ptrs, ptr_ld, key_index, key_numel, key_offset, key_kind, n_keys, K,
                                     weights, reinterpret_cast<int64_t>(int_scratch), int_scratch ? scratch_elems : 0,
-                                    fuse_req, segwin_desc_disabled()};
+                                    fuse_req};
   fedavg_staging::RoundOut st;
   fedavg_staging::Msg msg;
   int rc = fedavg_staging::stage_device_round(rin, host_ws, ws_bytes, plan_fn, &st, &msg);

@@ -205,8 +205,7 @@ struct RoundIn {
   const double* weights;
   int64_t int_scratch;    // device address of the [K, S] fp32 scratch (0: none)
   int64_t scratch_elems;  // its floats
-  bool fuse;            // the caller asked for the fused :291 sums (and K allows them)
-  bool desc_disabled;   // FEDAVG_SEGWIN_DESC=0
+  bool fuse;              // the caller asked for the fused :291 sums (and K allows them)
 };
 
 struct RoundOut {
@@ -352,8 +351,7 @@ int stage_device_round(const RoundIn& in, void* host_ws, int64_t ws_bytes, PlanF
   // table of more than 2,047 keys at KMAX 128 has no room reserved, and a
   // smaller KMAX's table must not overrun it.
   const int64_t dbytes = fuse && plan.win && plan.kmax > 0 ? seg_desc_bytes(n_keys, plan.kmax) : 0;
-  const bool with_desc = fuse && plan.win && plan.kmax > 0 && dbytes <= kSegDescMaxBytes && dbytes <= L.desc_room &&
-                         !in.desc_disabled;
+  const bool with_desc = fuse && plan.win && plan.kmax > 0 && dbytes <= kSegDescMaxBytes && dbytes <= L.desc_room;
   if (with_desc) {
     auto* hd = reinterpret_cast<Desc*>(hb + moff);
     const int64_t km = plan.kmax;

@@ -21,6 +21,14 @@ window) or the kernel's own structure costs the time against the packed
 rows' fused pass.  Prints one JSON line with the layout and an event-timed
 median per call (the tables' H2D, the integer-key pass, the fused kernel
 and the sums' finalize).
+
+The device round runs from the probe library (every product entry point, same
+kernels and plans with nothing set), so its tuning knobs apply to an A/B:
+FEDAVG_SEG_SPLIT_MIN_K (first client count of the split windows, 129),
+FEDAVG_SEGWINN_PER_CU (their workgroups per CU, 0 = the production rule),
+FEDAVG_SEGWIN_MIN_PER_WAVE (windows per wave below which the tiles keep the
+round, 16) and FEDAVG_SEGWIN=0 (tiles for every round).  The product library
+ignores all of them.
 """
 from __future__ import annotations
 
@@ -94,7 +102,7 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    lib = mfl_amd._lib.load()
+    lib = mfl_amd._lib.load_probe()
     counts, dicts = device_clients(args.config, dev)
     if args.clients:
         counts, dicts = counts[:args.clients], dicts[:args.clients]

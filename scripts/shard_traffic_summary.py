@@ -1,7 +1,8 @@
 """PMC traffic of the per-rank kernel at every chunk geometry the N > 1 sweep
 can pick (bench.chunk_candidates: 1, 2, 4, 8 chunks), from the separate
 ``rocprofv3 --pmc FETCH_SIZE`` / ``--pmc WRITE_SIZE`` passes of
-``bench.py --shard-of N --chunks C`` (scripts/r05_gpu_stream.sh):
+``bench.py --shard-of N --chunks C --steps 4 --warmup 1 --no-cpu-baseline``
+(profiles/README.md, `shard_pmc`):
 
     python scripts/shard_traffic_summary.py gpurun_out/r05/g1 --round r05
 

@@ -1,5 +1,7 @@
 """Per-wave timeline of the zero-copy split windows (reduce_sqdist_segwinf_kernel,
 FEDAVG_SEGWINF_STAMPS=1: the MODE 8 build) on a resnet18_gn-shaped device round.
+The stamp build and its switch exist in the probe library only, which this
+script loads; the product library ignores the variable.
 
     python scripts/zc_timeline.py [--clients 129 257 500] [--calls 5]
 
@@ -14,7 +16,7 @@ import os
 import sys
 from pathlib import Path
 
-os.environ["FEDAVG_SEGWINF_STAMPS"] = "1"  # read once, at the library's first device round
+os.environ["FEDAVG_SEGWINF_STAMPS"] = "1"  # read once, at the probe library's first device round
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
@@ -36,7 +38,7 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    lib = mfl_amd._lib.load()
+    lib = mfl_amd._lib.load_probe()
     counts_all, dicts_all = device_clients(args.config, dev)
     for Kc in args.clients:
         counts, dicts = counts_all[:Kc], dicts_all[:Kc]

@@ -39,6 +39,7 @@ using namespace fedavg_staging;
 namespace {
 
 int failures = 0;
+int desc_rounds = 0, ptr_rounds = 0;  // one-wave window rounds staged with / without the descriptor table
 #define CHECK(cond, ...)                                   \
   do {                                                     \
     if (!(cond)) {                                         \
@@ -151,8 +152,7 @@ void fuzz_device_round(std::mt19937_64& rng, int64_t n_keys, int64_t K, bool eve
       auto* buf = static_cast<unsigned char*>(std::malloc(static_cast<size_t>(L.end)));
       std::memset(buf, fill, static_cast<size_t>(L.end));
       RoundIn in{t.ptrs.data(), t.ld, t.use_index ? t.key_index.data() : nullptr, t.numel.data(), t.offset.data(),
-                 t.kind.data(), n_keys, K, t.weights.data(), int64_t(1) << 44, K * S, want_fuse,
-                 rng() % 8 == 0};
+                 t.kind.data(), n_keys, K, t.weights.data(), int64_t(1) << 44, K * S, want_fuse};
       bool fused_seen = false;
       const auto plan_fn = [&](bool fuse, bool) -> RoundPlan {
         fused_seen = fuse;
@@ -168,6 +168,8 @@ void fuzz_device_round(std::mt19937_64& rng, int64_t n_keys, int64_t K, bool eve
         CHECK(lw < st.bytes, "a staged byte (%lld) lies past the shipped bytes (%lld); K=%lld n=%lld kmax=%d",
               (long long)lw, (long long)st.bytes, (long long)K, (long long)n_keys, st.plan.kmax);
         CHECK(fused_seen == st.fuse, "plan_fn saw fuse=%d, round fuse=%d", fused_seen, st.fuse);
+        // a one-wave window round: with the descriptor table, or (a table too large for its room) without
+        if (st.fuse && st.plan.win && st.plan.kmax > 0) ++(st.with_desc ? desc_rounds : ptr_rounds);
         if (st.with_desc)
           CHECK(st.moff + seg_desc_bytes(n_keys, st.plan.kmax) <= L.end, "descriptor table past the room");
         if (st.with_map) CHECK(st.moff + st.units * 4 <= L.end, "unit map past the room");
@@ -312,6 +314,8 @@ int main(int argc, char** argv) {
     fuzz_segment_tables(rng, n_keys, K);
     if (it % 4 == 0) fuzz_pack(rng);
   }
+  CHECK(desc_rounds > 0 && ptr_rounds > 0, "window rounds with / without the descriptor table: %d / %d", desc_rounds,
+        ptr_rounds);
   std::printf("staging fuzz: %d iterations, seed %llu, %d failures\n", iters, (unsigned long long)seed, failures);
   return failures ? 1 : 0;
 }

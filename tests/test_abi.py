@@ -75,6 +75,28 @@ def test_library_is_gfx950_code_object():
     assert b"gfx950" in data
 
 
+# every variable that once chose a kernel, a grid or a band edge in csrc/
+ENV_REMOVED = (b"FEDAVG_SEGWINN_BARRIER", b"FEDAVG_SEGWINF_TWO_PATHS", b"FEDAVG_SEG_LADDR", b"FEDAVG_SEGWIN_DESC",
+               b"FEDAVG_SPLIT_PREFETCH")
+# tuning knobs (common.hpp's tuning_knob): compiled into the probe library only
+ENV_PROBE_ONLY = (b"FEDAVG_SEGWIN_MIN_PER_WAVE", b"FEDAVG_SEG_SPLIT_MIN_K", b"FEDAVG_SEGWINN_PER_CU", b"FEDAVG_SEGWIN",
+                  b"FEDAVG_SEGWINF_STAMPS")
+
+
+def test_product_library_names_no_environment_variable(lib):
+    """The product selects nothing by environment: none of the ten variable
+    names occurs in libfedavg_amd.so; the probe library holds the five knobs
+    that are kept (and none of the removed ones)."""
+    product = _lib.library_path().read_bytes()
+    for name in ENV_REMOVED + ENV_PROBE_ONLY:
+        assert name not in product, name
+    probe = _lib.PROBE_LIB_PATH.read_bytes()
+    for name in ENV_PROBE_ONLY:
+        assert name + b"\0" in probe, name  # the whole literal: FEDAVG_SEGWIN is a prefix of others
+    for name in ENV_REMOVED:
+        assert name not in probe, name
+
+
 def test_abi_version(lib):
     assert lib.fedavg_abi_version() == _lib.ABI_VERSION
 

@@ -345,6 +345,40 @@ def test_window_plan_short_rows_and_other_k():
     assert lib.fedavg_fused_plan_of(64, 1_500_000) // 1000000 != KIND_WIN
 
 
+_PLAN_SHAPES = [(200, 1 << 20), (300, 1 << 20), (500, 1 << 20), (100, 1 << 22)]
+_PARTIALS_K = [200, 500]
+_PLAN_CHILD = """
+import sys
+sys.path.insert(0, sys.argv[1])
+import mfl_amd
+lib = mfl_amd._lib.load()
+print([lib.fedavg_fused_plan_of(K, P) for K, P in %r] + [lib.fedavg_reduce_sqdist_segments_partials(K) for K in %r])
+""" % (_PLAN_SHAPES, _PARTIALS_K)
+
+
+def test_product_plans_ignore_the_environment():
+    """The product library chooses no kernel, grid or band edge by environment:
+    a fresh process (the variables were read at first use) with the old
+    switches set plans what this one plans with nothing set.  No launch."""
+    import ast
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    switches = {"FEDAVG_SPLIT_PREFETCH": "0", "FEDAVG_SEGWINN_BARRIER": "1", "FEDAVG_SEG_SPLIT_MIN_K": "2"}
+    lib = mfl_amd._lib.load()
+    here = [lib.fedavg_fused_plan_of(K, P) for K, P in _PLAN_SHAPES] + \
+           [lib.fedavg_reduce_sqdist_segments_partials(K) for K in _PARTIALS_K]
+    assert all(v > 0 for v in here), here
+    proc = subprocess.run([sys.executable, "-c", _PLAN_CHILD, str(Path(__file__).resolve().parents[1])],
+                          env={**os.environ, **switches}, capture_output=True, text=True, timeout=120)
+    assert proc.returncode == 0, proc.stderr
+    there = ast.literal_eval(proc.stdout.strip().splitlines()[-1])
+    print("plans and partials:", here, "with the switches set:", there)
+    assert there == here
+
+
 WIN_DEVICE_SHAPES = [("layer.weight", (8_400_017,)), ("layer.bias", (1001,)), ("tiny", (3,)),
                      ("proj.weight", (800, 1000)), ("proj.bias", (640,))]
 
