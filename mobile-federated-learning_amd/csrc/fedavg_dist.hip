@@ -1,6 +1,7 @@
 // fedavg_dist.hip -- the post-aggregate client distance pass
 // (fedavg_trainer.py:291) of libfedavg_amd.so.
 #include "common.hpp"
+#include "window.hpp"
 
 namespace {
 using namespace fedavg_impl;
@@ -1126,9 +1127,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_win_kernel(
         acc[64 * b] += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
         continue;
       }
-      const double q01 = fold32(p[0], p[1]), q23 = fold32(p[2], p[3]);
-      const double q45 = fold32(p[4], p[5]), q67 = fold32(p[6], p[7]);
-      acc[64 * b] += fold8(fold16(q01, q23), fold16(q45, q67), upper);
+      acc[64 * b] += win_fold_batch(p, upper);
     }
     if constexpr ((MODE & 2) != 0) __builtin_amdgcn_s_setprio(0);
   }
@@ -1139,10 +1138,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_win_kernel(
   const int row_in = win_batch_row(lane);
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    double s = acc[64 * b];
-    s += dpp_move_f64<0xB1, 0xF>(s);   // quad_perm [1,0,3,2]
-    s += dpp_move_f64<0x4E, 0xF>(s);   // quad_perm [2,3,0,1]
-    s += dpp_move_f64<0x141, 0xF>(s);  // row_half_mirror: the other quad of the 8-lane group
+    const double s = win_row_sum(acc[64 * b]);
     const int row = 8 * b + row_in;
     if ((lane & 7) == 0 && row < K) partials[static_cast<int64_t>(row) * GW + gw] = s;
   }
@@ -1418,9 +1414,7 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(KH, VEC)) void reduce_sqd
           }
         }
       }
-      const double q01 = fold32(p[0], p[1]), q23 = fold32(p[2], p[3]);
-      const double q45 = fold32(p[4], p[5]), q67 = fold32(p[6], p[7]);
-      acc[64 * b] += fold8(fold16(q01, q23), fold16(q45, q67), upper);
+      acc[64 * b] += win_fold_batch(p, upper);
     }
     stamp(4);
     __syncthreads();  // xa is read by every wave before the next window's chain rewrites it
@@ -1430,29 +1424,20 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(KH, VEC)) void reduce_sqd
   const int row_in = win_batch_row(lane);
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    double s = acc[64 * b];
-    s += dpp_move_f64<0xB1, 0xF>(s);
-    s += dpp_move_f64<0x4E, 0xF>(s);
-    s += dpp_move_f64<0x141, 0xF>(s);
+    const double s = win_row_sum(acc[64 * b]);
     const int row = 8 * b + row_in;
     if ((lane & 7) == 0 && row < KH && r0 + row < K) partials[static_cast<int64_t>(r0 + row) * G + blockIdx.x] = s;
   }
 }
 
 // workgroups of the split window launch: the resident ones (ceil(K / KH)
-// waves each) rounded down to a power of two per CU -- 3 workgroups of 5
-// waves on a CU ran 12-15 % slower than 2 (profiles/r05/prefetch/) --, at
-// most one per window
+// waves each) rounded down to a power of two per CU (split_per_cu), at most
+// one per window
 template <int KH, int VEC, int NSMAX, int PF = 0, int LE = 0, int MODE = 0>
 int64_t fused_winn_grid(int64_t K, int64_t P, int blocks_per_cu) {
   const int ns = static_cast<int>((K + KH - 1) / KH);
-  int64_t per_cu = blocks_per_cu;
-  if (per_cu <= 0) {
-    const int64_t r = resident_blocks(reduce_sqdist_winn_kernel<KH, VEC, NSMAX, PF, LE, MODE>, 64 * ns) / cu_count();
-    per_cu = 0;  // none resident: the caller reports it (grid 0)
-    if (r >= 1)
-      for (per_cu = 1; per_cu * 2 <= r;) per_cu *= 2;
-  }
+  int64_t per_cu = blocks_per_cu;  // none resident: the caller reports it (grid 0)
+  if (per_cu <= 0) per_cu = split_per_cu(resident_blocks(reduce_sqdist_winn_kernel<KH, VEC, NSMAX, PF, LE, MODE>, 64 * ns));
   const int64_t nwin = (P + 64 * VEC - 1) / (64 * VEC);
   const int64_t grid = per_cu * cu_count();
   return grid < nwin ? grid : nwin;
@@ -1512,7 +1497,7 @@ int launch_fused_winn(const float* clients, int64_t K, int64_t P, int64_t ld, co
 // turn at the squares' priority, 16 runs every wave's squares at priority 2, 32 by
 // halves (waves 0-7 at 2, the rest at 1).
 // ---------------------------------------------------------------------------
-constexpr int kHandoffSpinMax = 1 << 16;  // x 16 polls of ~100 clocks (or x s_sleep 1): < 50 ms, a window is ~13 us
+// (kHandoffSpinMax: window.hpp, shared with the zero-copy form)
 
 template <int NSMAX, int PF, int MODE = 0>
 __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdist_winf_kernel(
@@ -1556,27 +1541,11 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   for (int b = 0; b < NB; ++b) acc[64 * b] = 0.0;
   if (threadIdx.x <= NSMAX) flag[threadIdx.x] = -1;
   float wv[NWV];  // lane 16r + j of wv[k]: row 16k + j's weight (-0.0 past K)
-#pragma unroll
-  for (int k = 0; k < NWV; ++k) {
-    const int row = r0 + 16 * k + (lane & 15);
-    wv[k] = row < K ? W[row] : -0.0f;
-  }
+  handoff_weights(wv, W, r0, lane, K);
   __syncthreads();
-  // LDS pointers spelled out: a volatile access through a generic pointer is a
-  // flat_load, whose wait is vmcnt(0) -- every row load of the wave
-  typedef __attribute__((address_space(3))) volatile int lds_flag_t;
-  const auto wait_flag = [&](int idx, int seq) __attribute__((always_inline)) {
-    lds_flag_t* f = (lds_flag_t*)&flag[idx];
-    // tight polls (no s_sleep): 600 x 10M 4.20 -> 4.09 ms, 1000 x 12.5M 7.97 -> 7.93
-    // (profiles/r06/winf_modes/); MODE 1 is the s_sleep 1 form
-    for (int it = 0; __builtin_amdgcn_readfirstlane(*f) != seq && it < kHandoffSpinMax * ((MODE & 1) ? 1 : 16); ++it)
-      if constexpr ((MODE & 1) != 0) __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-  };
-  const auto publish = [&](int idx, int seq) __attribute__((always_inline)) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the payload's ds_write is done
-    *(lds_flag_t*)&flag[idx] = seq;
-  };
+  // (handoff_wait / handoff_publish / handoff_weights: window.hpp, one text for both forms)
+  const auto wait_flag = [&](int idx, int seq) __attribute__((always_inline)) { handoff_wait<MODE>(flag, idx, seq); };
+  const auto publish = [&](int idx, int seq) __attribute__((always_inline)) { handoff_publish(flag, idx, seq); };
   constexpr bool kPrio = (MODE & 2) == 0, kTurnPrio = kPrio && (MODE & 4) == 0;
   float x[KH];
   float xp[PF];
@@ -1688,9 +1657,7 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
           rp += row_bytes;
         }
       }
-      const double q01 = fold32(p[0], p[1]), q23 = fold32(p[2], p[3]);
-      const double q45 = fold32(p[4], p[5]), q67 = fold32(p[6], p[7]);
-      acc[64 * b] += fold8(fold16(q01, q23), fold16(q45, q67), upper);
+      acc[64 * b] += win_fold_batch(p, upper);
     }
     __builtin_amdgcn_s_setprio(0);
     stamp(4);
@@ -1699,22 +1666,16 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   const int row_in = win_batch_row(lane);
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    double sm = acc[64 * b];
-    sm += dpp_move_f64<0xB1, 0xF>(sm);
-    sm += dpp_move_f64<0x4E, 0xF>(sm);
-    sm += dpp_move_f64<0x141, 0xF>(sm);
+    const double s = win_row_sum(acc[64 * b]);
     const int row = 8 * b + row_in;
-    if ((lane & 7) == 0 && r0 + row < K) partials[static_cast<int64_t>(r0 + row) * G + blockIdx.x] = sm;
+    if ((lane & 7) == 0 && r0 + row < K) partials[static_cast<int64_t>(r0 + row) * G + blockIdx.x] = s;
   }
 }
 
 template <int NSMAX, int PF, int MODE = 0>
 int64_t fused_winf_grid(int64_t K, int64_t P) {
   const int ns = static_cast<int>((K + 63) / 64);
-  const int64_t r = resident_blocks(reduce_sqdist_winf_kernel<NSMAX, PF, MODE>, 64 * ns) / cu_count();
-  int64_t per_cu = 0;
-  if (r >= 1)
-    for (per_cu = 1; per_cu * 2 <= r;) per_cu *= 2;
+  const int64_t per_cu = split_per_cu(resident_blocks(reduce_sqdist_winf_kernel<NSMAX, PF, MODE>, 64 * ns));
   const int64_t nwin = (P + 63) / 64;
   const int64_t grid = per_cu * cu_count();
   return grid < nwin ? grid : nwin;
@@ -1875,18 +1836,13 @@ __global__ __launch_bounds__(128, win_min_waves(KH, VEC)) void reduce_sqdist_win
           rp += row_bytes;
         }
       }
-      const double q01 = fold32(p[0], p[1]), q23 = fold32(p[2], p[3]);
-      const double q45 = fold32(p[4], p[5]), q67 = fold32(p[6], p[7]);
-      acc[64 * b] += fold8(fold16(q01, q23), fold16(q45, q67), upper);
+      acc[64 * b] += win_fold_batch(p, upper);
     }
   }
   const int row_in = win_batch_row(lane);
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    double s = acc[64 * b];
-    s += dpp_move_f64<0xB1, 0xF>(s);
-    s += dpp_move_f64<0x4E, 0xF>(s);
-    s += dpp_move_f64<0x141, 0xF>(s);
+    const double s = win_row_sum(acc[64 * b]);
     const int row = 8 * b + row_in;
     if ((lane & 7) == 0 && row < KH && r0 + row < K) partials[static_cast<int64_t>(r0 + row) * G + blockIdx.x] = s;
   }
@@ -1966,7 +1922,7 @@ constexpr int64_t kFusedWinnMinK = 369;
 // 1.26; 500 x 11.2M 3.66 vs 3.57; 400 x 10M 2.73 vs 2.60; 370 x 5M 1.25 vs
 // 1.18; every output bit-identical).  The barrier form is a variant of the
 // probe library (fedavg_reduce_sqdist_f32_variant), never a production plan.
-constexpr int kWinfPF8 = 8, kWinfPF16 = 16;
+// (kSplitForms, window.hpp: for_split gives <8, PF 8> or <16, PF 16>)
 // With the prefetch the split windows also beat the register-staged tiles at
 // 161-256 and 289-368 rows on long rows (profiles/r05/prefetch/, ms, tiles vs
 // split: 170 x 5M 0.606 vs 0.593; 192 x 5M 0.725 vs 0.661; 240 x 5M 0.897 vs
@@ -2000,26 +1956,57 @@ struct FusedPlan {
 // 1.547 (profiles/r03/win/ldsrows.jsonl); every band has K > 24 rows
 constexpr int kWin100Mode = 64;
 
-// the window kernel instance for K rows ({kFusedNone} outside 17..128)
+constexpr int win_rows_mode(int kmax) { return kmax == 100 ? kWin100Mode : 0; }
+
+// the window kernel instance for K rows ({kFusedNone} outside 17..128: kWinBands, window.hpp)
 inline FusedPlan win_plan(int64_t K) {
-  if (K <= 16 || K > 128) return {kFusedNone, 0, 0};
-  if (K <= 48) return {kFusedWin, 48, 4};
-  if (K <= 64) return {kFusedWin, 64, 2};
-  if (K <= 80) return {kFusedWin, 80, 2};
-  if (K <= 100) return {kFusedWin, 100, 2};
-  return {kFusedWin, 128, 1};
+  const PlanEntry* band = win_band_of(K);
+  return band ? FusedPlan{kFusedWin, band->a, band->b} : FusedPlan{kFusedNone, 0, 0};
 }
 
 // waves of the production window launch for plan `pl` (0: not a window plan)
 inline int64_t win_waves(const FusedPlan& pl, int64_t P) {
-  if (pl.kind != kFusedWin) return 0;
-  switch (pl.S) {
-    case 48: return fused_win_waves<48, 4, 4>(P, 0);
-    case 64: return fused_win_waves<64, 2, 4>(P, 0);
-    case 80: return fused_win_waves<80, 2, 4>(P, 0);
-    case 100: return fused_win_waves<100, 2, 4, kWin100Mode>(P, 0);
-    default: return fused_win_waves<128, 1, 4>(P, 0);
+  int64_t waves = 0;
+  if (pl.kind == kFusedWin)
+    for_win_band(pl.S, [&](auto kmax, auto vec) {
+      constexpr int KMAX = decltype(kmax)::value, VEC = decltype(vec)::value;
+      waves = fused_win_waves<KMAX, VEC, 4, win_rows_mode(KMAX)>(P, 0);
+    });
+  return waves;
+}
+
+// The tile plans' instances: LDS-DMA tiles by columns, register-staged tiles
+// by {columns, slots}.  fused_plan returns entries of these tables; the
+// workspace size and the launch both go through for_lds_tile / for_rs_tile.
+constexpr PlanEntry kLdsTiles[] = {{64, 0}, {128, 0}, {256, 0}};
+constexpr PlanEntry kRsTiles[] = {{256, 8}, {64, 16}, {32, 10}, {32, 16}};
+template <class F>
+bool for_lds_tile(int S, F&& f) {  // f(S); false: no such tile
+  return for_entry<kLdsTiles>(S, kAnyB, [&](auto s, auto) { f(s); });
+}
+template <class F>
+bool for_rs_tile(int S, int slots, F&& f) {  // f(S, SLOTS); false: no such tile
+  return for_entry<kRsTiles>(S, slots, f);
+}
+
+// workgroups (one-wave windows: waves) of the production launch of plan `pl`:
+// the partials' second dimension
+inline int64_t fused_plan_parts(const FusedPlan& pl, int64_t K, int64_t P) {
+  int64_t n = 0;
+  if (pl.kind == kFusedWin) {
+    n = win_waves(pl, P);
+  } else if (pl.kind == kFusedLds) {
+    for_lds_tile(pl.S, [&](auto s) { n = fused_grid<decltype(s)::value>(K, P, 0); });
+  } else if (pl.kind == kFusedWinn) {
+    for_split(pl.slots, [&](auto nsmax, auto pf) {
+      n = fused_winf_grid<decltype(nsmax)::value, decltype(pf)::value>(K, P);
+    });
+  } else if (pl.kind == kFusedRs) {
+    for_rs_tile(pl.S, pl.slots, [&](auto s, auto slots) {
+      n = fused_rs_grid<decltype(s)::value, decltype(slots)::value, 0>(K, P, 0);
+    });
   }
+  return n;
 }
 
 inline FusedPlan fused_plan(int64_t K, int64_t P) {
@@ -2034,7 +2021,7 @@ inline FusedPlan fused_plan(int64_t K, int64_t P) {
   if (K <= 64) return {kFusedLds, 128, 0};
   if (K <= 128) return {kFusedLds, 64, 0};
   if (K >= kFusedWinnLowMinK && K < kFusedWinnMinK) {
-    const int64_t grid = fused_winf_grid<8, kWinfPF8>(K, P);
+    const int64_t grid = fused_plan_parts({kFusedWinn, 64, 8}, K, P);
     if (grid > 0 && (P + 63) / 64 >= kFusedWinnLowMinPerBlock * grid) return {kFusedWinn, 64, 8};
   }
   if (K <= 192) return {kFusedRs, 64, 16};
@@ -2351,24 +2338,7 @@ int64_t fedavg_reduce_sqdist_workspace(int64_t K, int64_t P) {
   if (K <= 0 || P <= 0) return 0;
   const FusedPlan pl = fused_plan(K, P);
   const int64_t two_pass = fedavg_client_sqdist_workspace(K, P);
-  int64_t fused = 0;
-  if (pl.kind == kFusedWin) {
-    fused = K * win_waves(pl, P);
-  } else if (pl.kind == kFusedLds) {
-    if (pl.S == 64) fused = K * fused_grid<64>(K, P, 0);
-    if (pl.S == 128) fused = K * fused_grid<128>(K, P, 0);
-    if (pl.S == 256) fused = K * fused_grid<256>(K, P, 0);
-  } else if (pl.kind == kFusedWinn) {
-    fused = K * (pl.slots == 8 ? fused_winf_grid<8, kWinfPF8>(K, P) : fused_winf_grid<16, kWinfPF16>(K, P));
-  } else if (pl.kind == kFusedRs) {
-    switch (pl.S * 100 + pl.slots) {
-      case 25608: fused = K * fused_rs_grid<256, 8, 0>(K, P, 0); break;
-      case 6416: fused = K * fused_rs_grid<64, 16, 0>(K, P, 0); break;
-      case 3210: fused = K * fused_rs_grid<32, 10, 0>(K, P, 0); break;
-      case 3216: fused = K * fused_rs_grid<32, 16, 0>(K, P, 0); break;
-      default: break;
-    }
-  }
+  const int64_t fused = K * fused_plan_parts(pl, K, P);
   return fused > two_pass ? fused : two_pass;
 }
 
@@ -2390,52 +2360,31 @@ int fedavg_reduce_sqdist_f32(const float* clients, int64_t K, int64_t P, int64_t
   }
   const FusedPlan pl = fused_plan(K, P);
   if (pl.kind != kFusedNone && aligned4(out) && aligned4(weights)) {
-    if (pl.kind == kFusedWin) {
-      switch (pl.S) {
-        case 48:
-          return launch_fused_win<48, 4, 4>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s,
-                                            what);
-        case 64:
-          return launch_fused_win<64, 2, 4>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s,
-                                            what);
-        case 80:
-          return launch_fused_win<80, 2, 4>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s,
-                                            what);
-        case 100:
-          return launch_fused_win<100, 2, 4, kWin100Mode>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                          sumsq, 0, s, what);
-        default:
-          return launch_fused_win<128, 1, 4>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s,
-                                             what);
-      }
-    }
-    if (pl.kind == kFusedWinn) {
-      if (pl.slots == 8)
-        return launch_fused_winf<8, kWinfPF8>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, s,
-                                              what);
-      return launch_fused_winf<16, kWinfPF16>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, s,
-                                              what);
-    }
-    if (pl.kind == kFusedLds) {  // K <= 128: one row per thread in the squares (RM 1; launch_fused's RM 2 is the variants')
-      if (pl.S == 64)
-        return launch_fused_rm<64, false, 0, false, 1>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                       sumsq, 0, s, what);
-      if (pl.S == 256)
-        return launch_fused_rm<256, false, 0, false, 1>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                        sumsq, 0, s, what);
-      return launch_fused_rm<128, false, 0, false, 1>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                      sumsq, 0, s, what);
-    }
-    switch (pl.S * 100 + pl.slots) {
-      case 25608:
-        return launch_fused_rs<256, 8>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s, what);
-      case 6416:
-        return launch_fused_rs<64, 16>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s, what);
-      case 3210:
-        return launch_fused_rs<32, 10>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s, what);
-      default:
-        return launch_fused_rs<32, 16>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, 0, s, what);
-    }
+    bool found = false;
+    if (pl.kind == kFusedWin)
+      found = for_win_band(pl.S, [&](auto kmax, auto vec) {
+        constexpr int KMAX = decltype(kmax)::value, VEC = decltype(vec)::value;
+        rc = launch_fused_win<KMAX, VEC, 4, win_rows_mode(KMAX)>(clients, K, P, ld, weights, out, workspace,
+                                                                  workspace_elems, sumsq, 0, s, what);
+      });
+    else if (pl.kind == kFusedWinn)
+      found = for_split(pl.slots, [&](auto nsmax, auto pf) {
+        rc = launch_fused_winf<decltype(nsmax)::value, decltype(pf)::value>(clients, K, P, ld, weights, out, workspace,
+                                                                            workspace_elems, sumsq, s, what);
+      });
+    else if (pl.kind == kFusedLds)  // K <= 128: one row per thread in the squares (RM 1; launch_fused's RM 2 is the variants')
+      found = for_lds_tile(pl.S, [&](auto cols) {
+        rc = launch_fused_rm<decltype(cols)::value, false, 0, false, 1>(clients, K, P, ld, weights, out, workspace,
+                                                                        workspace_elems, sumsq, 0, s, what);
+      });
+    else
+      found = for_rs_tile(pl.S, pl.slots, [&](auto cols, auto slots) {
+        rc = launch_fused_rs<decltype(cols)::value, decltype(slots)::value>(clients, K, P, ld, weights, out, workspace,
+                                                                            workspace_elems, sumsq, 0, s, what);
+      });
+    if (!found)
+      return set_error(FEDAVG_EMODE, "%s: plan %d / %d / %d names no kernel instance", what, pl.kind, pl.S, pl.slots);
+    return rc;
   }
   rc = fedavg_reduce_f32(clients, K, P, ld, weights, out, stream);
   if (rc) return rc;

@@ -19,6 +19,7 @@
 // key-major in round-split launches of 3 x CUs workgroups, so a launch streams
 // one compact window of every client's tensors, like the row-major reduce.
 #include "common.hpp"
+#include "window.hpp"
 #include "staging.hpp"
 
 #include <chrono>
@@ -903,9 +904,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_segwin_kernel(
                                  voff, soffn);
           }
         }
-        const double q01 = fold32(p[0], p[1]), q23 = fold32(p[2], p[3]);
-        const double q45 = fold32(p[4], p[5]), q67 = fold32(p[6], p[7]);
-        acc[64 * b] += fold8(fold16(q01, q23), fold16(q45, q67), upper);
+        acc[64 * b] += win_fold_batch(p, upper);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int r = 0; r < 8; ++r) dc[r] = dn[r];
@@ -923,9 +922,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_segwin_kernel(
             load_fast(i, soffn, nrecn, Kwn);
           }
         }
-        const double q01 = fold32(p[0], p[1]), q23 = fold32(p[2], p[3]);
-        const double q45 = fold32(p[4], p[5]), q67 = fold32(p[6], p[7]);
-        acc[64 * b] += fold8(fold16(q01, q23), fold16(q45, q67), upper);
+        acc[64 * b] += win_fold_batch(p, upper);
       }
     }
     if (un < units32 && !fastn) {
@@ -944,12 +941,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_segwin_kernel(
   const int row_in = win_batch_row(lane);
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    double sm = acc[64 * b];
-    sm += dpp_move_f64<0xB1, 0xF>(sm);
-    sm += dpp_move_f64<0x4E, 0xF>(sm);
-    sm += dpp_move_f64<0x141, 0xF>(sm);
+    const double s = win_row_sum(acc[64 * b]);
     const int row = 8 * b + row_in;
-    if ((lane & 7) == 0 && row < K) partials[static_cast<int64_t>(row) * GW + gw] = sm;
+    if ((lane & 7) == 0 && row < K) partials[static_cast<int64_t>(row) * GW + gw] = s;
   }
 }
 
@@ -990,7 +984,6 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   constexpr int KH = 64, WC = 64, NB = 8, NWV = 4;
   static_assert(PF >= 1 && PF <= KH, "prefetched rows");
   static_assert(UNI, "one load path for full and ragged windows");
-  constexpr int kSpinMax = 1 << 20;  // tight polls, as the rows kernel's
   const int lane = threadIdx.x & 63;
   const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ns = __builtin_amdgcn_readfirstlane(static_cast<int>(blockDim.x >> 6));
@@ -1020,23 +1013,11 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   for (int b = 0; b < NB; ++b) acc[64 * b] = 0.0;
   if (threadIdx.x <= NSMAX) flag[threadIdx.x] = -1;
   float wv[NWV];  // lane 16r + j of wv[k]: client 16k + j's weight (-0.0 past K)
-#pragma unroll
-  for (int k = 0; k < NWV; ++k) {
-    const int row = r0 + 16 * k + (lane & 15);
-    wv[k] = row < K ? W[row] : -0.0f;
-  }
+  handoff_weights(wv, W, r0, lane, K);
   __syncthreads();
-  typedef __attribute__((address_space(3))) volatile int lds_flag_t;
-  const auto wait_flag = [&](int idx, int seq) __attribute__((always_inline)) {
-    lds_flag_t* f = (lds_flag_t*)&flag[idx];
-    for (int it = 0; __builtin_amdgcn_readfirstlane(*f) != seq && it < kSpinMax; ++it) {
-    }
-    asm volatile("" ::: "memory");
-  };
-  const auto publish = [&](int idx, int seq) __attribute__((always_inline)) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    *(lds_flag_t*)&flag[idx] = seq;
-  };
+  // (handoff_wait / handoff_publish / handoff_weights: window.hpp, one text for both forms)
+  const auto wait_flag = [&](int idx, int seq) __attribute__((always_inline)) { handoff_wait<MODE>(flag, idx, seq); };
+  const auto publish = [&](int idx, int seq) __attribute__((always_inline)) { handoff_publish(flag, idx, seq); };
   const auto load_ptrs = [&](const int64_t* P) __attribute__((always_inline)) -> int64_t {
     const gptr<int64_t> q = to_global<int64_t>(P);
     return r0 + lane < K ? q[r0 + lane] : 0;
@@ -1158,9 +1139,7 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
         else
           x[i] = load_row(pvn, i, c0n, nn, Kwn);
       }
-      const double q01 = fold32(p[0], p[1]), q23 = fold32(p[2], p[3]);
-      const double q45 = fold32(p[4], p[5]), q67 = fold32(p[6], p[7]);
-      acc[64 * b] += fold8(fold16(q01, q23), fold16(q45, q67), upper);
+      acc[64 * b] += win_fold_batch(p, upper);
     }
     __builtin_amdgcn_s_setprio(0);
     stamp(4);
@@ -1176,19 +1155,13 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   const int row_in = win_batch_row(lane);
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    double sm = acc[64 * b];
-    sm += dpp_move_f64<0xB1, 0xF>(sm);
-    sm += dpp_move_f64<0x4E, 0xF>(sm);
-    sm += dpp_move_f64<0x141, 0xF>(sm);
+    const double s = win_row_sum(acc[64 * b]);
     const int row = 8 * b + row_in;
-    if ((lane & 7) == 0 && r0 + row < K) partials[static_cast<int64_t>(r0 + row) * G + blockIdx.x] = sm;
+    if ((lane & 7) == 0 && r0 + row < K) partials[static_cast<int64_t>(r0 + row) * G + blockIdx.x] = s;
   }
 }
 
 constexpr int64_t kSegSplitMaxK = 1024;  // the split-row windows' reach (16 waves of 64 clients)
-
-// workgroups of the split-row window launch over `units` windows (0: not resident)
-constexpr int kSegWinfPF8 = 8, kSegWinfPF16 = 16;  // prefetched rows at <= 8 / 16 waves
 
 // Probe library only (tuning_knob, common.hpp): FEDAVG_SEGWINF_STAMPS=1
 // launches the hand-off kernel's timeline build (MODE 8; the partials grow by
@@ -1198,24 +1171,21 @@ inline bool seg_split_stamps() {
   return on;
 }
 
+// workgroups of the split-row window launch over `units` windows (0: not resident)
 inline int64_t segwinn_blocks(int64_t K, int64_t units) {
   const int ns = static_cast<int>((K + 63) / 64);
-  int64_t res = ns <= 8 ? resident_blocks(reduce_sqdist_segwinf_kernel<8, kSegWinfPF8>, 64 * ns)
-                        : resident_blocks(reduce_sqdist_segwinf_kernel<16, kSegWinfPF16>, 64 * ns);
+  int64_t res = 0;
+  for_split(ns, [&](auto nsmax, auto pf) {
+    res = resident_blocks(reduce_sqdist_segwinf_kernel<decltype(nsmax)::value, decltype(pf)::value>, 64 * ns);
+  });
   // workgroups per CU: the resident ones rounded down to a power of two, as
-  // the rows kernel's grid (round 6, resnet18_gn-shaped rounds,
+  // the rows kernel's grid (split_per_cu; round 6, resnet18_gn-shaped rounds,
   // profiles/r06/zc_percu/, ms: 257 clients 3 per CU 2.70 vs 2 2.32; 300 2.83
   // vs 2.47; 129 clients 5 per CU 1.53 vs 4 1.47; 500 equal); the probe
   // library's FEDAVG_SEGWINN_PER_CU caps it instead
   static const int64_t per_cu_knob = tuning_knob("FEDAVG_SEGWINN_PER_CU", 0);
   const int64_t cus = cu_count();
-  int64_t per_cu = per_cu_knob;
-  if (per_cu <= 0) {
-    const int64_t r = res / cus;
-    per_cu = 0;
-    if (r >= 1)
-      for (per_cu = 1; per_cu * 2 <= r;) per_cu *= 2;
-  }
+  const int64_t per_cu = per_cu_knob > 0 ? per_cu_knob : split_per_cu(res);
   if (per_cu > 0 && per_cu * cus < res) res = per_cu * cus;
   return units < res ? units : res;
 }
@@ -1248,19 +1218,21 @@ int64_t segwin_waves(int64_t units) {
 // path's per-lane 64-bit element addresses, gone with the buffer-load form
 // (232 VGPRs, no scratch), so 81-100 clients take 100 x 2 as on rows
 inline int segwin_kmax(int64_t K) {
-  return K <= 16 || K > 128 ? 0 : (K <= 48 ? 48 : (K <= 64 ? 64 : (K <= 80 ? 80 : (K <= 100 ? 100 : 128))));
+  const PlanEntry* band = win_band_of(K);
+  return band ? band->a : 0;
 }
-inline int segwin_vec(int kmax) { return kmax == 48 ? 4 : (kmax == 128 ? 1 : 2); }
+inline int segwin_vec(int kmax) {  // 0: no such band
+  int v = 0;
+  for_win_band(kmax, [&](auto, auto vec) { v = decltype(vec)::value; });
+  return v;
+}
 
-inline int64_t segwin_waves_for(int kmax, int64_t units) {
-  switch (kmax) {
-    case 48: return segwin_waves<48, 4, 4>(units);
-    case 64: return segwin_waves<64, 2, 4>(units);
-    case 80: return segwin_waves<80, 2, 4>(units);
-    case 100: return segwin_waves<100, 2, 4>(units);
-    case 128: return segwin_waves<128, 1, 4>(units);
-    default: return 0;
-  }
+inline int64_t segwin_waves_for(int kmax, int64_t units) {  // 0: no such band
+  int64_t waves = 0;
+  for_win_band(kmax, [&](auto km, auto vec) {
+    waves = segwin_waves<decltype(km)::value, decltype(vec)::value, 4>(units);
+  });
+  return waves;
 }
 
 constexpr int kSegFusedMaxK = kBlock;
@@ -1308,11 +1280,21 @@ int64_t seg_fused_grid(int64_t K, int64_t units) {
   return units < g ? units : g;
 }
 
+// the tile widths of seg_fused_cols; f(S)
+constexpr PlanEntry kSegTiles[] = {{32, 0}, {64, 0}, {128, 0}, {256, 0}};
+template <class F>
+bool for_seg_tile(int S, F&& f) {  // false: no such tile
+  return for_entry<kSegTiles>(S, kAnyB, [&](auto s, auto) { f(s); });
+}
+
 // resident workgroups per CU of either tile kernel form (the partials' bound)
-template <int S>
-int seg_fused_per_cu_max(int64_t K) {
-  const int a = seg_fused_per_cu<S, false>(K), b = seg_fused_per_cu<S, true>(K);
-  return a > b ? a : b;
+inline int seg_fused_per_cu_max(int S, int64_t K) {
+  int per_cu = 0;
+  for_seg_tile(S, [&](auto s) {
+    const int a = seg_fused_per_cu<decltype(s)::value, false>(K), b = seg_fused_per_cu<decltype(s)::value, true>(K);
+    per_cu = a > b ? a : b;
+  });
+  return per_cu;
 }
 
 int64_t units_of(const int64_t* numel, int64_t n_keys, int64_t span = kSegSpan) {
@@ -1471,67 +1453,60 @@ int launch_seg_fused(const SegFusedPlan& p, const SegKey* keys, const int64_t* t
     const dim3 grid(static_cast<unsigned>(p.waves)), block(static_cast<unsigned>(64 * ns));
     if (K < 2)
       return set_error(FEDAVG_EMODE, "%s: the split windows take K >= 2", what);
-#ifdef FEDAVG_TUNING
-    if (seg_split_stamps()) {  // timeline probe
-      if (partial_elems < K * p.waves + winn_stamp_elems(16))
-        return set_error(FEDAVG_EINVAL, "%s: the timeline needs %lld more doubles", what, (long long)winn_stamp_elems(16));
-      if (ns <= 8)
-        hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<8, kSegWinfPF8, true, 8>), grid, block, 0, s, keys, tptrs,
-                           n_keys, units, k32, weights, out, partials);
-      else
-        hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<16, kSegWinfPF16, true, 8>), grid, block, 0, s, keys, tptrs,
-                           n_keys, units, k32, weights, out, partials);
-    } else
+#ifdef FEDAVG_TUNING  // the timeline build: MODE 8, the partials grow by the stamps
+    const bool stamps = seg_split_stamps();
+    if (stamps && partial_elems < K * p.waves + winn_stamp_elems(16))
+      return set_error(FEDAVG_EINVAL, "%s: the timeline needs %lld more doubles", what, (long long)winn_stamp_elems(16));
 #endif
-    if (ns <= 8) {
-      hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<8, kSegWinfPF8>), grid, block, 0, s, keys, tptrs, n_keys, units,
-                         k32, weights, out, partials);
-    } else {
-      hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<16, kSegWinfPF16>), grid, block, 0, s, keys, tptrs, n_keys,
-                         units, k32, weights, out, partials);
-    }
+    const bool found = for_split(ns, [&](auto nsmax, auto pf) {
+      constexpr int NSMAX = decltype(nsmax)::value, PF = decltype(pf)::value;
+#ifdef FEDAVG_TUNING
+      if (stamps) {
+        hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<NSMAX, PF, true, 8>), grid, block, 0, s, keys, tptrs, n_keys,
+                           units, k32, weights, out, partials);
+        return;
+      }
+#endif
+      hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<NSMAX, PF>), grid, block, 0, s, keys, tptrs, n_keys, units, k32,
+                         weights, out, partials);
+    });
+    if (!found) return set_error(FEDAVG_EMODE, "%s: no split window form for %d waves", what, ns);
     nparts = p.waves;
   } else if (p.win) {
     if (partial_elems < K * p.waves)
       return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)(K * p.waves));
     const dim3 grid(static_cast<unsigned>(p.waves / 4)), block(256);
-#define FEDAVG_SEGWIN(KM, VC)                                                                                       \
-  if (desc)                                                                                                        \
-    hipLaunchKernelGGL((reduce_sqdist_segwin_kernel<KM, VC, 4, true>), grid, block, 0, s, keys, tptrs, n_keys,     \
-                       units, k32, weights, out, partials, desc);                                                  \
-  else                                                                                                             \
-    hipLaunchKernelGGL((reduce_sqdist_segwin_kernel<KM, VC, 4, false>), grid, block, 0, s, keys, tptrs, n_keys,    \
-                       units, k32, weights, out, partials, nullptr);
-    switch (p.kmax) {
-      case 48: FEDAVG_SEGWIN(48, 4) break;
-      case 64: FEDAVG_SEGWIN(64, 2) break;
-      case 80: FEDAVG_SEGWIN(80, 2) break;
-      case 100: FEDAVG_SEGWIN(100, 2) break;
-      default: FEDAVG_SEGWIN(128, 1) break;
-    }
-#undef FEDAVG_SEGWIN
+    const bool found = for_win_band(p.kmax, [&](auto kmax, auto vec) {
+      constexpr int KMAX = decltype(kmax)::value, VEC = decltype(vec)::value;
+      if (desc)
+        hipLaunchKernelGGL((reduce_sqdist_segwin_kernel<KMAX, VEC, 4, true>), grid, block, 0, s, keys, tptrs, n_keys,
+                           units, k32, weights, out, partials, desc);
+      else
+        hipLaunchKernelGGL((reduce_sqdist_segwin_kernel<KMAX, VEC, 4, false>), grid, block, 0, s, keys, tptrs, n_keys,
+                           units, k32, weights, out, partials, nullptr);
+    });
+    if (!found) return set_error(FEDAVG_EMODE, "%s: no window instance for KMAX %d", what, p.kmax);
     nparts = p.waves;
   } else {
     const int S = static_cast<int>(p.span);
-#define FEDAVG_SEG_FUSED(C, MAP)                                                                                   \
-  if (S == C && (umap != nullptr) == MAP) {                                                                        \
-    if (seg_fused_per_cu<C, MAP>(K) <= 0) return set_error(FEDAVG_EMODE, "%s: tile does not fit LDS", what);       \
-    nparts = seg_fused_grid<C, MAP>(K, units);                                                                     \
-    if (partial_elems < K * nparts)                                                                                \
-      return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)(K * nparts));             \
-    hipLaunchKernelGGL((reduce_sqdist_segments_f32_kernel<C, MAP, MAP>), dim3(static_cast<unsigned>(nparts)),       \
-                       dim3(kBlock), static_cast<unsigned>(seg_fused_lds_bytes(K, C, MAP)), s, keys, tptrs, n_keys, \
-                       units, k32, weights, out, partials, umap);                                                   \
-  }
-    FEDAVG_SEG_FUSED(32, false)
-    FEDAVG_SEG_FUSED(32, true)
-    FEDAVG_SEG_FUSED(64, false)
-    FEDAVG_SEG_FUSED(64, true)
-    FEDAVG_SEG_FUSED(128, false)
-    FEDAVG_SEG_FUSED(128, true)
-    FEDAVG_SEG_FUSED(256, false)
-    FEDAVG_SEG_FUSED(256, true)
-#undef FEDAVG_SEG_FUSED
+    int rc = FEDAVG_OK;
+    const bool found = for_seg_tile(S, [&](auto cols) {
+      constexpr int C = decltype(cols)::value;
+      const auto launch = [&](auto map) {
+        constexpr bool MAP = decltype(map)::value;
+        if (seg_fused_per_cu<C, MAP>(K) <= 0) return set_error(FEDAVG_EMODE, "%s: tile does not fit LDS", what);
+        nparts = seg_fused_grid<C, MAP>(K, units);
+        if (partial_elems < K * nparts)
+          return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)(K * nparts));
+        hipLaunchKernelGGL((reduce_sqdist_segments_f32_kernel<C, MAP, MAP>), dim3(static_cast<unsigned>(nparts)),
+                           dim3(kBlock), static_cast<unsigned>(seg_fused_lds_bytes(K, C, MAP)), s, keys, tptrs, n_keys,
+                           units, k32, weights, out, partials, umap);
+        return static_cast<int>(FEDAVG_OK);
+      };
+      rc = umap != nullptr ? launch(std::true_type{}) : launch(std::false_type{});
+    });
+    if (!found) return set_error(FEDAVG_EMODE, "%s: no tile instance of %d columns", what, S);
+    if (rc) return rc;
   }
   int rc = launch_status(what);
   if (rc) return rc;
@@ -1681,9 +1656,7 @@ int64_t fedavg_reduce_sqdist_segments_partials(int64_t K) {
   if (K > kSegFusedMaxK)  // the split-row windows (device round)
     return K * segwinn_blocks(K, INT64_MAX / 2) + (seg_split_stamps() ? winn_stamp_elems(16) : 0);
   const int S = seg_fused_cols(K);
-  const int per_cu = S == 32 ? seg_fused_per_cu_max<32>(K)
-                     : (S == 64 ? seg_fused_per_cu_max<64>(K)
-                                : (S == 128 ? seg_fused_per_cu_max<128>(K) : seg_fused_per_cu_max<256>(K)));
+  const int per_cu = seg_fused_per_cu_max(S, K);
   const int64_t tiles = K * static_cast<int64_t>(per_cu > 0 ? per_cu : 1) * cu_count();
   const int64_t windows = K * segwin_waves_for(segwin_kmax(K), INT64_MAX / 2);  // a full window launch
   const int64_t split = K >= seg_split_min_k() ? K * segwinn_blocks(K, INT64_MAX / 2) : 0;  // 129-256: split windows

@@ -58,6 +58,25 @@ def test_every_exported_entry_point_is_declared(lib):
     assert exported == declared_functions(("fedavg_amd.h",))
 
 
+def test_product_library_holds_exactly_the_listed_kernels(lib):
+    """The product's gfx950 kernel set is tests/product_kernels.txt (DESIGN.md
+    §3's inventory, sorted demangled names): a dispatch helper that
+    instantiates more than a plan can launch, or drops an instance, fails here."""
+    import importlib.util
+
+    root = Path(__file__).resolve().parents[1]
+    spec = importlib.util.spec_from_file_location("kernel_inventory", root / "scripts" / "kernel_inventory.py")
+    inv = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(inv)
+    if not inv.have_tools():
+        pytest.skip("llvm-objcopy / llvm-readelf not found")
+    listed = (Path(__file__).with_name("product_kernels.txt")).read_text().splitlines()
+    built = sorted(inv.inventory(_lib.library_path()))
+    assert sorted(set(built) - set(listed)) == [], "kernels built but not listed"
+    assert sorted(set(listed) - set(built)) == [], "kernels listed but not built"
+    assert built == listed and len(built) == 114
+
+
 def test_probe_library_exports_product_and_tuning_hooks(lib):
     """libfedavg_amd_probe.so = the product entry points + every hook of
     include/fedavg_amd_tuning.h, each typed in _lib.TUNING_SIGNATURES."""
