@@ -156,6 +156,7 @@ int fedavg_reduce_sqdist_f32(const float* clients, int64_t K, int64_t P, int64_t
  * the groups' sums and rounds sqrt() to torch.cat's promoted dtype.
  * workspace : fedavg_client_sqdist_workspace_elems(K, P, elem_size) doubles
  * (elem_size 2, 4 or 8); rows 16-B aligned with ld a multiple of 16 B.
+ * (Aggregate + these sums in one read of the rows: fedavg_amd_fusedvec.h.)
  */
 int64_t fedavg_client_sqdist_workspace_elems(int64_t K, int64_t P, int64_t elem_size);
 int fedavg_client_sqdist_f64(const double* clients, int64_t K, int64_t P, int64_t ld,

@@ -9,7 +9,7 @@ import ctypes
 import threading
 from pathlib import Path
 
-from .build import LIB_PATH, PROBE_LIB_PATH
+from .build import FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -110,7 +110,19 @@ TUNING_SIGNATURES = {
     "fedavg_reduce_tiled_f32": (_c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _c_int, _vp]),
 }
 
+# libfedavg_amd_fusedvec.so (include/fedavg_amd_fusedvec.h)
+FUSEDVEC_SIGNATURES = {
+    "fedavg_fusedvec_abi_version": (_c_int, []),
+    "fedavg_fusedvec_last_error": (ctypes.c_char_p, []),
+    "fedavg_reduce_sqdist_vec_workspace": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "fedavg_fused_vec_plan_of": (_c_i64, [_c_i64, _c_i64, _c_i64, _c_int]),
+    "fedavg_reduce_sqdist_f64": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp]),
+    "fedavg_reduce_sqdist_f16": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp]),
+    "fedavg_reduce_sqdist_bf16": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp]),
+}
+
 ABI_VERSION = 1
+FUSEDVEC_ABI_VERSION = 1
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -131,6 +143,7 @@ class FedAvgLibraryError(RuntimeError):
 _lock = threading.Lock()
 _lib = None
 _probe = None
+_fusedvec = None
 
 
 def library_path() -> Path:
@@ -187,6 +200,47 @@ def load_probe() -> ctypes.CDLL:
             fn.argtypes = args
         _probe = lib
     return _probe
+
+
+def load_fusedvec() -> ctypes.CDLL:
+    """The fused aggregate + :291 library for fp64 / fp16 / bf16 rows
+    (include/fedavg_amd_fusedvec.h).  It calls the product library for its
+    two-pass route, so that one is loaded first.  No fallback: a missing or
+    stale library raises ``FedAvgLibraryError``."""
+    global _fusedvec
+    if _fusedvec is not None:
+        return _fusedvec
+    load()
+    with _lock:
+        if _fusedvec is not None:
+            return _fusedvec
+        if not FUSEDVEC_LIB_PATH.exists():
+            raise FedAvgLibraryError(
+                f"{FUSEDVEC_LIB_PATH} not built: run __graft_entry__.build(); there is no fallback for the "
+                "one-read aggregate + distances pass of fp64 / fp16 / bf16 rows")
+        try:
+            lib = ctypes.CDLL(str(FUSEDVEC_LIB_PATH))
+        except OSError as e:
+            raise FedAvgLibraryError(f"{FUSEDVEC_LIB_PATH} does not load: {e}") from e
+        for name, (res, args) in FUSEDVEC_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise FedAvgLibraryError(f"{FUSEDVEC_LIB_PATH} does not export {name}") from e
+            fn.restype = res
+            fn.argtypes = args
+        ver = lib.fedavg_fusedvec_abi_version()
+        if ver != FUSEDVEC_ABI_VERSION:
+            raise FedAvgLibraryError(f"ABI version {ver} != expected {FUSEDVEC_ABI_VERSION}; rebuild the library")
+        _fusedvec = lib
+    return _fusedvec
+
+
+def check_fusedvec(rc: int, what: str) -> None:
+    """``check`` for a call into libfedavg_amd_fusedvec.so (its own message)."""
+    if rc != 0:
+        msg = load_fusedvec().fedavg_fusedvec_last_error().decode(errors="replace")
+        raise FedAvgLibraryError(f"{what} failed (rc={rc}): {msg}")
 
 
 def f32_schedule(K: int, P: int, ld: int = 0) -> dict:

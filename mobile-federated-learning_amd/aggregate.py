@@ -181,12 +181,37 @@ def fuse_eligible(devbuf: torch.Tensor) -> bool:
             and devbuf.stride(-1) == 1)
 
 
+_FUSED_VEC_DTYPES = (torch.float64, torch.float16, torch.bfloat16)
+
+
+def fuse_eligible_vec(devbuf: torch.Tensor, out: Optional[torch.Tensor] = None) -> bool:
+    """fp64 / fp16 / bf16 rows the one-read aggregate + :291 pass takes
+    (fedavg_reduce_sqdist_{f64,f16,bf16}): K <= FUSED_MAX_K, the rows' start
+    and stride -- and ``out``, when given -- multiples of 16 BYTES.  A column
+    chunk (``column_chunks``) starts on a multiple of 64 elements, 128 B for
+    the 2-byte types, so the chunks of eligible rows are eligible.
+
+    Eligible means "one call gives the average and the sums", not "one read":
+    the library reads the rows once to 64 (fp64) / 128 (fp16, bf16) clients
+    and runs the two passes inside the call beyond that
+    (``fedavg_fused_vec_plan_of`` says which).  Either way the sums are kept
+    for ``client_distances``, as for fp32 rows above their fused range.
+    ``multi.ShardedAggregator``'s round goes through ``reduce_rows`` too, so
+    its shards of these dtypes take the same call."""
+    es = devbuf.element_size()
+    return (FUSE_DISTANCES and devbuf.dtype in _FUSED_VEC_DTYPES and 0 < devbuf.shape[0] <= FUSED_MAX_K
+            and devbuf.data_ptr() % 16 == 0 and (devbuf.shape[0] == 1 or (devbuf.stride(0) * es) % 16 == 0)
+            and (devbuf.shape[0] > 1 or (devbuf.shape[1] * es) % 16 == 0)
+            and devbuf.stride(-1) == 1 and (out is None or out.data_ptr() % 16 == 0))
+
+
 def reduce_rows(devbuf: torch.Tensor, w_dev: torch.Tensor, P: int, out: torch.Tensor,
                 sums: Optional[list] = None) -> None:
     """``reduce_packed`` of [K, ld] rows into ``out``; with ``sums`` (a list)
-    and fused-eligible rows, the :291 sums of squares of the same columns are
+    and fused-eligible rows (``fuse_eligible``: fp32; ``fuse_eligible_vec``:
+    fp64 / fp16 / bf16), the :291 sums of squares of the same columns are
     formed in the same pass and their [K] fp64 device tensor appended."""
-    if sums is not None and fuse_eligible(devbuf):
+    if sums is not None and (fuse_eligible(devbuf) or fuse_eligible_vec(devbuf, out)):
         sums.append(reduce_with_sqdist(devbuf, w_dev, P, out)[1])
     else:
         reduce_packed(devbuf, w_dev, P, out)
@@ -220,7 +245,7 @@ def reduce_and_fetch(devbuf: torch.Tensor, w_dev: torch.Tensor, P: int, d2h_stre
         reduce_rows(devbuf[:, c0:c1] if len(chunks) > 1 else devbuf, w_dev, c1 - c0, out_dev[c0:c1], parts)
         d2h_stream.wait_stream(compute)
         _fetch(out_dev[c0:c1], out_host[c0:c1], d2h_stream)
-    if parts:
+    if parts and len(parts) == len(chunks):  # every chunk fused (a one-row group's ragged last chunk may not be)
         total = parts[0]
         for s in parts[1:]:
             total = total + s

@@ -1,4 +1,5 @@
-"""Build recipe for libfedavg_amd.so and libfedavg_amd_probe.so (gfx950 only).
+"""Build recipe for libfedavg_amd.so, libfedavg_amd_probe.so and
+libfedavg_amd_fusedvec.so (gfx950 only).
 
     python -m mfl_amd.build           # or __graft_entry__.build()
 
@@ -17,6 +18,12 @@ The tuning hooks (``include/fedavg_amd_tuning.h``: kernel variants, probes)
 are NOT in the product library.  The same sources plus
 ``fedavg_variants.hip``, compiled with ``-DFEDAVG_TUNING``, link into
 ``lib/libfedavg_amd_probe.so``, which scripts/ and the variant tests load.
+
+``csrc/fedavg_fused_vec.hip`` (the one-read aggregate + :291 pass for fp64 /
+fp16 / bf16 rows, ``include/fedavg_amd_fusedvec.h``) is a product library of
+its own, ``lib/libfedavg_amd_fusedvec.so``: same flags, no ``FEDAVG_TUNING``,
+linked against ``libfedavg_amd.so`` (found next to it, ``$ORIGIN``) for the
+two-pass route.
 """
 from __future__ import annotations
 
@@ -34,6 +41,7 @@ HIP_SOURCES = [CSRC_DIR / "fedavg_reduce.hip", CSRC_DIR / "fedavg_dist.hip",
                CSRC_DIR / "fedavg_fpf.hip", CSRC_DIR / "fedavg_xfer.hip", CSRC_DIR / "fedavg_pack.hip",
                CSRC_DIR / "fedavg_segments.hip", CSRC_DIR / "fedavg_client.hip"]
 PROBE_SOURCES = [CSRC_DIR / "fedavg_variants.hip"]  # probe library only
+FUSEDVEC_SOURCES = [CSRC_DIR / "fedavg_fused_vec.hip"]  # libfedavg_amd_fusedvec.so only
 CSRC_HOST = CSRC_DIR / "fedavg_host.cpp"
 CSRC_COMMON = CSRC_DIR / "common.hpp"
 CSRC_WINDOW = CSRC_DIR / "window.hpp"  # what the rows and zero-copy window kernels share
@@ -46,6 +54,7 @@ OBJ_DIR = LIB_DIR / "obj"
 PROBE_OBJ_DIR = LIB_DIR / "obj_probe"
 LIB_PATH = LIB_DIR / "libfedavg_amd.so"
 PROBE_LIB_PATH = LIB_DIR / "libfedavg_amd_probe.so"
+FUSEDVEC_LIB_PATH = LIB_DIR / "libfedavg_amd_fusedvec.so"
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [
@@ -68,12 +77,12 @@ def hipcc_path() -> str:
 
 
 def sources():
-    return [*HIP_SOURCES, *PROBE_SOURCES, CSRC_HOST, CSRC_COMMON, CSRC_WINDOW, CSRC_STAGING, INCLUDE / "fedavg_amd.h",
-            INCLUDE / "fedavg_amd_tuning.h", Path(__file__)]
+    return [*HIP_SOURCES, *PROBE_SOURCES, *FUSEDVEC_SOURCES, CSRC_HOST, CSRC_COMMON, CSRC_WINDOW, CSRC_STAGING,
+            INCLUDE / "fedavg_amd.h", INCLUDE / "fedavg_amd_tuning.h", INCLUDE / "fedavg_amd_fusedvec.h", Path(__file__)]
 
 
 def up_to_date() -> bool:
-    for lib in (LIB_PATH, PROBE_LIB_PATH):
+    for lib in (LIB_PATH, PROBE_LIB_PATH, FUSEDVEC_LIB_PATH):
         if not lib.exists():
             return False
         t = lib.stat().st_mtime
@@ -121,9 +130,10 @@ def _compile_all(jobs, verbose):
         raise RuntimeError("\n".join(errors))
 
 
-def _link(objs, lib_path, verbose):
+def _link(objs, lib_path, verbose, extra=()):
     tmp = lib_path.with_suffix(".so.tmp")
-    cmd = [hipcc_path(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-pthread", "-o", str(tmp), *map(str, objs)]
+    cmd = [hipcc_path(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-pthread", "-o", str(tmp), *map(str, objs),
+           *extra]
     if verbose:
         print(" ".join(cmd))
     proc = subprocess.run(cmd, capture_output=True, text=True)
@@ -133,7 +143,8 @@ def _link(objs, lib_path, verbose):
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Build the product library and the probe library; returns the product path."""
+    """Build the product library, the probe library and the fused-vec
+    library; returns the product path."""
     if not force and up_to_date():
         return LIB_PATH
     OBJ_DIR.mkdir(parents=True, exist_ok=True)
@@ -148,9 +159,17 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         jobs.append((src, obj, ["-DFEDAVG_TUNING=1"]))
         probe_objs.append(obj)
     probe_objs.append(OBJ_DIR / (CSRC_HOST.name + ".o"))  # host packer: no tuning hooks
+    fusedvec_objs = []
+    for src in FUSEDVEC_SOURCES:
+        obj = OBJ_DIR / (src.name + ".o")
+        jobs.append((src, obj, []))
+        fusedvec_objs.append(obj)
     _compile_all(jobs, verbose)
     _link(objs, LIB_PATH, verbose)
     _link(probe_objs, PROBE_LIB_PATH, verbose)
+    # the two-pass route calls the product library, found next to this one at load time
+    _link(fusedvec_objs, FUSEDVEC_LIB_PATH, verbose,
+          extra=[f"-L{LIB_DIR}", f"-l:{LIB_PATH.name}", "-Wl,-rpath,$ORIGIN"])
     return LIB_PATH
 
 

@@ -264,17 +264,35 @@ def client_sqdist(clients: torch.Tensor, glob: torch.Tensor, P: Optional[int] = 
     return out
 
 
+_FUSEDVEC_ENTRY = {
+    torch.float64: "fedavg_reduce_sqdist_f64",
+    torch.float16: "fedavg_reduce_sqdist_f16",
+    torch.bfloat16: "fedavg_reduce_sqdist_bf16",
+}
+
+
 def reduce_with_sqdist(clients: torch.Tensor, weights: torch.Tensor, P: Optional[int] = None,
                        out: Optional[torch.Tensor] = None, *, stream: Optional[torch.cuda.Stream] = None):
     """One round's aggregate (fedavg_trainer.py:450-457) AND its :291 sums of
-    squares in one pass over fp32 rows: returns ``(out, sumsq)`` with ``out``
+    squares in one pass over the rows: returns ``(out, sumsq)`` with ``out``
     the bits of ``reduce_packed(clients, weights, P)`` and ``sumsq`` [K]
     float64 device sums as ``client_sqdist(clients, out, P)`` forms them.
-    K <= 1024 reads the rows once (fedavg_reduce_sqdist_f32); larger K runs
-    the two passes inside the same call."""
+    fp32 rows: K <= 1024 reads the rows once (fedavg_reduce_sqdist_f32).
+    fp64 rows to K = 64 and fp16 / bf16 rows to K = 128 read them once as
+    well (fedavg_reduce_sqdist_{f64,f16,bf16}, libfedavg_amd_fusedvec.so).
+    Larger K runs the two passes inside the same call.  Rows (and, for the
+    non-fp32 types, ``out``) must be 16-B aligned."""
     K, ld, P, dtype, out = _check_packed(clients, weights, P, out)
     if dtype != torch.float32:
-        raise TypeError("reduce_with_sqdist: fp32 rows only (other dtypes: reduce_packed + client_sqdist)")
+        entry = _FUSEDVEC_ENTRY[dtype]
+        lib = _lib.load_fusedvec()
+        n_ws = lib.fedavg_reduce_sqdist_vec_workspace(K, P, clients.element_size())
+        work = torch.empty(max(n_ws, 1), dtype=torch.float64, device=clients.device)
+        sumsq = torch.empty(K, dtype=torch.float64, device=clients.device)
+        rc = getattr(lib, entry)(clients.data_ptr(), K, P, ld, weights.data_ptr(), out.data_ptr(), work.data_ptr(),
+                                 n_ws, sumsq.data_ptr(), _stream_handle(stream, clients.device))
+        _lib.check_fusedvec(rc, entry)
+        return out, sumsq
     lib = _lib.load()
     n_ws = lib.fedavg_reduce_sqdist_workspace(K, P)
     work = torch.empty(max(n_ws, 1), dtype=torch.float64, device=clients.device)
