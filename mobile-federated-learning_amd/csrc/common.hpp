@@ -586,30 +586,6 @@ void launch_f32x4(const float* clients, int K, int64_t ld, int64_t P, const floa
   }
 }
 
-// Blocks of a kernel the whole chip holds at once (occupancy x CUs), cached
-// per (device, kernel) -- kernels of one signature share a template
-// instantiation of this function, so the cache must be keyed by the kernel.
-template <typename Kern>
-int64_t resident_blocks(Kern kernel, int block = kBlock) {
-  static std::mutex mu;
-  static std::map<std::tuple<int, const void*, int>, int64_t> cache;  // per device, kernel and block size
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 1024;
-  const auto key = std::make_tuple(dev, reinterpret_cast<const void*>(kernel), block);
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-  }
-  int per_cu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess || per_cu <= 0) per_cu = 1;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  const int64_t n = static_cast<int64_t>(per_cu) * cus;
-  std::lock_guard<std::mutex> lk(mu);
-  cache[key] = n;
-  return n;
-}
-
 inline int cu_count() {
   static std::mutex mu;
   static std::map<int, int> cache;
@@ -622,6 +598,53 @@ inline int cu_count() {
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
   cache[dev] = cus;
   return cus;
+}
+
+// The occupancy query, the only one: workgroups of `block` threads with `lds`
+// bytes of dynamic LDS that one CU keeps resident, cached per (device,
+// kernel, block size, LDS bytes).  Above 64 KiB the kernel's dynamic LDS limit
+// is raised first.  0 = the launch cannot be resident (the LDS request is not
+// granted, or the query failed).
+inline int occupancy_per_cu(const void* kernel, int block, int64_t lds) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, const void*, int, int64_t>, int> cache;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const auto key = std::make_tuple(dev, kernel, block, lds);
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+  }
+  int per_cu = 0;
+  if (lds > 65536 &&
+      hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) {
+    (void)hipGetLastError();
+  } else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, static_cast<size_t>(lds)) !=
+             hipSuccess) {
+    (void)hipGetLastError();
+    per_cu = 0;
+  }
+  std::lock_guard<std::mutex> lk(mu);
+  cache[key] = per_cu;
+  return per_cu;
+}
+
+// Kernels with dynamic LDS: resident workgroups PER CU, 0 = `lds` bytes
+// cannot be granted (the launchers report "does not fit LDS")
+template <typename Kern>
+int lds_blocks_per_cu(Kern kernel, int block, int64_t lds) {
+  return occupancy_per_cu(reinterpret_cast<const void*>(kernel), block, lds);
+}
+
+// Kernels without: blocks the WHOLE CHIP holds at once (occupancy x CUs),
+// never less than one per CU
+template <typename Kern>
+int64_t resident_blocks(Kern kernel, int block = kBlock) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 1024;
+  const int per_cu = occupancy_per_cu(reinterpret_cast<const void*>(kernel), block, 0);
+  return static_cast<int64_t>(per_cu > 0 ? per_cu : 1) * cu_count();
 }
 
 // Round-split dispatch: the column range is cut into the fewest EQUAL

@@ -523,76 +523,67 @@ inline int64_t fused_lds_bytes(int64_t K, int S, bool db = false) {
   return b > kBlock * 8 ? b : kBlock * 8;
 }
 
-// Workgroups per CU the fused kernel keeps resident at this K (LDS-bound),
-// after raising the kernel's dynamic LDS limit past 64 KiB where needed;
-// cached per (device, S, K).  0 = the LDS request cannot be granted.
+// One call of the fused pass as its launchers take it: the entry point's
+// arguments (partials = the workspace)
+struct FusedCall {
+  const float* clients;
+  int64_t K, P, ld;
+  const float* weights;
+  float* out;
+  double* partials;
+  int64_t partial_elems;
+  double* sumsq;
+  hipStream_t s;
+  const char* what;
+};
+
+const LaunchCtx kRowsLaunch{set_error, launch_status, "%s: workspace needs %lld doubles",
+                            reinterpret_cast<const void*>(client_sqdist_finalize_kernel)};
+
+// the launch step (window.hpp) on a call's workspace: partials[K][parts] (+ extra)
+template <class Launch>
+int fused_launch(const FusedCall& c, int64_t parts, int64_t extra, Launch&& launch, bool finalize = true) {
+  return launch_and_finalize(kRowsLaunch, c.what, c.K, parts, extra, c.partials, c.partial_elems, c.sumsq, c.s, launch,
+                             finalize);
+}
+
+// Workgroups per CU the fused kernel keeps resident at this K (LDS-bound);
+// 0 = the LDS request cannot be granted.
 template <int S, bool DB = false, int RW = 0, bool LO = false, int RM = 1>
 int fused_per_cu(int64_t K) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int64_t>, int> cache;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find({dev, K});
-  if (it != cache.end()) return it->second;
-  const auto kern = reduce_sqdist_f32_kernel<S, DB, RW, LO, RM>;
-  const int64_t lds = fused_lds_bytes(K, S, DB);
-  int per_cu = 0;
-  if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-  } else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, static_cast<size_t>(lds)) !=
-             hipSuccess) {
-    (void)hipGetLastError();
-    per_cu = 0;
-  }
-  cache[{dev, K}] = per_cu;
-  return per_cu;
+  return lds_blocks_per_cu(reduce_sqdist_f32_kernel<S, DB, RW, LO, RM>, kBlock, fused_lds_bytes(K, S, DB));
 }
 
 template <int S, bool DB = false, int RW = 0, bool LO = false, int RM = 1>
 int64_t fused_grid(int64_t K, int64_t P, int blocks_per_cu) {
-  const int per_cu = blocks_per_cu > 0 ? blocks_per_cu : fused_per_cu<S, DB, RW, LO, RM>(K);
-  const int64_t ntiles = (P + S - 1) / S;
-  const int64_t g = static_cast<int64_t>(per_cu) * cu_count();
-  return ntiles < g ? ntiles : g;
+  return persistent_grid(blocks_per_cu > 0 ? blocks_per_cu : fused_per_cu<S, DB, RW, LO, RM>(K), cu_count(),
+                         (P + S - 1) / S);
 }
 
+// RM = rows per thread in the squares: 1 up to 256 rows, else 2 (the variants')
 template <int S, bool DB, int RW, bool LO, int RM>
-int launch_fused_rm(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
-                    double* partials, int64_t partial_elems, double* sumsq, int blocks_per_cu, hipStream_t s,
-                    const char* what) {
-  if (RW > 0 && K > 4 * RW) return set_error(FEDAVG_EMODE, "%s: %d rows per wave cover K <= %d", what, RW, 4 * RW);
-  if (fused_per_cu<S, DB, RW, LO, RM>(K) <= 0)
-    return set_error(FEDAVG_EMODE, "%s: the %d-column tile does not fit LDS at K = %lld", what, S, (long long)K);
-  const int64_t ntiles = (P + S - 1) / S;
-  const int64_t grid = fused_grid<S, DB, RW, LO, RM>(K, P, blocks_per_cu);
-  if (partial_elems < K * grid)
-    return set_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)(K * grid));
-  hipLaunchKernelGGL((reduce_sqdist_f32_kernel<S, DB, RW, LO, RM>), dim3(static_cast<unsigned>(grid)), dim3(kBlock),
-                     static_cast<unsigned>(fused_lds_bytes(K, S, DB)), s, clients, static_cast<int>(K), ld, P, ntiles,
-                     weights, out, partials);
-  int rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(client_sqdist_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, partials, grid,
-                     sumsq);
-  return launch_status(what);
+int launch_fused_rm(const FusedCall& c, int blocks_per_cu) {
+  if (RW > 0 && c.K > 4 * RW)
+    return set_error(FEDAVG_EMODE, "%s: %d rows per wave cover K <= %d", c.what, RW, 4 * RW);
+  if (fused_per_cu<S, DB, RW, LO, RM>(c.K) <= 0)
+    return set_error(FEDAVG_EMODE, "%s: the %d-column tile does not fit LDS at K = %lld", c.what, S, (long long)c.K);
+  const int64_t ntiles = (c.P + S - 1) / S;
+  const int64_t grid = fused_grid<S, DB, RW, LO, RM>(c.K, c.P, blocks_per_cu);
+  return fused_launch(c, grid, 0, [&] {
+    hipLaunchKernelGGL((reduce_sqdist_f32_kernel<S, DB, RW, LO, RM>), dim3(static_cast<unsigned>(grid)), dim3(kBlock),
+                       static_cast<unsigned>(fused_lds_bytes(c.K, S, DB)), c.s, c.clients, static_cast<int>(c.K), c.ld,
+                       c.P, ntiles, c.weights, c.out, c.partials);
+  });
 }
 
-// RM = rows per thread in the squares: 1 up to 256 rows, else 2
+#ifdef FEDAVG_TUNING  // the variants pick RM by K; production names RM 1 (K <= 128)
 template <int S, bool DB = false, int RW = 0, bool LO = false>
-int launch_fused(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
-                 double* partials, int64_t partial_elems, double* sumsq, int blocks_per_cu, hipStream_t s,
-                 const char* what) {
-  if (K <= kBlock)
-    return launch_fused_rm<S, DB, RW, LO, 1>(clients, K, P, ld, weights, out, partials, partial_elems, sumsq,
-                                             blocks_per_cu, s, what);
-  if constexpr (RW == 0 && !LO)
-    return launch_fused_rm<S, DB, RW, LO, 2>(clients, K, P, ld, weights, out, partials, partial_elems, sumsq,
-                                             blocks_per_cu, s, what);
-  return set_error(FEDAVG_EMODE, "%s: this variant covers K <= %d", what, kBlock);
+int launch_fused(const FusedCall& c, int blocks_per_cu) {
+  if (c.K <= kBlock) return launch_fused_rm<S, DB, RW, LO, 1>(c, blocks_per_cu);
+  if constexpr (RW == 0 && !LO) return launch_fused_rm<S, DB, RW, LO, 2>(c, blocks_per_cu);
+  return set_error(FEDAVG_EMODE, "%s: this variant covers K <= %d", c.what, kBlock);
 }
+#endif  // FEDAVG_TUNING
 
 // ---------------------------------------------------------------------------
 // Register-staged fused tiles (round 3).  The LDS-DMA form above fills a
@@ -781,63 +772,36 @@ inline int64_t fused_rs_lds_bytes(int64_t K, int S, int mode = 0) { return mode 
 
 template <int S, int SLOTS, int MODE, int FLAGS = 0, int DEPTH = 1>
 int fused_rs_per_cu(int64_t K) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int64_t>, int> cache;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find({dev, K});
-  if (it != cache.end()) return it->second;
-  const auto kern = reduce_sqdist_rs_kernel<S, SLOTS, MODE, FLAGS, DEPTH>;
-  const int64_t lds = fused_rs_lds_bytes(K, S, MODE);
-  int per_cu = 0;
-  if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-  } else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, static_cast<size_t>(lds)) !=
-             hipSuccess) {
-    (void)hipGetLastError();
-    per_cu = 0;
-  }
-  cache[{dev, K}] = per_cu;
-  return per_cu;
+  return lds_blocks_per_cu(reduce_sqdist_rs_kernel<S, SLOTS, MODE, FLAGS, DEPTH>, kBlock,
+                           fused_rs_lds_bytes(K, S, MODE));
 }
 
 template <int S, int SLOTS, int MODE, int FLAGS = 0, int DEPTH = 1>
 int64_t fused_rs_grid(int64_t K, int64_t P, int blocks_per_cu) {
-  const int per_cu = blocks_per_cu > 0 ? blocks_per_cu : fused_rs_per_cu<S, SLOTS, MODE, FLAGS, DEPTH>(K);
-  const int64_t ntiles = (P + S - 1) / S;
-  const int64_t g = static_cast<int64_t>(per_cu) * cu_count();
-  return ntiles < g ? ntiles : g;
+  return persistent_grid(blocks_per_cu > 0 ? blocks_per_cu : fused_rs_per_cu<S, SLOTS, MODE, FLAGS, DEPTH>(K),
+                         cu_count(), (P + S - 1) / S);
 }
 
 template <int S, int SLOTS, int MODE = 0, int FLAGS = 0, int DEPTH = 1>
-int launch_fused_rs(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
-                    double* partials, int64_t partial_elems, double* sumsq, int blocks_per_cu, hipStream_t s,
-                    const char* what) {
+int launch_fused_rs(const FusedCall& c, int blocks_per_cu) {
+  const int64_t K = c.K;
   if ((K * S + 1023) / 1024 > SLOTS)
-    return set_error(FEDAVG_EMODE, "%s: %d slots per thread cover K <= %d at %d columns", what, SLOTS,
+    return set_error(FEDAVG_EMODE, "%s: %d slots per thread cover K <= %d at %d columns", c.what, SLOTS,
                      SLOTS * 1024 / S, S);
   const int per_cu = fused_rs_per_cu<S, SLOTS, MODE, FLAGS, DEPTH>(K);
   if (per_cu <= 0)
-    return set_error(FEDAVG_EMODE, "%s: the %d-column tile does not fit LDS at K = %lld", what, S, (long long)K);
+    return set_error(FEDAVG_EMODE, "%s: the %d-column tile does not fit LDS at K = %lld", c.what, S, (long long)K);
   if (blocks_per_cu > per_cu)
-    return set_error(FEDAVG_EMODE, "%s: %d workgroups per CU requested, %d resident", what, blocks_per_cu, per_cu);
-  const int64_t ntiles = (P + S - 1) / S;
-  const int64_t grid = fused_rs_grid<S, SLOTS, MODE, FLAGS, DEPTH>(K, P, blocks_per_cu);
+    return set_error(FEDAVG_EMODE, "%s: %d workgroups per CU requested, %d resident", c.what, blocks_per_cu, per_cu);
+  const int64_t ntiles = (c.P + S - 1) / S;
+  const int64_t grid = fused_rs_grid<S, SLOTS, MODE, FLAGS, DEPTH>(K, c.P, blocks_per_cu);
   if ((FLAGS & 6) != 0 && (cu_count() != 256 || grid != (blocks_per_cu > 0 ? blocks_per_cu : per_cu) * 256LL))
-    return set_error(FEDAVG_EMODE, "%s: the XCD / CU remaps need a full grid on 256 CUs", what);
-  if (partial_elems < K * grid)
-    return set_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)(K * grid));
-  hipLaunchKernelGGL((reduce_sqdist_rs_kernel<S, SLOTS, MODE, FLAGS, DEPTH>), dim3(static_cast<unsigned>(grid)),
-                     dim3(kBlock), static_cast<unsigned>(fused_rs_lds_bytes(K, S, MODE)), s, clients, static_cast<int>(K), ld, P, ntiles,
-                     weights, out, partials);
-  int rc = launch_status(what);
-  if (rc || MODE != 0) return rc;
-  hipLaunchKernelGGL(client_sqdist_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, partials, grid,
-                     sumsq);
-  return launch_status(what);
+    return set_error(FEDAVG_EMODE, "%s: the XCD / CU remaps need a full grid on 256 CUs", c.what);
+  return fused_launch(c, grid, 0, [&] {
+    hipLaunchKernelGGL((reduce_sqdist_rs_kernel<S, SLOTS, MODE, FLAGS, DEPTH>), dim3(static_cast<unsigned>(grid)),
+                       dim3(kBlock), static_cast<unsigned>(fused_rs_lds_bytes(K, S, MODE)), c.s, c.clients,
+                       static_cast<int>(K), c.ld, c.P, ntiles, c.weights, c.out, c.partials);
+  }, MODE == 0);  // the probe modes' partials are not sums
 }
 
 // ---------------------------------------------------------------------------
@@ -1149,33 +1113,24 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_win_kernel(
 template <int KMAX, int VEC, int NW, int MODE = 0, int MINW = win_min_waves(KMAX, VEC)>
 int64_t fused_win_waves(int64_t P, int blocks_per_cu) {
   const auto kern = reduce_sqdist_win_kernel<KMAX, VEC, NW, MODE, MINW>;
-  const int64_t per_cu = blocks_per_cu > 0 ? blocks_per_cu : resident_blocks(kern, 64 * NW) / cu_count();
-  const int64_t nwin = (P + 64 * VEC - 1) / (64 * VEC);
-  const int64_t need = (nwin + NW - 1) / NW;
-  const int64_t grid = per_cu * cu_count();
-  return (grid < need ? grid : need) * NW;
+  return window_waves(blocks_per_cu > 0 ? blocks_per_cu : resident_blocks(kern, 64 * NW) / cu_count(), cu_count(),
+                      (P + 64 * VEC - 1) / (64 * VEC), NW);
 }
 
 template <int KMAX, int VEC, int NW, int MODE = 0, int MINW = win_min_waves(KMAX, VEC)>
-int launch_fused_win(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
-                     double* partials, int64_t partial_elems, double* sumsq, int blocks_per_cu, hipStream_t s,
-                     const char* what) {
-  if (K > KMAX) return set_error(FEDAVG_EMODE, "%s: this window kernel covers K <= %d", what, KMAX);
-  if ((MODE & 64) != 0 && K <= 24) return set_error(FEDAVG_EMODE, "%s: LDS rows need K > 24", what);
-  if ((MODE & 128) != 0 && ld * 4 * 7 + 64 * VEC * 4 >= (int64_t(1) << 32))
-    return set_error(FEDAVG_EMODE, "%s: 8-row descriptors need 7 row pitches + a window < 4 GiB", what);
-  const int64_t waves = fused_win_waves<KMAX, VEC, NW, MODE, MINW>(P, blocks_per_cu);
-  if (waves <= 0) return set_error(FEDAVG_EMODE, "%s: the window kernel is not resident", what);
-  if (partial_elems < K * waves)
-    return set_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)(K * waves));
-  const int64_t nwin = (P + 64 * VEC - 1) / (64 * VEC);
-  hipLaunchKernelGGL((reduce_sqdist_win_kernel<KMAX, VEC, NW, MODE, MINW>), dim3(static_cast<unsigned>(waves / NW)),
-                     dim3(64 * NW), 0, s, clients, static_cast<int>(K), ld, P, nwin, weights, out, partials);
-  int rc = launch_status(what);
-  if (rc || (MODE & 1) != 0) return rc;
-  hipLaunchKernelGGL(client_sqdist_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, partials,
-                     waves, sumsq);
-  return launch_status(what);
+int launch_fused_win(const FusedCall& c, int blocks_per_cu) {
+  if (c.K > KMAX) return set_error(FEDAVG_EMODE, "%s: this window kernel covers K <= %d", c.what, KMAX);
+  if ((MODE & 64) != 0 && c.K <= 24) return set_error(FEDAVG_EMODE, "%s: LDS rows need K > 24", c.what);
+  if ((MODE & 128) != 0 && c.ld * 4 * 7 + 64 * VEC * 4 >= (int64_t(1) << 32))
+    return set_error(FEDAVG_EMODE, "%s: 8-row descriptors need 7 row pitches + a window < 4 GiB", c.what);
+  const int64_t waves = fused_win_waves<KMAX, VEC, NW, MODE, MINW>(c.P, blocks_per_cu);
+  if (waves <= 0) return set_error(FEDAVG_EMODE, "%s: the window kernel is not resident", c.what);
+  const int64_t nwin = (c.P + 64 * VEC - 1) / (64 * VEC);
+  return fused_launch(c, waves, 0, [&] {
+    hipLaunchKernelGGL((reduce_sqdist_win_kernel<KMAX, VEC, NW, MODE, MINW>), dim3(static_cast<unsigned>(waves / NW)),
+                       dim3(64 * NW), 0, c.s, c.clients, static_cast<int>(c.K), c.ld, c.P, nwin, c.weights, c.out,
+                       c.partials);
+  }, (MODE & 1) == 0);  // MODE 1: loads only
 }
 
 // ---------------------------------------------------------------------------
@@ -1434,35 +1389,20 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(KH, VEC)) void reduce_sqd
 // waves each) rounded down to a power of two per CU (split_per_cu), at most
 // one per window
 template <int KH, int VEC, int NSMAX, int PF = 0, int LE = 0, int MODE = 0>
-int64_t fused_winn_grid(int64_t K, int64_t P, int blocks_per_cu) {
+int launch_fused_winn(const FusedCall& c, int blocks_per_cu) {
+  const int64_t K = c.K;
+  if (K > NSMAX * KH) return set_error(FEDAVG_EMODE, "%s: this split window kernel covers K <= %d", c.what, NSMAX * KH);
   const int ns = static_cast<int>((K + KH - 1) / KH);
-  int64_t per_cu = blocks_per_cu;  // none resident: the caller reports it (grid 0)
-  if (per_cu <= 0) per_cu = split_per_cu(resident_blocks(reduce_sqdist_winn_kernel<KH, VEC, NSMAX, PF, LE, MODE>, 64 * ns));
-  const int64_t nwin = (P + 64 * VEC - 1) / (64 * VEC);
-  const int64_t grid = per_cu * cu_count();
-  return grid < nwin ? grid : nwin;
-}
-
-template <int KH, int VEC, int NSMAX, int PF = 0, int LE = 0, int MODE = 0>
-int launch_fused_winn(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
-                      double* partials, int64_t partial_elems, double* sumsq, int blocks_per_cu, hipStream_t s,
-                      const char* what) {
-  if (K > NSMAX * KH) return set_error(FEDAVG_EMODE, "%s: this split window kernel covers K <= %d", what, NSMAX * KH);
-  const int ns = static_cast<int>((K + KH - 1) / KH);
-  const int64_t nwin = (P + 64 * VEC - 1) / (64 * VEC);
-  const int64_t grid = fused_winn_grid<KH, VEC, NSMAX, PF, LE, MODE>(K, P, blocks_per_cu);
-  if (grid <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", what);
-  const int64_t need = K * grid + ((MODE & 8) != 0 ? winn_stamp_elems(NSMAX) : 0);
-  if (partial_elems < need)
-    return set_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)need);
-  hipLaunchKernelGGL((reduce_sqdist_winn_kernel<KH, VEC, NSMAX, PF, LE, MODE>), dim3(static_cast<unsigned>(grid)),
-                     dim3(static_cast<unsigned>(64 * ns)), 0, s, clients, static_cast<int>(K), ld, P, nwin, weights,
-                     out, partials);
-  int rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(client_sqdist_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, partials,
-                     grid, sumsq);
-  return launch_status(what);
+  const int64_t nwin = (c.P + 64 * VEC - 1) / (64 * VEC);
+  const auto kern = reduce_sqdist_winn_kernel<KH, VEC, NSMAX, PF, LE, MODE>;
+  const int64_t grid = persistent_grid(blocks_per_cu > 0 ? blocks_per_cu : split_per_cu(resident_blocks(kern, 64 * ns)),
+                                       cu_count(), nwin);
+  if (grid <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", c.what);
+  return fused_launch(c, grid, (MODE & 8) != 0 ? winn_stamp_elems(NSMAX) : 0, [&] {
+    hipLaunchKernelGGL((reduce_sqdist_winn_kernel<KH, VEC, NSMAX, PF, LE, MODE>), dim3(static_cast<unsigned>(grid)),
+                       dim3(static_cast<unsigned>(64 * ns)), 0, c.s, c.clients, static_cast<int>(K), c.ld, c.P, nwin,
+                       c.weights, c.out, c.partials);
+  });
 }
 #endif  // FEDAVG_TUNING
 
@@ -1672,35 +1612,30 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   }
 }
 
+// workgroups of the hand-off launch: the resident ones (ceil(K / 64) waves
+// each) rounded down to a power of two per CU (split_per_cu), at most one per
+// window; 0: none resident
 template <int NSMAX, int PF, int MODE = 0>
 int64_t fused_winf_grid(int64_t K, int64_t P) {
   const int ns = static_cast<int>((K + 63) / 64);
-  const int64_t per_cu = split_per_cu(resident_blocks(reduce_sqdist_winf_kernel<NSMAX, PF, MODE>, 64 * ns));
-  const int64_t nwin = (P + 63) / 64;
-  const int64_t grid = per_cu * cu_count();
-  return grid < nwin ? grid : nwin;
+  return persistent_grid(split_per_cu(resident_blocks(reduce_sqdist_winf_kernel<NSMAX, PF, MODE>, 64 * ns)), cu_count(),
+                         (P + 63) / 64);
 }
 
 template <int NSMAX, int PF, int MODE = 0>
-int launch_fused_winf(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
-                      double* partials, int64_t partial_elems, double* sumsq, hipStream_t s, const char* what) {
+int launch_fused_winf(const FusedCall& c) {
+  const int64_t K = c.K;
   if (K > NSMAX * 64 || K < 2)
-    return set_error(FEDAVG_EMODE, "%s: these split windows cover 2 <= K <= %d", what, NSMAX * 64);
+    return set_error(FEDAVG_EMODE, "%s: these split windows cover 2 <= K <= %d", c.what, NSMAX * 64);
   const int ns = static_cast<int>((K + 63) / 64);
-  const int64_t nwin = (P + 63) / 64;
-  const int64_t grid = fused_winf_grid<NSMAX, PF, MODE>(K, P);
-  if (grid <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", what);
-  const int64_t need = K * grid + ((MODE & 8) != 0 ? winn_stamp_elems(NSMAX) : 0);
-  if (partial_elems < need)
-    return set_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)need);
-  hipLaunchKernelGGL((reduce_sqdist_winf_kernel<NSMAX, PF, MODE>), dim3(static_cast<unsigned>(grid)),
-                     dim3(static_cast<unsigned>(64 * ns)), 0, s, clients, static_cast<int>(K), ld, P, nwin, weights,
-                     out, partials);
-  int rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(client_sqdist_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, partials,
-                     grid, sumsq);
-  return launch_status(what);
+  const int64_t nwin = (c.P + 63) / 64;
+  const int64_t grid = fused_winf_grid<NSMAX, PF, MODE>(K, c.P);
+  if (grid <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", c.what);
+  return fused_launch(c, grid, (MODE & 8) != 0 ? winn_stamp_elems(NSMAX) : 0, [&] {
+    hipLaunchKernelGGL((reduce_sqdist_winf_kernel<NSMAX, PF, MODE>), dim3(static_cast<unsigned>(grid)),
+                       dim3(static_cast<unsigned>(64 * ns)), 0, c.s, c.clients, static_cast<int>(K), c.ld, c.P, nwin,
+                       c.weights, c.out, c.partials);
+  });
 }
 
 #ifdef FEDAVG_TUNING
@@ -1849,25 +1784,17 @@ __global__ __launch_bounds__(128, win_min_waves(KH, VEC)) void reduce_sqdist_win
 }
 
 template <int KH, int VEC>
-int launch_fused_win2(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
-                      double* partials, int64_t partial_elems, double* sumsq, int blocks_per_cu, hipStream_t s,
-                      const char* what) {
-  if (K > 2 * KH) return set_error(FEDAVG_EMODE, "%s: this split window kernel covers K <= %d", what, 2 * KH);
+int launch_fused_win2(const FusedCall& c, int blocks_per_cu) {
+  if (c.K > 2 * KH) return set_error(FEDAVG_EMODE, "%s: this split window kernel covers K <= %d", c.what, 2 * KH);
   const auto kern = reduce_sqdist_win2_kernel<KH, VEC>;
-  const int64_t per_cu = blocks_per_cu > 0 ? blocks_per_cu : resident_blocks(kern, 128) / cu_count();
-  const int64_t nwin = (P + 64 * VEC - 1) / (64 * VEC);
-  int64_t grid = per_cu * cu_count();
-  if (grid > nwin) grid = nwin;
-  if (grid <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", what);
-  if (partial_elems < K * grid)
-    return set_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)(K * grid));
-  hipLaunchKernelGGL((reduce_sqdist_win2_kernel<KH, VEC>), dim3(static_cast<unsigned>(grid)), dim3(128), 0, s,
-                     clients, static_cast<int>(K), ld, P, nwin, weights, out, partials);
-  int rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(client_sqdist_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, partials,
-                     grid, sumsq);
-  return launch_status(what);
+  const int64_t nwin = (c.P + 64 * VEC - 1) / (64 * VEC);
+  const int64_t grid = persistent_grid(blocks_per_cu > 0 ? blocks_per_cu : resident_blocks(kern, 128) / cu_count(),
+                                       cu_count(), nwin);
+  if (grid <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", c.what);
+  return fused_launch(c, grid, 0, [&] {
+    hipLaunchKernelGGL((reduce_sqdist_win2_kernel<KH, VEC>), dim3(static_cast<unsigned>(grid)), dim3(128), 0, c.s,
+                       c.clients, static_cast<int>(c.K), c.ld, c.P, nwin, c.weights, c.out, c.partials);
+  });
 }
 #endif  // FEDAVG_TUNING
 
@@ -1964,55 +1891,66 @@ inline FusedPlan win_plan(int64_t K) {
   return band ? FusedPlan{kFusedWin, band->a, band->b} : FusedPlan{kFusedNone, 0, 0};
 }
 
-// waves of the production window launch for plan `pl` (0: not a window plan)
-inline int64_t win_waves(const FusedPlan& pl, int64_t P) {
-  int64_t waves = 0;
-  if (pl.kind == kFusedWin)
-    for_win_band(pl.S, [&](auto kmax, auto vec) {
-      constexpr int KMAX = decltype(kmax)::value, VEC = decltype(vec)::value;
-      waves = fused_win_waves<KMAX, VEC, 4, win_rows_mode(KMAX)>(P, 0);
-    });
-  return waves;
-}
-
 // The tile plans' instances: LDS-DMA tiles by columns, register-staged tiles
-// by {columns, slots}.  fused_plan returns entries of these tables; the
-// workspace size and the launch both go through for_lds_tile / for_rs_tile.
+// by {columns, slots}.  fused_plan returns entries of these tables.
 constexpr PlanEntry kLdsTiles[] = {{64, 0}, {128, 0}, {256, 0}};
 constexpr PlanEntry kRsTiles[] = {{256, 8}, {64, 16}, {32, 10}, {32, 16}};
+
+// The production instance a plan names, as a tag: parts(K, P) = workgroups
+// (one-wave windows: waves) of its launch, the partials' second dimension;
+// launch(call) = that launch.
+template <int KMAX, int VEC>
+struct WinInstance {  // one-wave windows, 4 waves per workgroup
+  static int64_t parts(int64_t, int64_t P) { return fused_win_waves<KMAX, VEC, 4, win_rows_mode(KMAX)>(P, 0); }
+  static int launch(const FusedCall& c) { return launch_fused_win<KMAX, VEC, 4, win_rows_mode(KMAX)>(c, 0); }
+};
+template <int NSMAX, int PF>
+struct SplitInstance {  // split-row windows, hand-off form
+  static int64_t parts(int64_t K, int64_t P) { return fused_winf_grid<NSMAX, PF>(K, P); }
+  static int launch(const FusedCall& c) { return launch_fused_winf<NSMAX, PF>(c); }
+};
+template <int S>
+struct LdsInstance {  // LDS-DMA tiles, K <= 128: one row per thread in the squares (RM 1)
+  static int64_t parts(int64_t K, int64_t P) { return fused_grid<S, false, 0, false, 1>(K, P, 0); }
+  static int launch(const FusedCall& c) { return launch_fused_rm<S, false, 0, false, 1>(c, 0); }
+};
+template <int S, int SLOTS>
+struct RsInstance {  // register-staged tiles
+  static int64_t parts(int64_t K, int64_t P) { return fused_rs_grid<S, SLOTS, 0>(K, P, 0); }
+  static int launch(const FusedCall& c) { return launch_fused_rs<S, SLOTS>(c, 0); }
+};
+
+// f(instance tag) for the production instance plan `pl` names; false: it
+// names none.  The only walk over the plan kinds: the workspace size and the
+// launch both come through here.
 template <class F>
-bool for_lds_tile(int S, F&& f) {  // f(S); false: no such tile
-  return for_entry<kLdsTiles>(S, kAnyB, [&](auto s, auto) { f(s); });
-}
-template <class F>
-bool for_rs_tile(int S, int slots, F&& f) {  // f(S, SLOTS); false: no such tile
-  return for_entry<kRsTiles>(S, slots, f);
+bool with_fused_instance(const FusedPlan& pl, F&& f) {
+  switch (pl.kind) {
+    case kFusedWin:
+      return for_win_band(pl.S, [&](auto kmax, auto vec) { f(WinInstance<decltype(kmax)::value, decltype(vec)::value>{}); });
+    case kFusedWinn:
+      return for_split(pl.slots,
+                       [&](auto nsmax, auto pf) { f(SplitInstance<decltype(nsmax)::value, decltype(pf)::value>{}); });
+    case kFusedLds:
+      return for_entry<kLdsTiles>(pl.S, kAnyB, [&](auto s, auto) { f(LdsInstance<decltype(s)::value>{}); });
+    case kFusedRs:
+      return for_entry<kRsTiles>(pl.S, pl.slots,
+                                 [&](auto s, auto slots) { f(RsInstance<decltype(s)::value, decltype(slots)::value>{}); });
+  }
+  return false;
 }
 
-// workgroups (one-wave windows: waves) of the production launch of plan `pl`:
-// the partials' second dimension
+// the partials' second dimension of the production launch of plan `pl` (0: no instance)
 inline int64_t fused_plan_parts(const FusedPlan& pl, int64_t K, int64_t P) {
   int64_t n = 0;
-  if (pl.kind == kFusedWin) {
-    n = win_waves(pl, P);
-  } else if (pl.kind == kFusedLds) {
-    for_lds_tile(pl.S, [&](auto s) { n = fused_grid<decltype(s)::value>(K, P, 0); });
-  } else if (pl.kind == kFusedWinn) {
-    for_split(pl.slots, [&](auto nsmax, auto pf) {
-      n = fused_winf_grid<decltype(nsmax)::value, decltype(pf)::value>(K, P);
-    });
-  } else if (pl.kind == kFusedRs) {
-    for_rs_tile(pl.S, pl.slots, [&](auto s, auto slots) {
-      n = fused_rs_grid<decltype(s)::value, decltype(slots)::value, 0>(K, P, 0);
-    });
-  }
+  with_fused_instance(pl, [&](auto inst) { n = decltype(inst)::parts(K, P); });
   return n;
 }
 
 inline FusedPlan fused_plan(int64_t K, int64_t P) {
   if (K < 1 || K > kFusedRowsMaxK) return {kFusedNone, 0, 0};
   const FusedPlan win = win_plan(K);
-  if (win.kind == kFusedWin && ((P + 64 * win.slots - 1) / (64 * win.slots) >= kWinMinPerWave * win_waves(win, P) ||
+  if (win.kind == kFusedWin && ((P + 64 * win.slots - 1) / (64 * win.slots) >= kWinMinPerWave * fused_plan_parts(win, K, P) ||
                                  (K >= kWinHoleMinK && K <= kWinHoleMaxK && P >= kWinHoleMinP)))
     return win;
   if (K <= 16) return {kFusedRs, 256, 8};
@@ -2128,22 +2066,18 @@ int sqdist_impl(const float* clients, int64_t K, int64_t P, int64_t ld, const fl
     return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned clients/glob and ld %% 4 == 0", what);
   if (cols != 4 && cols != 8) return set_error(FEDAVG_EMODE, "%s: cols must be 4 or 8", what);
   const int64_t nwaves = sqdist_waves_for(P, cols);
-  if (!workspace || workspace_elems < K * nwaves)
-    return set_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)(K * nwaves));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int k = static_cast<int>(K);
-  switch (unroll * 100 + cols) {
-    case 404: launch_sqdist<4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 804: launch_sqdist<8, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 408: launch_sqdist<4, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 208: launch_sqdist<2, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    default: return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", what, unroll, cols);
-  }
-  rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(client_sqdist_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, workspace,
-                     nwaves, sumsq);
-  return launch_status(what);
+  return launch_and_finalize(kRowsLaunch, what, K, nwaves, 0, workspace, workspace ? workspace_elems : 0, sumsq, s, [&] {
+    switch (unroll * 100 + cols) {
+      case 404: launch_sqdist<4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 804: launch_sqdist<8, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 408: launch_sqdist<4, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 208: launch_sqdist<2, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      default: return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", what, unroll, cols);
+    }
+    return static_cast<int>(FEDAVG_OK);
+  });
 }
 #endif  // FEDAVG_TUNING
 
@@ -2174,25 +2108,20 @@ int sqdist_vec_impl(const void* clients, int64_t K, int64_t P, int64_t ld, const
   const int64_t nvec = (P + lanes - 1) / lanes;
   const int cols = dist_vec_cols(nvec);
   const int64_t nwaves = sqdist_vec_waves(nvec, cols);
-  if (!workspace || workspace_elems < K * nwaves)
-    return set_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)(K * nwaves));
   hipStream_t s = static_cast<hipStream_t>(stream);
   using vec = typename D::vec;
   const int64_t blocks = (nvec + kBlock * cols - 1) / (kBlock * cols);
-  if (cols == kDistCols)
-    hipLaunchKernelGGL((client_sqdist_vec_kernel<D, kDistRows, kDistCols>), dim3(static_cast<unsigned>(blocks)),
-                       dim3(kBlock), 0, s, reinterpret_cast<const vec*>(clients), static_cast<int>(K), ld / lanes, nvec,
-                       static_cast<int>(P % lanes), reinterpret_cast<const vec*>(glob), workspace, nwaves);
-  else
-    hipLaunchKernelGGL((client_sqdist_vec_kernel<D, kDistSmallRows, kDistSmallCols>),
-                       dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, reinterpret_cast<const vec*>(clients),
-                       static_cast<int>(K), ld / lanes, nvec, static_cast<int>(P % lanes),
-                       reinterpret_cast<const vec*>(glob), workspace, nwaves);
-  rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(client_sqdist_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, workspace,
-                     nwaves, sumsq);
-  return launch_status(what);
+  return launch_and_finalize(kRowsLaunch, what, K, nwaves, 0, workspace, workspace ? workspace_elems : 0, sumsq, s, [&] {
+    if (cols == kDistCols)
+      hipLaunchKernelGGL((client_sqdist_vec_kernel<D, kDistRows, kDistCols>), dim3(static_cast<unsigned>(blocks)),
+                         dim3(kBlock), 0, s, reinterpret_cast<const vec*>(clients), static_cast<int>(K), ld / lanes,
+                         nvec, static_cast<int>(P % lanes), reinterpret_cast<const vec*>(glob), workspace, nwaves);
+    else
+      hipLaunchKernelGGL((client_sqdist_vec_kernel<D, kDistSmallRows, kDistSmallCols>),
+                         dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, reinterpret_cast<const vec*>(clients),
+                         static_cast<int>(K), ld / lanes, nvec, static_cast<int>(P % lanes),
+                         reinterpret_cast<const vec*>(glob), workspace, nwaves);
+  });
 }
 
 int sqdist_buf_impl(const float* clients, int64_t K, int64_t P, int64_t ld, const float* glob, double* workspace,
@@ -2206,67 +2135,63 @@ int sqdist_buf_impl(const float* clients, int64_t K, int64_t P, int64_t ld, cons
   if (cols != 1 && cols != 2 && cols != 4 && cols != 8 && cols != 12 && cols != 16)
     return set_error(FEDAVG_EMODE, "%s: cols must be 1, 2, 4, 8, 12 or 16", what);
   const int64_t nwaves = sqdist_waves_for(P, cols);
-  if (!workspace || workspace_elems < K * nwaves)
-    return set_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)(K * nwaves));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int k = static_cast<int>(K);
-  switch (unroll * 100 + cols) {
-    // production (fedavg_client_sqdist_f32, dist_cols): 4 chains at U2 x C16, U4 x C8, U4 x C4; 2 at U8 x C2
-    case 4000216: launch_sqdist<2, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000408: launch_sqdist<4, 8, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000404: launch_sqdist<4, 4, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000802: launch_sqdist<8, 2, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+  return launch_and_finalize(kRowsLaunch, what, K, nwaves, 0, workspace, workspace ? workspace_elems : 0, sumsq, s, [&] {
+    switch (unroll * 100 + cols) {
+      // production (fedavg_client_sqdist_f32, dist_cols): 4 chains at U2 x C16, U4 x C8, U4 x C4; 2 at U8 x C2
+      case 4000216: launch_sqdist<2, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4000408: launch_sqdist<4, 8, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4000404: launch_sqdist<4, 4, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4000802: launch_sqdist<8, 2, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
 #ifdef FEDAVG_TUNING  // every other shape: fedavg_client_sqdist_buf, probe library only
-    case 408: launch_sqdist<4, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 804: launch_sqdist<8, 4, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 216: launch_sqdist<2, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    // register-capped forms (launch_bounds min waves per SIMD 3 / 4): more
-    // waves resident, fewer loads in flight per wave
-    case 30216: launch_sqdist<2, 16, true, 3>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 40216: launch_sqdist<2, 16, true, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 30408: launch_sqdist<4, 8, true, 3>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 116: launch_sqdist<1, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 112: launch_sqdist<1, 12, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 212: launch_sqdist<2, 12, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 208: launch_sqdist<2, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 808: launch_sqdist<8, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    // 2 / 4 interleaved fp64 chains per row (codes + 1,000,000 x ACC)
-    case 2000216: launch_sqdist<2, 16, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 2000408: launch_sqdist<4, 8, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 8000216: launch_sqdist<2, 16, true, 1, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 16000216: launch_sqdist<2, 16, true, 1, 16>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    // U = 0: row k + 1 loads while row k is summed (one row of registers each)
-    case 16: launch_sqdist<0, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000016: launch_sqdist<0, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000012: launch_sqdist<0, 12, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000008: launch_sqdist<0, 8, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    // 4 chains under a register cap (min waves per SIMD 3 / 4)
-    case 4030212: launch_sqdist<2, 12, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4030216: launch_sqdist<2, 16, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4040208: launch_sqdist<2, 8, true, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4030308: launch_sqdist<3, 8, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    // narrow column groups for small models (more workgroups per launch)
-    case 4000804: launch_sqdist<8, 4, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000402: launch_sqdist<4, 2, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000801: launch_sqdist<8, 1, true, 1, 1>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4001601: launch_sqdist<16, 1, true, 1, 1>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 4000116: launch_sqdist<1, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    // interleaved loads and squares, L loads in flight: + 100000000 x L
-    case 204000216: launch_sqdist<2, 16, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 404000216: launch_sqdist<2, 16, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 804000216: launch_sqdist<2, 16, true, 1, 4, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 204000404: launch_sqdist<4, 4, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 404000404: launch_sqdist<4, 4, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 204000408: launch_sqdist<4, 8, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-    case 404000408: launch_sqdist<4, 8, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 408: launch_sqdist<4, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 804: launch_sqdist<8, 4, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 216: launch_sqdist<2, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      // register-capped forms (launch_bounds min waves per SIMD 3 / 4): more
+      // waves resident, fewer loads in flight per wave
+      case 30216: launch_sqdist<2, 16, true, 3>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 40216: launch_sqdist<2, 16, true, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 30408: launch_sqdist<4, 8, true, 3>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 116: launch_sqdist<1, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 112: launch_sqdist<1, 12, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 212: launch_sqdist<2, 12, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 208: launch_sqdist<2, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 808: launch_sqdist<8, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      // 2 / 4 interleaved fp64 chains per row (codes + 1,000,000 x ACC)
+      case 2000216: launch_sqdist<2, 16, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 2000408: launch_sqdist<4, 8, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 8000216: launch_sqdist<2, 16, true, 1, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 16000216: launch_sqdist<2, 16, true, 1, 16>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      // U = 0: row k + 1 loads while row k is summed (one row of registers each)
+      case 16: launch_sqdist<0, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4000016: launch_sqdist<0, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4000012: launch_sqdist<0, 12, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4000008: launch_sqdist<0, 8, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      // 4 chains under a register cap (min waves per SIMD 3 / 4)
+      case 4030212: launch_sqdist<2, 12, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4030216: launch_sqdist<2, 16, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4040208: launch_sqdist<2, 8, true, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4030308: launch_sqdist<3, 8, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      // narrow column groups for small models (more workgroups per launch)
+      case 4000804: launch_sqdist<8, 4, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4000402: launch_sqdist<4, 2, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4000801: launch_sqdist<8, 1, true, 1, 1>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4001601: launch_sqdist<16, 1, true, 1, 1>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 4000116: launch_sqdist<1, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      // interleaved loads and squares, L loads in flight: + 100000000 x L
+      case 204000216: launch_sqdist<2, 16, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 404000216: launch_sqdist<2, 16, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 804000216: launch_sqdist<2, 16, true, 1, 4, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 204000404: launch_sqdist<4, 4, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 404000404: launch_sqdist<4, 4, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 204000408: launch_sqdist<4, 8, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
+      case 404000408: launch_sqdist<4, 8, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
 #endif  // FEDAVG_TUNING
-    default: return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", what, unroll, cols);
-  }
-  rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(client_sqdist_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, workspace,
-                     nwaves, sumsq);
-  return launch_status(what);
+      default: return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", what, unroll, cols);
+    }
+    return static_cast<int>(FEDAVG_OK);
+  });
 }
 
 }  // namespace
@@ -2360,29 +2285,8 @@ int fedavg_reduce_sqdist_f32(const float* clients, int64_t K, int64_t P, int64_t
   }
   const FusedPlan pl = fused_plan(K, P);
   if (pl.kind != kFusedNone && aligned4(out) && aligned4(weights)) {
-    bool found = false;
-    if (pl.kind == kFusedWin)
-      found = for_win_band(pl.S, [&](auto kmax, auto vec) {
-        constexpr int KMAX = decltype(kmax)::value, VEC = decltype(vec)::value;
-        rc = launch_fused_win<KMAX, VEC, 4, win_rows_mode(KMAX)>(clients, K, P, ld, weights, out, workspace,
-                                                                  workspace_elems, sumsq, 0, s, what);
-      });
-    else if (pl.kind == kFusedWinn)
-      found = for_split(pl.slots, [&](auto nsmax, auto pf) {
-        rc = launch_fused_winf<decltype(nsmax)::value, decltype(pf)::value>(clients, K, P, ld, weights, out, workspace,
-                                                                            workspace_elems, sumsq, s, what);
-      });
-    else if (pl.kind == kFusedLds)  // K <= 128: one row per thread in the squares (RM 1; launch_fused's RM 2 is the variants')
-      found = for_lds_tile(pl.S, [&](auto cols) {
-        rc = launch_fused_rm<decltype(cols)::value, false, 0, false, 1>(clients, K, P, ld, weights, out, workspace,
-                                                                        workspace_elems, sumsq, 0, s, what);
-      });
-    else
-      found = for_rs_tile(pl.S, pl.slots, [&](auto cols, auto slots) {
-        rc = launch_fused_rs<decltype(cols)::value, decltype(slots)::value>(clients, K, P, ld, weights, out, workspace,
-                                                                            workspace_elems, sumsq, 0, s, what);
-      });
-    if (!found)
+    const FusedCall call{clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, s, what};
+    if (!with_fused_instance(pl, [&](auto inst) { rc = decltype(inst)::launch(call); }))
       return set_error(FEDAVG_EMODE, "%s: plan %d / %d / %d names no kernel instance", what, pl.kind, pl.S, pl.slots);
     return rc;
   }
@@ -2411,14 +2315,14 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
   if (rc) return rc;
   if (P == 0 || K > 1024 || !aligned16(clients) || (ld % 4) != 0 || !sumsq || !workspace)
     return set_error(FEDAVG_EINVAL, "%s: needs 1 <= K <= 1024, P >= 1, 16-B aligned rows", what);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  const FusedCall call{clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq,
+                       static_cast<hipStream_t>(stream), what};
   // cols + 1000: double-buffered tiles (the next tile's loads in flight while
   // one is used); + 10000: rows per wave with one register accumulator each
   switch (cols) {
 #define FEDAVG_FUSED_CASE(C, DBUF, RWS)                                                                           \
   case C + (DBUF ? 1000 : 0) + (RWS ? 10000 : 0):                                                                \
-    return launch_fused<C, DBUF, RWS>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq,         \
-                                      blocks_per_cu, s, what);
+    return launch_fused<C, DBUF, RWS>(call, blocks_per_cu);
     FEDAVG_FUSED_CASE(32, false, 0)
     FEDAVG_FUSED_CASE(64, false, 0)
     FEDAVG_FUSED_CASE(128, false, 0)
@@ -2432,19 +2336,15 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     FEDAVG_FUSED_CASE(128, true, 32)
 #undef FEDAVG_FUSED_CASE
     // + 100000: the tile loads alone (no average, no sums: a traffic probe, wrong results)
-    case 100064: return launch_fused<64, false, 0, true>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                         sumsq, blocks_per_cu, s, what);
-    case 100128: return launch_fused<128, false, 0, true>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                          sumsq, blocks_per_cu, s, what);
-    case 101064: return launch_fused<64, true, 0, true>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                        sumsq, blocks_per_cu, s, what);
+    case 100064: return launch_fused<64, false, 0, true>(call, blocks_per_cu);
+    case 100128: return launch_fused<128, false, 0, true>(call, blocks_per_cu);
+    case 101064: return launch_fused<64, true, 0, true>(call, blocks_per_cu);
     // register-staged tiles (reduce_sqdist_rs_kernel): 200000 + S; 210000 + S
     // with the slots of K = 100 at 128 / 256 columns; + 100000: loads only,
     // + 200000: loads + LDS writes (traffic probes, wrong results)
 #define FEDAVG_RS_CASE(CODE, C, SL, MODE)                                                                         \
   case CODE:                                                                                                     \
-    return launch_fused_rs<C, SL, MODE>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq,      \
-                                        blocks_per_cu, s, what);
+    return launch_fused_rs<C, SL, MODE>(call, blocks_per_cu);
     FEDAVG_RS_CASE(200032, 32, 10, 0)
     FEDAVG_RS_CASE(200064, 64, 8, 0)
     FEDAVG_RS_CASE(200128, 128, 8, 0)
@@ -2460,64 +2360,40 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
 #undef FEDAVG_RS_CASE
     // + 1000000: the same over a TILED buffer [ceil(P / S)][K][S] (probe: is the
     // row-major tile walk limited by the spread of its K row segments?)
-    case 1200064: return launch_fused_rs<64, 8, 0, 1>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                         sumsq, blocks_per_cu, s, what);
-    case 1300064: return launch_fused_rs<64, 8, 1, 1>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                         sumsq, blocks_per_cu, s, what);
-    case 1310128: return launch_fused_rs<128, 13, 1, 1>(clients, K, P, ld, weights, out, workspace,
-                                                         workspace_elems, sumsq, blocks_per_cu, s, what);
+    case 1200064: return launch_fused_rs<64, 8, 0, 1>(call, blocks_per_cu);
+    case 1300064: return launch_fused_rs<64, 8, 1, 1>(call, blocks_per_cu);
+    case 1310128: return launch_fused_rs<128, 13, 1, 1>(call, blocks_per_cu);
     // + 2000000 / 4000000: XCD-contiguous / XCD- and CU-contiguous tile sweeps
-    case 2200064: return launch_fused_rs<64, 8, 0, 2>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                      sumsq, blocks_per_cu, s, what);
-    case 2300064: return launch_fused_rs<64, 8, 1, 2>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                      sumsq, blocks_per_cu, s, what);
-    case 4200064: return launch_fused_rs<64, 8, 0, 4>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                      sumsq, blocks_per_cu, s, what);
-    case 4300064: return launch_fused_rs<64, 8, 1, 4>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                      sumsq, blocks_per_cu, s, what);
-    case 4200032: return launch_fused_rs<32, 10, 0, 4>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                       sumsq, blocks_per_cu, s, what);
+    case 2200064: return launch_fused_rs<64, 8, 0, 2>(call, blocks_per_cu);
+    case 2300064: return launch_fused_rs<64, 8, 1, 2>(call, blocks_per_cu);
+    case 4200064: return launch_fused_rs<64, 8, 0, 4>(call, blocks_per_cu);
+    case 4300064: return launch_fused_rs<64, 8, 1, 4>(call, blocks_per_cu);
+    case 4200032: return launch_fused_rs<32, 10, 0, 4>(call, blocks_per_cu);
     // + 10000000: two tiles in flight per workgroup; 5300064 / 5310128: loads
     // only, no LDS (occupancy from registers alone)
-    case 10200064: return launch_fused_rs<64, 8, 0, 0, 2>(clients, K, P, ld, weights, out, workspace,
-                                                          workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 10200032: return launch_fused_rs<32, 10, 0, 0, 2>(clients, K, P, ld, weights, out, workspace,
-                                                           workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 10200128: return launch_fused_rs<128, 8, 0, 0, 2>(clients, K, P, ld, weights, out, workspace,
-                                                           workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 10300064: return launch_fused_rs<64, 8, 1, 0, 2>(clients, K, P, ld, weights, out, workspace,
-                                                          workspace_elems, sumsq, blocks_per_cu, s, what);
+    case 10200064: return launch_fused_rs<64, 8, 0, 0, 2>(call, blocks_per_cu);
+    case 10200032: return launch_fused_rs<32, 10, 0, 0, 2>(call, blocks_per_cu);
+    case 10200128: return launch_fused_rs<128, 8, 0, 0, 2>(call, blocks_per_cu);
+    case 10300064: return launch_fused_rs<64, 8, 1, 0, 2>(call, blocks_per_cu);
     // many clients: S = 32 with 16 / 32 slots per thread (K <= 512 / 1024), S = 64 with 16 (K <= 256)
-    case 200032 + 1600000: return launch_fused_rs<32, 16>(clients, K, P, ld, weights, out, workspace,
-                                                         workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 200032 + 3200000: return launch_fused_rs<32, 32>(clients, K, P, ld, weights, out, workspace,
-                                                         workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 200064 + 1600000: return launch_fused_rs<64, 16>(clients, K, P, ld, weights, out, workspace,
-                                                         workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 5300064: return launch_fused_rs<64, 8, 3>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                   sumsq, blocks_per_cu, s, what);
+    case 200032 + 1600000: return launch_fused_rs<32, 16>(call, blocks_per_cu);
+    case 200032 + 3200000: return launch_fused_rs<32, 32>(call, blocks_per_cu);
+    case 200064 + 1600000: return launch_fused_rs<64, 16>(call, blocks_per_cu);
+    case 5300064: return launch_fused_rs<64, 8, 3>(call, blocks_per_cu);
     // wide tiles with 2-3 tiles in flight (registers) beside the one in LDS:
     // 20000000 + DEPTH * 1000000 + S (K = 100: 13 slots at 128, 25 at 256)
-    case 22000128: return launch_fused_rs<128, 13, 0, 0, 2>(clients, K, P, ld, weights, out, workspace,
-                                                            workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 23000128: return launch_fused_rs<128, 13, 0, 0, 3>(clients, K, P, ld, weights, out, workspace,
-                                                            workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 22000256: return launch_fused_rs<256, 25, 0, 0, 2>(clients, K, P, ld, weights, out, workspace,
-                                                            workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 23000256: return launch_fused_rs<256, 25, 0, 0, 3>(clients, K, P, ld, weights, out, workspace,
-                                                            workspace_elems, sumsq, blocks_per_cu, s, what);
-    case 5310128: return launch_fused_rs<128, 13, 3>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                     sumsq, blocks_per_cu, s, what);
-    case 5310256: return launch_fused_rs<256, 25, 3>(clients, K, P, ld, weights, out, workspace, workspace_elems,
-                                                     sumsq, blocks_per_cu, s, what);
-    case 15300064: return launch_fused_rs<64, 8, 3, 0, 2>(clients, K, P, ld, weights, out, workspace,
-                                                          workspace_elems, sumsq, blocks_per_cu, s, what);
+    case 22000128: return launch_fused_rs<128, 13, 0, 0, 2>(call, blocks_per_cu);
+    case 23000128: return launch_fused_rs<128, 13, 0, 0, 3>(call, blocks_per_cu);
+    case 22000256: return launch_fused_rs<256, 25, 0, 0, 2>(call, blocks_per_cu);
+    case 23000256: return launch_fused_rs<256, 25, 0, 0, 3>(call, blocks_per_cu);
+    case 5310128: return launch_fused_rs<128, 13, 3>(call, blocks_per_cu);
+    case 5310256: return launch_fused_rs<256, 25, 3>(call, blocks_per_cu);
+    case 15300064: return launch_fused_rs<64, 8, 3, 0, 2>(call, blocks_per_cu);
     // wave-owned windows (reduce_sqdist_win_kernel): 60000000 + MODE *
     // 1000000 + NW * 10 + VEC at K <= 100; 70000000 + KMAX * 100 + NW * 10 + VEC
 #define FEDAVG_WIN_CASE(VEC, NW, MODE)                                                                            \
   case 60000000 + MODE * 1000000 + NW * 10 + VEC:                                                                \
-    return launch_fused_win<100, VEC, NW, MODE>(clients, K, P, ld, weights, out, workspace, workspace_elems,     \
-                                                sumsq, blocks_per_cu, s, what);
+    return launch_fused_win<100, VEC, NW, MODE>(call, blocks_per_cu);
     FEDAVG_WIN_CASE(2, 4, 1)
     FEDAVG_WIN_CASE(4, 4, 1)
     FEDAVG_WIN_CASE(2, 4, 2)
@@ -2534,12 +2410,10 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     FEDAVG_WIN_CASE(2, 4, 256)  // broadcast weights (round 6)
     FEDAVG_WIN_CASE(2, 4, 320)  // LDS rows + broadcast weights (round 6)
     case 60000000 + 192 * 1000000 + 42:  // LDS rows + 8-row descriptors
-      return launch_fused_win<100, 2, 4, 192>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq,
-                                              blocks_per_cu, s, what);
+      return launch_fused_win<100, 2, 4, 192>(call, blocks_per_cu);
 #define FEDAVG_WINK_CASE(KMAX, VEC, MINW)                                                                         \
   case 70000000 + KMAX * 100 + 40 + VEC:                                                                         \
-    return launch_fused_win<KMAX, VEC, 4, 0, MINW>(clients, K, P, ld, weights, out, workspace, workspace_elems,  \
-                                                   sumsq, blocks_per_cu, s, what);
+    return launch_fused_win<KMAX, VEC, 4, 0, MINW>(call, blocks_per_cu);
     FEDAVG_WINK_CASE(100, 2, 2)
     FEDAVG_WINK_CASE(80, 2, 2)
     FEDAVG_WINK_CASE(64, 2, 3)
@@ -2552,8 +2426,7 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     // split-row windows (reduce_sqdist_win2_kernel): 80000000 + KH * 100 + VEC, K <= 2 KH
 #define FEDAVG_WIN2_CASE(KH, VEC)                                                                                 \
   case 80000000 + KH * 100 + VEC:                                                                                \
-    return launch_fused_win2<KH, VEC>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq,        \
-                                      blocks_per_cu, s, what);
+    return launch_fused_win2<KH, VEC>(call, blocks_per_cu);
     FEDAVG_WIN2_CASE(50, 2)
     FEDAVG_WIN2_CASE(40, 2)
     FEDAVG_WIN2_CASE(32, 2)
@@ -2565,8 +2438,7 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     // 85000000 + NSMAX * 10000 + KH * 10 + VEC
 #define FEDAVG_WINN_CASE(KH, VEC, NSMAX)                                                                          \
   case 85000000 + NSMAX * 10000 + KH * 10 + VEC:                                                                 \
-    return launch_fused_winn<KH, VEC, NSMAX>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq,  \
-                                             blocks_per_cu, s, what);
+    return launch_fused_winn<KH, VEC, NSMAX>(call, blocks_per_cu);
     FEDAVG_WINN_CASE(64, 1, 8)
     FEDAVG_WINN_CASE(64, 2, 8)
     FEDAVG_WINN_CASE(32, 2, 16)
@@ -2577,8 +2449,7 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     // window prefetched: 87000000 + PF * 100 + NSMAX
 #define FEDAVG_WINNPF_CASE(NSMAX, PF)                                                                             \
   case 87000000 + PF * 100 + NSMAX:                                                                              \
-    return launch_fused_winn<64, 1, NSMAX, PF>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, \
-                                               blocks_per_cu, s, what);
+    return launch_fused_winn<64, 1, NSMAX, PF>(call, blocks_per_cu);
     FEDAVG_WINNPF_CASE(8, 4)
     FEDAVG_WINNPF_CASE(8, 8)
     FEDAVG_WINNPF_CASE(8, 12)
@@ -2597,8 +2468,7 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     // 89000000 + PF * 100 + NSMAX
 #define FEDAVG_WINN128_CASE(NSMAX, PF)                                                                            \
   case 89000000 + PF * 100 + NSMAX:                                                                              \
-    return launch_fused_winn<128, 1, NSMAX, PF>(clients, K, P, ld, weights, out, workspace, workspace_elems,       \
-                                                sumsq, blocks_per_cu, s, what);
+    return launch_fused_winn<128, 1, NSMAX, PF>(call, blocks_per_cu);
     FEDAVG_WINN128_CASE(8, 0)
     FEDAVG_WINN128_CASE(8, 16)
     FEDAVG_WINN128_CASE(8, 32)
@@ -2611,8 +2481,7 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     // + LE * 100 + PF (NSMAX 16)
 #define FEDAVG_WINNLE_CASE(PF, LE, MODE)                                                                         \
   case 88000000 + MODE * 100000 + LE * 100 + PF:                                                                 \
-    return launch_fused_winn<64, 1, 16, PF, LE, MODE>(clients, K, P, ld, weights, out, workspace, workspace_elems, \
-                                                      sumsq, blocks_per_cu, s, what);
+    return launch_fused_winn<64, 1, 16, PF, LE, MODE>(call, blocks_per_cu);
     FEDAVG_WINNLE_CASE(8, 0, 1)
     FEDAVG_WINNLE_CASE(8, 0, 2)
     FEDAVG_WINNLE_CASE(8, 0, 3)
@@ -2632,8 +2501,7 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     // (reduce_sqdist_winf_kernel): 91000000 + MODE * 10000 + PF * 100 + NSMAX
 #define FEDAVG_WINF_CASE(NSMAX, PF, MODE)                                                                        \
   case 91000000 + MODE * 10000 + PF * 100 + NSMAX:                                                              \
-    return launch_fused_winf<NSMAX, PF, MODE>(clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, s, \
-                                              what);
+    return launch_fused_winf<NSMAX, PF, MODE>(call);
     FEDAVG_WINF_CASE(16, 8, 0)
     FEDAVG_WINF_CASE(16, 16, 0)
     FEDAVG_WINF_CASE(16, 8, 8)

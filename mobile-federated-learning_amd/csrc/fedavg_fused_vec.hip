@@ -320,30 +320,21 @@ const PlanEntry* vec_band(int64_t K, int64_t P, int64_t elem_size) {
   return elem_size == 8 ? vec_band_of<kVecBands64>(K) : (elem_size == 2 ? vec_band_of<kVecBands16>(K) : nullptr);
 }
 
-// waves (= partials per row) of an instance's launch
-int64_t vec_waves(int64_t P, int elem_size, int kmax, int sb) {
-  const int64_t nwin = (P * elem_size + 64 * sb - 1) / (64 * sb);
-  const int64_t need = (nwin + kVecNW - 1) / kVecNW;
-  const int64_t grid = kVecCUs * fv_min_waves(kmax, sb);
-  return (grid < need ? grid : need) * kVecNW;
-}
+// this library's error state behind the shared launch step (window.hpp)
+const LaunchCtx kVecLaunch{fv_error, fv_launch_status, "%s: workspace needs %lld doubles",
+                           reinterpret_cast<const void*>(fusedvec_finalize_kernel)};
 
 template <class T, int KMAX, int SB>
 int launch_vecwin(const void* clients, int64_t K, int64_t P, int64_t ld, const void* weights, void* out,
                   double* workspace, int64_t workspace_elems, double* sumsq, hipStream_t s, const char* what) {
   constexpr int ES = sizeof(typename T::elem);
-  const int64_t waves = vec_waves(P, ES, KMAX, SB);
-  if (workspace_elems < K * waves)
-    return fv_error(FEDAVG_EINVAL, "%s: workspace needs %lld doubles", what, (long long)(K * waves));
   const int64_t nwin = (P * ES + 64 * SB - 1) / (64 * SB);
-  hipLaunchKernelGGL((reduce_sqdist_vecwin_kernel<T, KMAX, SB, kVecNW>), dim3(static_cast<unsigned>(waves / kVecNW)),
-                     dim3(64 * kVecNW), 0, s, static_cast<const char*>(clients), static_cast<int>(K), ld * ES, P, nwin,
-                     static_cast<const typename T::wt*>(weights), static_cast<typename T::elem*>(out), workspace);
-  const int rc = fv_launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(fusedvec_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, workspace, waves,
-                     sumsq);
-  return fv_launch_status(what);
+  const int64_t waves = window_waves(fv_min_waves(KMAX, SB), kVecCUs, nwin, kVecNW);  // = partials per row
+  return launch_and_finalize(kVecLaunch, what, K, waves, 0, workspace, workspace_elems, sumsq, s, [&] {
+    hipLaunchKernelGGL((reduce_sqdist_vecwin_kernel<T, KMAX, SB, kVecNW>), dim3(static_cast<unsigned>(waves / kVecNW)),
+                       dim3(64 * kVecNW), 0, s, static_cast<const char*>(clients), static_cast<int>(K), ld * ES, P, nwin,
+                       static_cast<const typename T::wt*>(weights), static_cast<typename T::elem*>(out), workspace);
+  });
 }
 
 // the product library's message behind a failing call of the two-pass route

@@ -1171,25 +1171,6 @@ inline bool seg_split_stamps() {
   return on;
 }
 
-// workgroups of the split-row window launch over `units` windows (0: not resident)
-inline int64_t segwinn_blocks(int64_t K, int64_t units) {
-  const int ns = static_cast<int>((K + 63) / 64);
-  int64_t res = 0;
-  for_split(ns, [&](auto nsmax, auto pf) {
-    res = resident_blocks(reduce_sqdist_segwinf_kernel<decltype(nsmax)::value, decltype(pf)::value>, 64 * ns);
-  });
-  // workgroups per CU: the resident ones rounded down to a power of two, as
-  // the rows kernel's grid (split_per_cu; round 6, resnet18_gn-shaped rounds,
-  // profiles/r06/zc_percu/, ms: 257 clients 3 per CU 2.70 vs 2 2.32; 300 2.83
-  // vs 2.47; 129 clients 5 per CU 1.53 vs 4 1.47; 500 equal); the probe
-  // library's FEDAVG_SEGWINN_PER_CU caps it instead
-  static const int64_t per_cu_knob = tuning_knob("FEDAVG_SEGWINN_PER_CU", 0);
-  const int64_t cus = cu_count();
-  const int64_t per_cu = per_cu_knob > 0 ? per_cu_knob : split_per_cu(res);
-  if (per_cu > 0 && per_cu * cus < res) res = per_cu * cus;
-  return units < res ? units : res;
-}
-
 // windows per wave below which the LDS-DMA tiles keep the round
 // (kSegWinMinPerWave; the probe library's FEDAVG_SEGWIN_MIN_PER_WAVE overrides it)
 inline int64_t segwin_min_per_wave() {
@@ -1203,42 +1184,15 @@ inline bool segwin_disabled() {
   return off;
 }
 
-// waves of a zero-copy window launch over `units` windows
-template <int KMAX, int VEC, int NW, bool DESC = true>
-int64_t segwin_waves(int64_t units) {
-  const int64_t per_cu = resident_blocks(reduce_sqdist_segwin_kernel<KMAX, VEC, NW, DESC>, 64 * NW) / cu_count();
-  const int64_t grid = per_cu * cu_count();
-  const int64_t need = (units + NW - 1) / NW;
-  return (grid < need ? grid : need) * NW;
-}
-
-// the window instance for K clients (0 outside 17..128).  Round 3 ran 81-100
-// clients on the 128 x 1 instance because its 100 x 2 form spilled (device
-// round 100 x 25M 3.66 ms, profiles/r03/segwin/); the spill was the slow
-// path's per-lane 64-bit element addresses, gone with the buffer-load form
-// (232 VGPRs, no scratch), so 81-100 clients take 100 x 2 as on rows
-inline int segwin_kmax(int64_t K) {
-  const PlanEntry* band = win_band_of(K);
-  return band ? band->a : 0;
-}
-inline int segwin_vec(int kmax) {  // 0: no such band
-  int v = 0;
-  for_win_band(kmax, [&](auto, auto vec) { v = decltype(vec)::value; });
-  return v;
-}
-
-inline int64_t segwin_waves_for(int kmax, int64_t units) {  // 0: no such band
-  int64_t waves = 0;
-  for_win_band(kmax, [&](auto km, auto vec) {
-    waves = segwin_waves<decltype(km)::value, decltype(vec)::value, 4>(units);
-  });
-  return waves;
-}
-
+// Round 3 ran 81-100 clients on the 128 x 1 window instance because its
+// 100 x 2 form spilled (device round 100 x 25M 3.66 ms, profiles/r03/segwin/);
+// the spill was the slow path's per-lane 64-bit element addresses, gone with
+// the buffer-load form (232 VGPRs, no scratch), so 81-100 clients take 100 x 2
+// as on rows (kWinBands, window.hpp)
 constexpr int kSegFusedMaxK = kBlock;
 
-// tile width: as fedavg_dist.hip's fused_cols (32 above 128 clients, 64 above
-// 64, 128 up to 64, 256 up to 16); every width keeps <= 8 load slots per thread
+// tile width by clients (32 above 128, 64 above 64, 128 up to 64, 256 up to
+// 16): every width keeps <= 8 load slots per thread
 inline int seg_fused_cols(int64_t K) { return K > 128 ? 32 : (K > 64 ? 64 : (K > 16 ? 128 : 256)); }
 
 inline int64_t seg_fused_lds_bytes(int64_t K, int S, bool laddr = false) {
@@ -1250,52 +1204,12 @@ inline int64_t seg_fused_lds_bytes(int64_t K, int S, bool laddr = false) {
 // client addresses in registers) without a unit map, MAP = true (unit map,
 // client addresses in LDS) with one
 template <int S, bool MAP>
-int seg_fused_per_cu(int64_t K) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int64_t>, int> cache;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find({dev, K});
-  if (it != cache.end()) return it->second;
-  const auto kern = reduce_sqdist_segments_f32_kernel<S, MAP, MAP>;
-  const int64_t lds = seg_fused_lds_bytes(K, S, MAP);
-  int per_cu = 0;
-  if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-  } else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, static_cast<size_t>(lds)) !=
-             hipSuccess) {
-    (void)hipGetLastError();
-    per_cu = 0;
-  }
-  cache[{dev, K}] = per_cu;
-  return per_cu;
-}
-
-template <int S, bool MAP>
-int64_t seg_fused_grid(int64_t K, int64_t units) {
-  const int64_t g = static_cast<int64_t>(seg_fused_per_cu<S, MAP>(K)) * cu_count();
-  return units < g ? units : g;
+int seg_fused_per_cu(int64_t K) {  // 0: the tile does not fit LDS
+  return lds_blocks_per_cu(reduce_sqdist_segments_f32_kernel<S, MAP, MAP>, kBlock, seg_fused_lds_bytes(K, S, MAP));
 }
 
 // the tile widths of seg_fused_cols; f(S)
 constexpr PlanEntry kSegTiles[] = {{32, 0}, {64, 0}, {128, 0}, {256, 0}};
-template <class F>
-bool for_seg_tile(int S, F&& f) {  // false: no such tile
-  return for_entry<kSegTiles>(S, kAnyB, [&](auto s, auto) { f(s); });
-}
-
-// resident workgroups per CU of either tile kernel form (the partials' bound)
-inline int seg_fused_per_cu_max(int S, int64_t K) {
-  int per_cu = 0;
-  for_seg_tile(S, [&](auto s) {
-    const int a = seg_fused_per_cu<decltype(s)::value, false>(K), b = seg_fused_per_cu<decltype(s)::value, true>(K);
-    per_cu = a > b ? a : b;
-  });
-  return per_cu;
-}
 
 int64_t units_of(const int64_t* numel, int64_t n_keys, int64_t span = kSegSpan) {
   int64_t units = 0;
@@ -1392,38 +1306,161 @@ inline int64_t seg_split_min_k() {
   return v;
 }
 
+const LaunchCtx kSegLaunch{set_error, launch_status, "%s: partials need %lld doubles",
+                           reinterpret_cast<const void*>(segments_finalize_kernel)};
+
+// a fused launch's arguments: the staged tables (umap: the tiles' unit map,
+// desc: the windows' descriptor table, either may be null) and the outputs
+struct SegCall {
+  const SegKey* keys;
+  const int64_t* tptrs;
+  int64_t n_keys, units, K;
+  const float* weights;
+  float* out;
+  double* partials;
+  int64_t partial_elems;
+  double* sumsq;
+  hipStream_t s;
+  const char* what;
+  const int* umap;
+  const u32x4* desc;
+};
+
+template <class Launch>
+int seg_launch(const SegCall& c, int64_t parts, int64_t extra, Launch&& launch) {
+  return launch_and_finalize(kSegLaunch, c.what, c.K, parts, extra, c.partials, c.partial_elems, c.sumsq, c.s, launch);
+}
+
+// The instance a plan names, as a tag: parts(K, units) = the partials' second
+// dimension of its launch over `units` units; launch(plan, call).
+template <int NSMAX, int PF>
+struct SegSplitInstance {  // split-row windows: workgroups of ceil(K / 64) waves (0: not resident)
+  static int64_t parts(int64_t K, int64_t units) {
+    const int ns = static_cast<int>((K + 63) / 64);
+    const int64_t res = resident_blocks(reduce_sqdist_segwinf_kernel<NSMAX, PF>, 64 * ns);
+    // workgroups per CU: the resident ones rounded down to a power of two, as
+    // the rows kernel's grid (split_per_cu; round 6, resnet18_gn-shaped rounds,
+    // profiles/r06/zc_percu/, ms: 257 clients 3 per CU 2.70 vs 2 2.32; 300 2.83
+    // vs 2.47; 129 clients 5 per CU 1.53 vs 4 1.47; 500 equal); the probe
+    // library's FEDAVG_SEGWINN_PER_CU caps it instead
+    static const int64_t per_cu_knob = tuning_knob("FEDAVG_SEGWINN_PER_CU", 0);
+    const int64_t cus = cu_count();
+    return persistent_grid(per_cu_knob > 0 ? std::min(per_cu_knob, res / cus) : split_per_cu(res), cus, units);
+  }
+  static int launch(const SegFusedPlan& p, const SegCall& c) {
+    if (p.waves <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", c.what);
+    if (c.K < 2) return set_error(FEDAVG_EMODE, "%s: the split windows take K >= 2", c.what);
+    const dim3 grid(static_cast<unsigned>(p.waves)), block(static_cast<unsigned>(64 * ((c.K + 63) / 64)));
+    const int k32 = static_cast<int>(c.K);
+    const bool stamps = seg_split_stamps();  // the timeline build: MODE 8, the partials grow by the stamps
+    return seg_launch(c, p.waves, stamps ? winn_stamp_elems(16) : 0, [&] {
+#ifdef FEDAVG_TUNING
+      if (stamps) {
+        hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<NSMAX, PF, true, 8>), grid, block, 0, c.s, c.keys, c.tptrs,
+                           c.n_keys, c.units, k32, c.weights, c.out, c.partials);
+        return;
+      }
+#endif
+      hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<NSMAX, PF>), grid, block, 0, c.s, c.keys, c.tptrs, c.n_keys,
+                         c.units, k32, c.weights, c.out, c.partials);
+    });
+  }
+};
+template <int KMAX, int VEC>
+struct SegWinInstance {  // one-wave windows, 4 waves per workgroup: waves
+  static int64_t parts(int64_t, int64_t units) {
+    return window_waves(resident_blocks(reduce_sqdist_segwin_kernel<KMAX, VEC, 4, true>, 256) / cu_count(), cu_count(),
+                        units, 4);
+  }
+  static int launch(const SegFusedPlan& p, const SegCall& c) {
+    const dim3 grid(static_cast<unsigned>(p.waves / 4)), block(256);
+    const int k32 = static_cast<int>(c.K);
+    return seg_launch(c, p.waves, 0, [&] {
+      if (c.desc)
+        hipLaunchKernelGGL((reduce_sqdist_segwin_kernel<KMAX, VEC, 4, true>), grid, block, 0, c.s, c.keys, c.tptrs,
+                           c.n_keys, c.units, k32, c.weights, c.out, c.partials, c.desc);
+      else
+        hipLaunchKernelGGL((reduce_sqdist_segwin_kernel<KMAX, VEC, 4, false>), grid, block, 0, c.s, c.keys, c.tptrs,
+                           c.n_keys, c.units, k32, c.weights, c.out, c.partials, nullptr);
+    });
+  }
+};
+template <int S>
+struct SegTileInstance {  // LDS-DMA tiles; the form (MAP) by whether the round staged a unit map
+  // the bound over both forms, never less than one workgroup per CU (the launch's own: below)
+  static int64_t parts(int64_t K, int64_t units) {
+    const int per_cu = std::max(seg_fused_per_cu<S, false>(K), seg_fused_per_cu<S, true>(K));
+    return persistent_grid(per_cu > 0 ? per_cu : 1, cu_count(), units);
+  }
+  static int launch(const SegFusedPlan&, const SegCall& c) {
+    const auto go = [&](auto map) {
+      constexpr bool MAP = decltype(map)::value;
+      const int per_cu = seg_fused_per_cu<S, MAP>(c.K);
+      if (per_cu <= 0) return set_error(FEDAVG_EMODE, "%s: tile does not fit LDS", c.what);
+      const int64_t nparts = persistent_grid(per_cu, cu_count(), c.units);
+      return seg_launch(c, nparts, 0, [&] {
+        hipLaunchKernelGGL((reduce_sqdist_segments_f32_kernel<S, MAP, MAP>), dim3(static_cast<unsigned>(nparts)),
+                           dim3(kBlock), static_cast<unsigned>(seg_fused_lds_bytes(c.K, S, MAP)), c.s, c.keys, c.tptrs,
+                           c.n_keys, c.units, static_cast<int>(c.K), c.weights, c.out, c.partials, c.umap);
+      });
+    };
+    return c.umap != nullptr ? go(std::true_type{}) : go(std::false_type{});
+  }
+};
+
+// f(instance tag) for the instance plan `p` names at K clients (kmax < 0: the
+// split-row windows; win: the window band kmax; else the tile of `span`
+// columns); false: it names none.  The only walk over the zero-copy forms:
+// the plan's waves, the partials' bound and the launch come through here.
+template <class F>
+bool with_seg_instance(const SegFusedPlan& p, int64_t K, F&& f) {
+  if (p.win && p.kmax < 0)
+    return for_split(static_cast<int>((K + 63) / 64), [&](auto nsmax, auto pf) {
+      f(SegSplitInstance<decltype(nsmax)::value, decltype(pf)::value>{});
+    });
+  if (p.win)
+    return for_win_band(p.kmax, [&](auto kmax, auto vec) {
+      f(SegWinInstance<decltype(kmax)::value, decltype(vec)::value>{});
+    });
+  return for_entry<kSegTiles>(static_cast<int>(p.span), kAnyB,
+                              [&](auto s, auto) { f(SegTileInstance<decltype(s)::value>{}); });
+}
+
+inline int64_t seg_parts(const SegFusedPlan& p, int64_t K, int64_t units) {  // 0: no instance, or not resident
+  int64_t n = 0;
+  with_seg_instance(p, K, [&](auto inst) { n = decltype(inst)::parts(K, units); });
+  return n;
+}
+
 SegFusedPlan seg_fused_plan(const int64_t* numel, int64_t n_keys, int64_t K, bool all_raw) {
-  SegFusedPlan p{false, segwin_kmax(K), seg_fused_cols(K), 0};
+  const PlanEntry* band = win_band_of(K);  // {KMAX, VEC}, nullptr outside 17..128
+  SegFusedPlan p{false, band ? band->a : 0, seg_fused_cols(K), 0};
+  const SegFusedPlan split{true, -1, 64, 0};  // kmax -1: the split-row windows
   if (K >= seg_split_min_k() && K >= 2 && K <= kSegFusedMaxK && all_raw && seg_split_ok(numel, n_keys)) {
     const int64_t units = units_of(numel, n_keys, 64);
-    const int64_t blocks = segwinn_blocks(K, units);
+    const int64_t blocks = seg_parts(split, K, units);
     if (blocks > 0 && units >= kSegSplitMinPerBlock * blocks) {
-      p.win = true;
-      p.kmax = -1;
-      p.span = 64;
+      p = split;
       p.waves = blocks;
       return p;
     }
   }
-  if (K > kSegFusedMaxK) {  // kmax -1: the split-row windows (the caller checked seg_split_ok)
+  if (K > kSegFusedMaxK) {
     if (K <= kSegSplitMaxK && all_raw && seg_split_ok(numel, n_keys)) {
-      p.win = true;
-      p.kmax = -1;
-      p.span = 64;
-      p.waves = segwinn_blocks(K, units_of(numel, n_keys, 64));
+      p = split;
+      p.waves = seg_parts(split, K, units_of(numel, n_keys, 64));
     }
     return p;
   }
   // the windows address a key's bytes with 32-bit buffer offsets
   bool small_keys = numel != nullptr;
   for (int64_t j = 0; small_keys && j < n_keys; ++j) small_keys = numel[j] < (int64_t(1) << 30);
-  if (p.kmax > 0 && all_raw && small_keys && n_keys > 0 && n_keys < (int64_t(1) << 31) && !segwin_disabled()) {
-    const int64_t wc = 64 * segwin_vec(p.kmax);
-    const int64_t wunits = units_of(numel, n_keys, wc);
-    const int64_t waves = segwin_waves_for(p.kmax, wunits);
+  if (band && all_raw && small_keys && n_keys > 0 && n_keys < (int64_t(1) << 31) && !segwin_disabled()) {
+    const SegFusedPlan win{true, band->a, 64 * band->b, 0};
+    const int64_t wunits = units_of(numel, n_keys, win.span);
+    const int64_t waves = seg_parts(win, K, wunits);
     if (waves > 0 && wunits >= segwin_min_per_wave() * waves && wunits < (int64_t(1) << 31)) {
-      p.win = true;
-      p.span = wc;
+      p = win;
       p.waves = waves;
     }
   }
@@ -1431,88 +1468,19 @@ SegFusedPlan seg_fused_plan(const int64_t* numel, int64_t n_keys, int64_t K, boo
 }
 
 // The fused launch (+ the sums' finalize) on tables staged with plan.span
-int launch_seg_fused(const SegFusedPlan& p, const SegKey* keys, const int64_t* tptrs, int64_t n_keys, int64_t units,
-                     int64_t K, const float* weights, float* out, double* partials, int64_t partial_elems,
-                     double* sumsq, hipStream_t s, const char* what, const int* umap = nullptr,
-                     const u32x4* desc = nullptr) {
-  if (units == 0) {
-    const hipError_t e = hipMemsetAsync(sumsq, 0, static_cast<size_t>(K) * sizeof(double), s);
-    return e == hipSuccess ? FEDAVG_OK : set_error(-static_cast<int>(e), "%s: hipMemsetAsync failed", what);
+int launch_seg_fused(const SegFusedPlan& p, const SegCall& c) {
+  if (c.units == 0) {
+    const hipError_t e = hipMemsetAsync(c.sumsq, 0, static_cast<size_t>(c.K) * sizeof(double), c.s);
+    return e == hipSuccess ? FEDAVG_OK : set_error(-static_cast<int>(e), "%s: hipMemsetAsync failed", c.what);
   }
   // beyond kSegFusedMaxK clients only the split-row windows fuse: the tile
   // kernel loads at most kBlock client addresses per workgroup
-  if (K > kSegFusedMaxK && !(p.win && p.kmax < 0))
-    return set_error(FEDAVG_EMODE, "%s: K = %lld fuses only on the split-row windows", what, (long long)K);
-  const int k32 = static_cast<int>(K);
-  int64_t nparts = 0;
-  if (p.win && p.kmax < 0) {  // split-row windows: p.waves workgroups of ceil(K / 64) waves
-    if (p.waves <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", what);
-    if (partial_elems < K * p.waves)
-      return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)(K * p.waves));
-    const int ns = static_cast<int>((K + 63) / 64);
-    const dim3 grid(static_cast<unsigned>(p.waves)), block(static_cast<unsigned>(64 * ns));
-    if (K < 2)
-      return set_error(FEDAVG_EMODE, "%s: the split windows take K >= 2", what);
-#ifdef FEDAVG_TUNING  // the timeline build: MODE 8, the partials grow by the stamps
-    const bool stamps = seg_split_stamps();
-    if (stamps && partial_elems < K * p.waves + winn_stamp_elems(16))
-      return set_error(FEDAVG_EINVAL, "%s: the timeline needs %lld more doubles", what, (long long)winn_stamp_elems(16));
-#endif
-    const bool found = for_split(ns, [&](auto nsmax, auto pf) {
-      constexpr int NSMAX = decltype(nsmax)::value, PF = decltype(pf)::value;
-#ifdef FEDAVG_TUNING
-      if (stamps) {
-        hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<NSMAX, PF, true, 8>), grid, block, 0, s, keys, tptrs, n_keys,
-                           units, k32, weights, out, partials);
-        return;
-      }
-#endif
-      hipLaunchKernelGGL((reduce_sqdist_segwinf_kernel<NSMAX, PF>), grid, block, 0, s, keys, tptrs, n_keys, units, k32,
-                         weights, out, partials);
-    });
-    if (!found) return set_error(FEDAVG_EMODE, "%s: no split window form for %d waves", what, ns);
-    nparts = p.waves;
-  } else if (p.win) {
-    if (partial_elems < K * p.waves)
-      return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)(K * p.waves));
-    const dim3 grid(static_cast<unsigned>(p.waves / 4)), block(256);
-    const bool found = for_win_band(p.kmax, [&](auto kmax, auto vec) {
-      constexpr int KMAX = decltype(kmax)::value, VEC = decltype(vec)::value;
-      if (desc)
-        hipLaunchKernelGGL((reduce_sqdist_segwin_kernel<KMAX, VEC, 4, true>), grid, block, 0, s, keys, tptrs, n_keys,
-                           units, k32, weights, out, partials, desc);
-      else
-        hipLaunchKernelGGL((reduce_sqdist_segwin_kernel<KMAX, VEC, 4, false>), grid, block, 0, s, keys, tptrs, n_keys,
-                           units, k32, weights, out, partials, nullptr);
-    });
-    if (!found) return set_error(FEDAVG_EMODE, "%s: no window instance for KMAX %d", what, p.kmax);
-    nparts = p.waves;
-  } else {
-    const int S = static_cast<int>(p.span);
-    int rc = FEDAVG_OK;
-    const bool found = for_seg_tile(S, [&](auto cols) {
-      constexpr int C = decltype(cols)::value;
-      const auto launch = [&](auto map) {
-        constexpr bool MAP = decltype(map)::value;
-        if (seg_fused_per_cu<C, MAP>(K) <= 0) return set_error(FEDAVG_EMODE, "%s: tile does not fit LDS", what);
-        nparts = seg_fused_grid<C, MAP>(K, units);
-        if (partial_elems < K * nparts)
-          return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)(K * nparts));
-        hipLaunchKernelGGL((reduce_sqdist_segments_f32_kernel<C, MAP, MAP>), dim3(static_cast<unsigned>(nparts)),
-                           dim3(kBlock), static_cast<unsigned>(seg_fused_lds_bytes(K, C, MAP)), s, keys, tptrs, n_keys,
-                           units, k32, weights, out, partials, umap);
-        return static_cast<int>(FEDAVG_OK);
-      };
-      rc = umap != nullptr ? launch(std::true_type{}) : launch(std::false_type{});
-    });
-    if (!found) return set_error(FEDAVG_EMODE, "%s: no tile instance of %d columns", what, S);
-    if (rc) return rc;
-  }
-  int rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(segments_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, partials, nparts,
-                     sumsq);
-  return launch_status(what);
+  if (c.K > kSegFusedMaxK && !(p.win && p.kmax < 0))
+    return set_error(FEDAVG_EMODE, "%s: K = %lld fuses only on the split-row windows", c.what, (long long)c.K);
+  int rc = FEDAVG_OK;
+  if (!with_seg_instance(p, c.K, [&](auto inst) { rc = decltype(inst)::launch(p, c); }))
+    return set_error(FEDAVG_EMODE, "%s: plan %d / %lld names no kernel instance", c.what, p.kmax, (long long)p.span);
+  return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -1634,17 +1602,14 @@ int fedavg_client_sqdist_segments_f32(const int64_t* client_ptrs, const int64_t*
   const auto* ptrs = reinterpret_cast<const int64_t*>(static_cast<const char*>(dev_ws) +
                                                       n_keys * static_cast<int64_t>(sizeof(SegKey)));
   const int64_t nparts = units * (kBlock / 64);
-  if (small)
-    hipLaunchKernelGGL((sqdist_segments_f32_kernel<kSegDistU, kSegSmallC>), dim3(static_cast<unsigned>(units)),
-                       dim3(kBlock), 0, s, keys, ptrs, n_keys, int64_t(0), static_cast<int>(K), glob, partials, nparts);
-  else
-    hipLaunchKernelGGL((sqdist_segments_f32_kernel<kSegDistU, kSegDistC>), dim3(static_cast<unsigned>(units)),
-                       dim3(kBlock), 0, s, keys, ptrs, n_keys, int64_t(0), static_cast<int>(K), glob, partials, nparts);
-  int rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(segments_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, partials, nparts,
-                     sumsq);
-  return launch_status(what);
+  return launch_and_finalize(kSegLaunch, what, K, nparts, 0, partials, partial_elems, sumsq, s, [&] {
+    if (small)
+      hipLaunchKernelGGL((sqdist_segments_f32_kernel<kSegDistU, kSegSmallC>), dim3(static_cast<unsigned>(units)),
+                         dim3(kBlock), 0, s, keys, ptrs, n_keys, int64_t(0), static_cast<int>(K), glob, partials, nparts);
+    else
+      hipLaunchKernelGGL((sqdist_segments_f32_kernel<kSegDistU, kSegDistC>), dim3(static_cast<unsigned>(units)),
+                         dim3(kBlock), 0, s, keys, ptrs, n_keys, int64_t(0), static_cast<int>(K), glob, partials, nparts);
+  });
 }
 
 // Aggregate + :291 sums in one pass over device-resident clients (K <= 256,
@@ -1653,15 +1618,15 @@ int fedavg_client_sqdist_segments_f32(const int64_t* client_ptrs, const int64_t*
 // that out.  partials : fedavg_reduce_sqdist_segments_partials(K) doubles.
 int64_t fedavg_reduce_sqdist_segments_partials(int64_t K) {
   if (K <= 0 || K > kSegSplitMaxK) return 0;
-  if (K > kSegFusedMaxK)  // the split-row windows (device round)
-    return K * segwinn_blocks(K, INT64_MAX / 2) + (seg_split_stamps() ? winn_stamp_elems(16) : 0);
-  const int S = seg_fused_cols(K);
-  const int per_cu = seg_fused_per_cu_max(S, K);
-  const int64_t tiles = K * static_cast<int64_t>(per_cu > 0 ? per_cu : 1) * cu_count();
-  const int64_t windows = K * segwin_waves_for(segwin_kmax(K), INT64_MAX / 2);  // a full window launch
-  const int64_t split = K >= seg_split_min_k() ? K * segwinn_blocks(K, INT64_MAX / 2) : 0;  // 129-256: split windows
-  const int64_t need = tiles > windows ? tiles : windows;
-  return (need > split ? need : split) + (seg_split_stamps() ? winn_stamp_elems(16) : 0);
+  const int64_t full = INT64_MAX / 2;  // units of a launch that fills the chip
+  const int64_t stamps = seg_split_stamps() ? winn_stamp_elems(16) : 0;
+  const int64_t split = seg_parts({true, -1, 64, 0}, K, full);
+  if (K > kSegFusedMaxK) return K * split + stamps;  // the split-row windows (device round)
+  const PlanEntry* band = win_band_of(K);
+  const int64_t tiles = seg_parts({false, 0, seg_fused_cols(K), 0}, K, full);
+  const int64_t windows = band ? seg_parts({true, band->a, 64 * band->b, 0}, K, full) : 0;
+  const int64_t need = std::max(std::max(tiles, windows), K >= seg_split_min_k() ? split : 0);  // 129-256: split windows
+  return K * need + stamps;
 }
 
 int fedavg_reduce_sqdist_segments_f32(const int64_t* client_ptrs, const int64_t* key_numel, const int64_t* key_offset,
@@ -1693,7 +1658,8 @@ int fedavg_reduce_sqdist_segments_f32(const int64_t* client_ptrs, const int64_t*
   const auto* keys = static_cast<const SegKey*>(dev_ws);
   const auto* tptrs = reinterpret_cast<const int64_t*>(static_cast<const char*>(dev_ws) +
                                                        n_keys * static_cast<int64_t>(sizeof(SegKey)));
-  return launch_seg_fused(plan, keys, tptrs, n_keys, units, K, weights, out, partials, partial_elems, sumsq, s, what);
+  return launch_seg_fused(plan, SegCall{keys, tptrs, n_keys, units, K, weights, out, partials, partial_elems, sumsq, s,
+                                        what, nullptr, nullptr});
 }
 
 int64_t fedavg_device_round_workspace(int64_t K, int64_t n_keys) {
@@ -1831,9 +1797,9 @@ int fedavg_device_round_f32(const int64_t* client_ptrs, int64_t ptr_ld, const in
   }
   FEDAVG_ROUND_MARK(7);  // the integer keys' launch
   if (fuse) {
-    rc = launch_seg_fused(plan, keys, tptrs, n_keys, units, K, dw, out, partials, partial_elems, sumsq, s, what,
-                          with_map ? reinterpret_cast<const int*>(db + moff) : nullptr,
-                          with_desc ? reinterpret_cast<const u32x4*>(db + moff) : nullptr);
+    rc = launch_seg_fused(plan, SegCall{keys, tptrs, n_keys, units, K, dw, out, partials, partial_elems, sumsq, s, what,
+                                        with_map ? reinterpret_cast<const int*>(db + moff) : nullptr,
+                                        with_desc ? reinterpret_cast<const u32x4*>(db + moff) : nullptr});
     FEDAVG_ROUND_MARK(8);  // the fused launch and the sums' finalize
     return rc ? rc : FEDAVG_OK;
   }
@@ -1877,29 +1843,26 @@ int fedavg_client_sqdist_segments_f32_variant(const int64_t* client_ptrs, const 
   const int64_t nparts = units * (kBlock / 64);
   const dim3 grid(static_cast<unsigned>(units));
   const int k = static_cast<int>(K);
-  switch (uc) {
+  return launch_and_finalize(kSegLaunch, what, K, nparts, 0, partials, partial_elems, sumsq, s, [&] {
+    switch (uc) {
 #define FEDAVG_SQSEG_CASE(U, C)                                                                                      \
-  case U * 100 + C:                                                                                                  \
-    hipLaunchKernelGGL((sqdist_segments_f32_kernel<U, C>), grid, dim3(kBlock), 0, s, keys, ptrs, n_keys, int64_t(0), \
-                       k, glob, partials, nparts);                                                                   \
-    break;
-    FEDAVG_SQSEG_CASE(1, 4)
-    FEDAVG_SQSEG_CASE(2, 4)
-    FEDAVG_SQSEG_CASE(4, 4)
-    FEDAVG_SQSEG_CASE(8, 4)
-    FEDAVG_SQSEG_CASE(4, 1)
-    FEDAVG_SQSEG_CASE(8, 1)
-    FEDAVG_SQSEG_CASE(4, 2)
-    FEDAVG_SQSEG_CASE(8, 2)
-    FEDAVG_SQSEG_CASE(2, 8)
-    FEDAVG_SQSEG_CASE(4, 8)
+    case U * 100 + C:                                                                                                  \
+      hipLaunchKernelGGL((sqdist_segments_f32_kernel<U, C>), grid, dim3(kBlock), 0, s, keys, ptrs, n_keys, int64_t(0), \
+                         k, glob, partials, nparts);                                                                   \
+      break;
+      FEDAVG_SQSEG_CASE(1, 4)
+      FEDAVG_SQSEG_CASE(2, 4)
+      FEDAVG_SQSEG_CASE(4, 4)
+      FEDAVG_SQSEG_CASE(8, 4)
+      FEDAVG_SQSEG_CASE(4, 1)
+      FEDAVG_SQSEG_CASE(8, 1)
+      FEDAVG_SQSEG_CASE(4, 2)
+      FEDAVG_SQSEG_CASE(8, 2)
+      FEDAVG_SQSEG_CASE(2, 8)
+      FEDAVG_SQSEG_CASE(4, 8)
 #undef FEDAVG_SQSEG_CASE
-  }
-  int rc = launch_status(what);
-  if (rc) return rc;
-  hipLaunchKernelGGL(segments_finalize_kernel, dim3(static_cast<unsigned>(K)), dim3(kBlock), 0, s, partials, nparts,
-                     sumsq);
-  return launch_status(what);
+    }
+  });
 }
 #endif  // FEDAVG_TUNING
 

@@ -2,7 +2,8 @@
 // fedavg_segments.hip (zero-copy, device-resident clients) share: the
 // register-window helpers, the row-sum folds, the hand-off protocol's wait /
 // publish / weights, and the one-wave band table with the plan dispatch
-// helpers (host).
+// helpers (host); and, for every fused launcher (fedavg_fused_vec.hip's too),
+// the grid rule and the launch-and-finalize step (host).
 // Everything about where a row comes from stays with the kernels.
 #pragma once
 
@@ -212,6 +213,55 @@ inline int64_t split_per_cu(int64_t resident) {
   if (r >= 1)
     for (per_cu = 1; per_cu * 2 <= r;) per_cu *= 2;
   return per_cu;
+}
+
+// ---------------------------------------------------------------------------
+// The grid rule and the launch step of every fused aggregate + :291 launcher
+// (host).  The CU count is an argument: fedavg_fused_vec.hip sizes its grids
+// for a constant chip and answers without a device.
+// ---------------------------------------------------------------------------
+// workgroups of a persistent launch: every resident one, or one per work item
+// when there are fewer
+inline int64_t persistent_grid(int64_t per_cu, int64_t cus, int64_t items) {
+  const int64_t g = per_cu * cus;
+  return items < g ? items : g;
+}
+// waves of a window launch of NW-wave workgroups: a workgroup per NW windows
+inline int64_t window_waves(int64_t per_cu, int64_t cus, int64_t windows, int nw) {
+  return persistent_grid(per_cu, cus, (windows + nw - 1) / nw) * nw;
+}
+
+// What a translation unit's launches share: its library's error state, the
+// wording of its "too small" refusal (what, doubles needed) and the kernel
+// that sums partials[K][parts] into sumsq[K]
+struct LaunchCtx {
+  int (*error)(int code, const char* fmt, ...);
+  int (*status)(const char* what);
+  const char* too_small;
+  const void* finalize;  // __global__ void(const double* partials, int64_t parts, double* sumsq), kBlock threads
+};
+
+// The one launch path: refuse partials of fewer than K x parts + extra
+// doubles, issue the main launch (`launch`: void, or an int status that ends
+// the call when non-zero), check it, sum the partials (unless `finalize` is
+// false: probe modes whose partials are not sums), check that.
+template <class Launch>
+int launch_and_finalize(const LaunchCtx& cx, const char* what, int64_t K, int64_t parts, int64_t extra,
+                        double* partials, int64_t partial_elems, double* sumsq, hipStream_t s, Launch&& launch,
+                        bool finalize = true) {
+  const int64_t need = K * parts + extra;
+  if (partial_elems < need) return cx.error(FEDAVG_EINVAL, cx.too_small, what, (long long)need);
+  if constexpr (std::is_void_v<decltype(launch())>) {
+    launch();
+  } else if (const int rc = launch()) {
+    return rc;
+  }
+  const int rc = cx.status(what);
+  if (rc || !finalize) return rc;
+  const double* sums_of = partials;
+  void* args[] = {&sums_of, &parts, &sumsq};
+  (void)hipLaunchKernel(cx.finalize, dim3(static_cast<unsigned>(K)), dim3(kBlock), args, 0, s);
+  return cx.status(what);
 }
 
 }  // namespace fedavg_impl
