@@ -9,7 +9,7 @@ import ctypes
 import threading
 from pathlib import Path
 
-from .build import FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH
+from .build import FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -121,8 +121,22 @@ FUSEDVEC_SIGNATURES = {
     "fedavg_reduce_sqdist_bf16": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp]),
 }
 
+# libfedavg_amd_segvec.so (include/fedavg_amd_segvec.h)
+_SEGVEC_ROUND = (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp])
+SEGVEC_SIGNATURES = {
+    "fedavg_segvec_abi_version": (_c_int, []),
+    "fedavg_segvec_last_error": (ctypes.c_char_p, []),
+    "fedavg_device_round_vec_workspace": (_c_i64, [_c_i64, _c_i64]),
+    "fedavg_device_round_vec_partials": (_c_i64, [_c_i64, _c_i64]),
+    "fedavg_device_round_vec_plan_of": (_c_i64, [_c_i64, _c_i64, _c_int]),
+    "fedavg_device_round_f64": _SEGVEC_ROUND,
+    "fedavg_device_round_f16": _SEGVEC_ROUND,
+    "fedavg_device_round_bf16": _SEGVEC_ROUND,
+}
+
 ABI_VERSION = 1
 FUSEDVEC_ABI_VERSION = 1
+SEGVEC_ABI_VERSION = 1
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -144,6 +158,7 @@ _lock = threading.Lock()
 _lib = None
 _probe = None
 _fusedvec = None
+_segvec = None
 
 
 def library_path() -> Path:
@@ -234,6 +249,45 @@ def load_fusedvec() -> ctypes.CDLL:
             raise FedAvgLibraryError(f"ABI version {ver} != expected {FUSEDVEC_ABI_VERSION}; rebuild the library")
         _fusedvec = lib
     return _fusedvec
+
+
+def load_segvec() -> ctypes.CDLL:
+    """The zero-copy device-round library for fp64 / fp16 / bf16 groups
+    (include/fedavg_amd_segvec.h).  It calls no other library.  No fallback:
+    a missing or stale library raises ``FedAvgLibraryError``."""
+    global _segvec
+    if _segvec is not None:
+        return _segvec
+    with _lock:
+        if _segvec is not None:
+            return _segvec
+        if not SEGVEC_LIB_PATH.exists():
+            raise FedAvgLibraryError(
+                f"{SEGVEC_LIB_PATH} not built: run __graft_entry__.build(); there is no fallback for the "
+                "zero-copy device round of fp64 / fp16 / bf16 groups")
+        try:
+            lib = ctypes.CDLL(str(SEGVEC_LIB_PATH))
+        except OSError as e:
+            raise FedAvgLibraryError(f"{SEGVEC_LIB_PATH} does not load: {e}") from e
+        for name, (res, args) in SEGVEC_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise FedAvgLibraryError(f"{SEGVEC_LIB_PATH} does not export {name}") from e
+            fn.restype = res
+            fn.argtypes = args
+        ver = lib.fedavg_segvec_abi_version()
+        if ver != SEGVEC_ABI_VERSION:
+            raise FedAvgLibraryError(f"ABI version {ver} != expected {SEGVEC_ABI_VERSION}; rebuild the library")
+        _segvec = lib
+    return _segvec
+
+
+def check_segvec(rc: int, what: str) -> None:
+    """``check`` for a call into libfedavg_amd_segvec.so (its own message)."""
+    if rc != 0:
+        msg = load_segvec().fedavg_segvec_last_error().decode(errors="replace")
+        raise FedAvgLibraryError(f"{what} failed (rc={rc}): {msg}")
 
 
 def check_fusedvec(rc: int, what: str) -> None:

@@ -346,6 +346,8 @@ class DeviceAggregator:
         self._fast_small = None
         self.fast_rounds = 0  # rounds finished by the one-call native path
         self.arena_rounds = 0  # device rounds whose fp32 rows were the clients' own (client_arena layout)
+        # fp64 / fp16 / bf16 groups of device rounds reduced from the clients' own tensors (no packed rows)
+        self.vec_zero_copy_rounds = 0
         self._warm = False
 
     # A process's first round paid its HIP first-use costs on the round's
@@ -590,6 +592,56 @@ class DeviceAggregator:
         del scratch, partials  # freed in `stream` order, after the launches that read them
         return out_dev, (sumsq if rc == 0 else None)
 
+    _SEGVEC_ENTRY = {torch.float64: "fedavg_device_round_f64", torch.float16: "fedavg_device_round_f16",
+                     torch.bfloat16: "fedavg_device_round_bf16"}
+
+    def _device_round_vec(self, g, ptrs, weights, stream):
+        """An fp64 / fp16 / bf16 group of a device-resident round from the
+        clients' own tensors in ONE native call (libfedavg_amd_segvec.so's
+        fedavg_device_round_{f64,f16,bf16}): the averaged group and the
+        round's :291 sums in one read, no ``[K, ld]`` staging rows.  Returns
+        ``(out, sumsq)``, or None when the library refuses the round -- more
+        clients than its one-wave bands hold, or a source off 16-B alignment
+        (its FEDAVG_EMODE / FEDAVG_EALIGN codes decide, before any launch) --
+        and the caller packs rows as before.  FEDAVG_EMODE depends on K and
+        the dtype alone, so it is remembered per table and K and the call is
+        not made again; alignment is the round's own tensors' and is asked
+        every round."""
+        import numpy as np
+
+        lib = _lib.load_segvec()
+        K, n_cols = ptrs.shape
+        es = torch.empty((), dtype=g.dtype).element_size()
+        _, arrs, (ki_p, numel_p, offset_p, _kind), sizes = self._round_meta(g, n_cols)
+        n = len(arrs[1])
+        per_k = sizes.get(("vec", K))
+        if per_k is False:  # the library answered FEDAVG_EMODE for this K before
+            return None
+        if per_k is None:
+            per_k = sizes[("vec", K)] = (lib.fedavg_device_round_vec_partials(K, es),
+                                         lib.fedavg_device_round_vec_workspace(K, n))
+        n_part, ws_need = per_k
+        dev = self.device
+        if not ptrs.flags.c_contiguous:
+            ptrs = np.ascontiguousarray(ptrs, dtype=np.int64)
+        w64 = np.array(weights, dtype=np.float64)
+        out_dev = torch.empty(g.P, dtype=g.dtype, device=dev)
+        partials = torch.empty(n_part, dtype=torch.float64, device=dev)
+        sumsq = torch.empty(K, dtype=torch.float64, device=dev)
+        host_ws, dev_ws = self._stage_ws(ws_need)
+        entry = self._SEGVEC_ENTRY[g.dtype]
+        rc = getattr(lib, entry)(ptrs.ctypes.data, n_cols, ki_p, numel_p, offset_p, n, K, w64.ctypes.data,
+                                 out_dev.data_ptr(), partials.data_ptr(), n_part, sumsq.data_ptr(),
+                                 host_ws.data_ptr(), dev_ws.data_ptr(), host_ws.numel(), stream.cuda_stream)
+        self._table_ws_done.record(stream)
+        if rc == _lib.FEDAVG_EMODE:
+            sizes[("vec", K)] = False
+        if rc in (_lib.FEDAVG_EALIGN, _lib.FEDAVG_EMODE):
+            return None
+        _lib.check_segvec(rc, entry)
+        del partials  # freed in `stream` order, after the launches that read it
+        return out_dev, sumsq
+
     def _sqdist_segments(self, table: KeyTable, dicts, glob: torch.Tensor) -> torch.Tensor:
         """:291 sums of squares straight from device-resident clients' tensors."""
         lib = _lib.load()
@@ -621,28 +673,32 @@ class DeviceAggregator:
             keep = last["seg_keep0"] = OrderedDict(zip(*keep))
         return keep
 
-    def materialize_rows(self):
-        """The last round's client rows in HBM (``[K, ld]``), packing them on
-        demand after a zero-copy round: client 0 from its original tensors
-        (its dict now holds the average, :449), the others from their dicts.
-        Returns the rows or None when the last round left none."""
+    def materialize_rows(self, dtype: torch.dtype = torch.float32):
+        """The last round's client rows of the ``dtype`` group in HBM
+        (``[K, ld]``), packing them on demand after a zero-copy round: client
+        0 from its original tensors (its dict now holds the average, :449),
+        the others from their dicts.  Returns the rows or None when the last
+        round left none."""
         last = self._last
-        if "seg_keep0" not in last:
-            dev = last.get("dev", {}).get(torch.float32)
-            return None if dev is None else dev[0]
+        dev = last.get("dev", {}).get(dtype)
+        if dev is None:
+            return None
+        if dev[0] is not None or "seg_keep0" not in last:
+            return dev[0]
         refs = last.get("refs")
         dicts = [self._client0_tensors(last)] + [r() for r in refs[1:]] if refs is not None else [None]
         if any(d is None for d in dicts):
             return None
         table, K = last["table"], last["K"]
-        g = table.groups[torch.float32]
-        st = self._staging_for(torch.float32, K, g.ld)
+        g = table.groups[dtype]
+        st = self._staging_for(dtype, K, g.ld)
         ptrs, keep = table.collect(dicts, self.device)
         with torch.cuda.device(self.device):
             self._pack_on_device(table, g, ptrs, 0, st.dev, torch.cuda.current_stream(self.device))
         del keep
-        last["dev"][torch.float32] = (st.dev[:K], last["dev"][torch.float32][1])
-        del last["seg_keep0"]
+        last["dev"][dtype] = (st.dev[:K], dev[1])
+        if all(rows is not None for rows, _ in last["dev"].values()):
+            del last["seg_keep0"]  # every group has its rows: client 0's own tensors are not needed any more
         return st.dev[:K]
 
     @staticmethod
@@ -692,7 +748,9 @@ class DeviceAggregator:
     def _reduce_groups_device(self, table: KeyTable, ptrs, weights, dicts=None) -> "OrderedDict[str, torch.Tensor]":
         """Device-resident clients: the fp32 group reduced straight from the
         clients' tensors (zero-copy: the row reduce on them when they already
-        form the packed layout, else the segments kernel), other groups packed
+        form the packed layout, else the segments kernel), fp64 / fp16 / bf16
+        groups likewise within their one-wave bands (``_device_round_vec``),
+        any other group packed
         in HBM and reduced; the averaged model returned as device tensors on
         the current stream (no host round trip, no synchronization: like the
         reference's torch ops on device tensors)."""
@@ -726,6 +784,13 @@ class DeviceAggregator:
                         self._last.setdefault("sumsq", {})[g.dtype] = sums
                     self._last["dev"][g.dtype] = (None, out_dev)  # no rows: see materialize_rows
                     self._last["segments"] = True
+                elif (g.dtype in self._SEGVEC_ENTRY and self.DEVICE_SEGMENTS and FUSE_DISTANCES and g.P > 0
+                      and (done := self._device_round_vec(g, ptrs, weights, compute)) is not None):
+                    out_dev, sums = done
+                    self._last.setdefault("sumsq", {})[g.dtype] = sums
+                    self._last["dev"][g.dtype] = (None, out_dev)  # no rows: see materialize_rows
+                    self._last["segments"] = True
+                    self.vec_zero_copy_rounds += 1
                 else:
                     st = self._staging_for(g.dtype, K, g.ld)
                     self._pack_on_device(table, g, ptrs, 0, st.dev, compute)
@@ -904,7 +969,8 @@ class DeviceAggregator:
         cached = (refs is not None and last["acc"]() is w_glob and len(refs) == len(w_locals)
                   and all(r() is sd for r, (_, sd) in zip(refs, w_locals))
                   and bool(devs) and set(devs) == set(last["table"].groups)
-                  and all(rows is not None or dt == torch.float32 for dt, (rows, _) in devs.items()))
+                  and all(rows is not None or dt == torch.float32 or "seg_keep0" in last
+                          for dt, (rows, _) in devs.items()))
         # the reference's `w[para] - w_glob[para]` raises on bool buffers; the
         # round's key table already holds every client's (validated) dtypes
         if cached:
@@ -926,6 +992,11 @@ class DeviceAggregator:
                     P = table.groups[dt].P
                     if dt in fused:  # formed by the aggregate's own pass over the rows
                         parts.append((dt, fused[dt], out_dev[:P]))
+                    elif devbuf is None and dt != torch.float32:  # zero-copy round: its rows packed on demand
+                        rows = self.materialize_rows(dt)
+                        if rows is None:
+                            raise ValueError("client_distances: the round's client dicts are gone")
+                        parts.append((dt, client_sqdist(rows, out_dev, P), out_dev[:P]))
                     elif devbuf is None:  # zero-copy round: read the clients' tensors where they lie
                         # the dict aliased to w_glob (client 0, :449) holds the average
                         # now; its own tensors stand in (its norm is overridden below)

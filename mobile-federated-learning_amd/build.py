@@ -1,5 +1,5 @@
-"""Build recipe for libfedavg_amd.so, libfedavg_amd_probe.so and
-libfedavg_amd_fusedvec.so (gfx950 only).
+"""Build recipe for libfedavg_amd.so, libfedavg_amd_probe.so,
+libfedavg_amd_fusedvec.so and libfedavg_amd_segvec.so (gfx950 only).
 
     python -m mfl_amd.build           # or __graft_entry__.build()
 
@@ -24,6 +24,11 @@ fp16 / bf16 rows, ``include/fedavg_amd_fusedvec.h``) is a product library of
 its own, ``lib/libfedavg_amd_fusedvec.so``: same flags, no ``FEDAVG_TUNING``,
 linked against ``libfedavg_amd.so`` (found next to it, ``$ORIGIN``) for the
 two-pass route.
+
+``csrc/fedavg_segments_vec.hip`` (a device-resident round's fp64 / fp16 / bf16
+group from the clients' own tensors, ``include/fedavg_amd_segvec.h``) is the
+third product library, ``lib/libfedavg_amd_segvec.so``: same flags, no
+``FEDAVG_TUNING``; it calls no other library, so it links none.
 """
 from __future__ import annotations
 
@@ -42,10 +47,12 @@ HIP_SOURCES = [CSRC_DIR / "fedavg_reduce.hip", CSRC_DIR / "fedavg_dist.hip",
                CSRC_DIR / "fedavg_segments.hip", CSRC_DIR / "fedavg_client.hip"]
 PROBE_SOURCES = [CSRC_DIR / "fedavg_variants.hip"]  # probe library only
 FUSEDVEC_SOURCES = [CSRC_DIR / "fedavg_fused_vec.hip"]  # libfedavg_amd_fusedvec.so only
+SEGVEC_SOURCES = [CSRC_DIR / "fedavg_segments_vec.hip"]  # libfedavg_amd_segvec.so only
 CSRC_HOST = CSRC_DIR / "fedavg_host.cpp"
 CSRC_COMMON = CSRC_DIR / "common.hpp"
 CSRC_WINDOW = CSRC_DIR / "window.hpp"  # what the rows and zero-copy window kernels share
 CSRC_STAGING = CSRC_DIR / "staging.hpp"  # host-side staged layouts (also g++-built by tests/native)
+CSRC_VEC_RULES = CSRC_DIR / "fused_vec_rules.hpp"  # dtype rules and bands of the fused-vec and seg-vec kernels
 CSRC_COLLECT = CSRC_DIR / "fedavg_collect_ext.cpp"
 COLLECT_NAME = "fedavg_collect_ext"
 INCLUDE = REPO_DIR / "include"
@@ -55,6 +62,7 @@ PROBE_OBJ_DIR = LIB_DIR / "obj_probe"
 LIB_PATH = LIB_DIR / "libfedavg_amd.so"
 PROBE_LIB_PATH = LIB_DIR / "libfedavg_amd_probe.so"
 FUSEDVEC_LIB_PATH = LIB_DIR / "libfedavg_amd_fusedvec.so"
+SEGVEC_LIB_PATH = LIB_DIR / "libfedavg_amd_segvec.so"
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [
@@ -77,12 +85,13 @@ def hipcc_path() -> str:
 
 
 def sources():
-    return [*HIP_SOURCES, *PROBE_SOURCES, *FUSEDVEC_SOURCES, CSRC_HOST, CSRC_COMMON, CSRC_WINDOW, CSRC_STAGING,
-            INCLUDE / "fedavg_amd.h", INCLUDE / "fedavg_amd_tuning.h", INCLUDE / "fedavg_amd_fusedvec.h", Path(__file__)]
+    return [*HIP_SOURCES, *PROBE_SOURCES, *FUSEDVEC_SOURCES, *SEGVEC_SOURCES, CSRC_HOST, CSRC_COMMON, CSRC_WINDOW,
+            CSRC_STAGING, CSRC_VEC_RULES, INCLUDE / "fedavg_amd.h", INCLUDE / "fedavg_amd_tuning.h",
+            INCLUDE / "fedavg_amd_fusedvec.h", INCLUDE / "fedavg_amd_segvec.h", Path(__file__)]
 
 
 def up_to_date() -> bool:
-    for lib in (LIB_PATH, PROBE_LIB_PATH, FUSEDVEC_LIB_PATH):
+    for lib in (LIB_PATH, PROBE_LIB_PATH, FUSEDVEC_LIB_PATH, SEGVEC_LIB_PATH):
         if not lib.exists():
             return False
         t = lib.stat().st_mtime
@@ -143,8 +152,8 @@ def _link(objs, lib_path, verbose, extra=()):
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Build the product library, the probe library and the fused-vec
-    library; returns the product path."""
+    """Build the product library, the probe library, the fused-vec library
+    and the seg-vec library; returns the product path."""
     if not force and up_to_date():
         return LIB_PATH
     OBJ_DIR.mkdir(parents=True, exist_ok=True)
@@ -164,12 +173,18 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         obj = OBJ_DIR / (src.name + ".o")
         jobs.append((src, obj, []))
         fusedvec_objs.append(obj)
+    segvec_objs = []
+    for src in SEGVEC_SOURCES:
+        obj = OBJ_DIR / (src.name + ".o")
+        jobs.append((src, obj, []))
+        segvec_objs.append(obj)
     _compile_all(jobs, verbose)
     _link(objs, LIB_PATH, verbose)
     _link(probe_objs, PROBE_LIB_PATH, verbose)
     # the two-pass route calls the product library, found next to this one at load time
     _link(fusedvec_objs, FUSEDVEC_LIB_PATH, verbose,
           extra=[f"-L{LIB_DIR}", f"-l:{LIB_PATH.name}", "-Wl,-rpath,$ORIGIN"])
+    _link(segvec_objs, SEGVEC_LIB_PATH, verbose)  # calls no other library
     return LIB_PATH
 
 

@@ -9,7 +9,8 @@
 // instance, found by reading the code; this makes that class of bug a test).
 //
 // Callers: fedavg_segments.hip (stage_tables, fedavg_device_round_f32),
-// fedavg_pack.hip (fedavg_pack_rows_device).  The walk they stage is over the
+// fedavg_pack.hip (fedavg_pack_rows_device), fedavg_segments_vec.hip
+// (stage_device_round_vec, fuzzed by tests/native/segvec_fuzz.cpp).  The walk they stage is over the
 // reference's state_dicts (client.py:96, fedavg_trainer.py:199).
 #pragma once
 
@@ -374,6 +375,112 @@ int stage_device_round(const RoundIn& in, void* host_ws, int64_t ws_bytes, PlanF
   out->used = used;
   out->moff = moff;
   out->bytes = with_map ? moff + units * static_cast<int64_t>(sizeof(int)) : (with_desc ? moff + dbytes : used);
+  return FEDAVG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// fedavg_device_round_{f64,f16,bf16} (fedavg_segments_vec.hip): one dtype
+// group of a device-resident round, every key raw storage of that dtype.
+// Workspace (host and device alike, 16-B aligned parts):
+//   SegKey[n_keys] | int64 ptrs[n_keys * K + pad] | weights[K] (8 B each
+//   reserved: fp64 for fp64 keys, fp32 for the 2-byte types)
+// ---------------------------------------------------------------------------
+struct VecWs {
+  int64_t ptrs, w, end;
+};
+
+inline VecWs round_vec_ws(int64_t K, int64_t n_keys) {
+  VecWs r;
+  r.ptrs = n_keys * static_cast<int64_t>(sizeof(SegKey));
+  r.w = round16(r.ptrs + (n_keys * K + kSegWinTablePad) * static_cast<int64_t>(sizeof(int64_t)));
+  r.end = r.w + round16(K * static_cast<int64_t>(sizeof(double)));
+  return r;
+}
+
+inline int64_t round_vec_workspace_bytes(int64_t K, int64_t n_keys) {
+  if (K <= 0 || n_keys <= 0) return 0;
+  return round_vec_ws(K, n_keys).end;
+}
+
+struct RoundVecIn {
+  const int64_t* client_ptrs;
+  int64_t ptr_ld;
+  const int64_t* key_index;  // null: key j is column j
+  const int64_t* key_numel;
+  const int64_t* key_offset;
+  int64_t n_keys, K;
+  const double* weights;
+  int64_t elem_size;  // 2: fp32 weights; 8: fp64 weights
+  int64_t span;       // the window's columns (the key table's unit width)
+};
+
+struct RoundVecOut {
+  int64_t units, bytes;   // bytes: what the H2D ships (from host_ws[0])
+  const void* first_src;  // null: every key is empty (nothing to launch)
+  const void* last_src;
+};
+
+// The key table (kind raw, unit_start in windows of `span` columns), the
+// key-major pointer table filled client-major (stage_device_round's order)
+// and the weights.  A non-empty key needs a non-null source (FEDAVG_EINVAL)
+// that is 16-B aligned (FEDAVG_EALIGN: the kernel reads 16-B slices through
+// range-checked descriptors based at the source); nothing is decided about
+// empty keys' sources, which are never dereferenced.
+// (stage_segment_tables does not fit: it takes a dense [K][n_keys] table with
+// no key_index / ptr_ld, fills key-major, wants key kinds and accepts 4-B
+// aligned sources; SegKey, kSegWinTablePad and its table layout are reused.)
+inline int stage_device_round_vec(const RoundVecIn& in, void* host_ws, int64_t ws_bytes, RoundVecOut* out, Msg* msg) {
+  const int64_t n_keys = in.n_keys, K = in.K, ld = in.ptr_ld;
+  if (K <= 0 || n_keys <= 0 || in.span <= 0 || (in.elem_size != 2 && in.elem_size != 8))
+    return msg->fail(FEDAVG_EINVAL, "bad sizes");
+  const VecWs L = round_vec_ws(K, n_keys);
+  if (ws_bytes < L.end) return msg->fail(FEDAVG_EINVAL, "workspace needs %lld bytes", (long long)L.end);
+  char* hb = static_cast<char*>(host_ws);
+  auto* hk = reinterpret_cast<SegKey*>(hb);
+  auto* hp = reinterpret_cast<int64_t*>(hb + L.ptrs);
+  *out = RoundVecOut{0, 0, nullptr, nullptr};
+  int64_t units = 0;
+  for (int64_t j = 0; j < n_keys; ++j) {
+    const int64_t col = in.key_index ? in.key_index[j] : j;
+    if (in.key_numel[j] < 0 || in.key_offset[j] < 0 || col < 0 || col >= ld ||
+        in.key_numel[j] > (int64_t(1) << 56))
+      return msg->fail(FEDAVG_EINVAL, "bad key %lld", (long long)j);
+    hk[j] = SegKey{in.key_numel[j], in.key_offset[j], kRaw, units};
+    units += (in.key_numel[j] + in.span - 1) / in.span;
+    if (units >= (int64_t(1) << 31)) return msg->fail(FEDAVG_EINVAL, "too many windows");
+  }
+  int64_t null_src = 0, align_bits = 0;
+  for (int64_t k = 0; k < K; ++k) {
+    const int64_t* row = in.client_ptrs + k * ld;
+    for (int64_t j = 0; j < n_keys; ++j) {
+      const int64_t p = row[in.key_index ? in.key_index[j] : j];
+      hp[j * K + k] = p;
+      if (in.key_numel[j] > 0) {
+        null_src |= static_cast<int64_t>(p == 0);
+        align_bits |= p & 15;
+      }
+    }
+  }
+  // the pad the windows' 64-address groups load unconditionally: never dereferenced
+  for (int64_t i = 0; i < kSegWinTablePad; ++i) hp[n_keys * K + i] = 0;
+  if (null_src) return msg->fail(FEDAVG_EINVAL, "a non-empty key has a null source");
+  if (align_bits) return msg->fail(FEDAVG_EALIGN, "a non-empty key's source is not 16-B aligned");
+  for (int64_t j = 0; j < n_keys && !out->first_src; ++j)
+    if (in.key_numel[j] > 0) out->first_src = reinterpret_cast<const void*>(hp[j * K]);
+  for (int64_t j = n_keys - 1; j >= 0 && !out->last_src; --j)
+    if (in.key_numel[j] > 0) out->last_src = reinterpret_cast<const void*>(hp[j * K + K - 1]);
+  // the reference's weights n_i / N (fedavg_trainer.py:453): fp64 as they are,
+  // or rounded once to fp32 (nearest even, the cast ATen applies at :455)
+  if (in.elem_size == 8) {
+    auto* hw = reinterpret_cast<double*>(hb + L.w);
+    for (int64_t k = 0; k < K; ++k) hw[k] = in.weights[k];
+    out->bytes = L.w + K * static_cast<int64_t>(sizeof(double));
+  } else {
+    auto* hw = reinterpret_cast<float*>(hb + L.w);
+    for (int64_t k = 0; k < K; ++k) hw[k] = static_cast<float>(in.weights[k]);
+    out->bytes = L.w + K * static_cast<int64_t>(sizeof(float));
+  }
+  out->units = units;
   return FEDAVG_OK;
 }
 

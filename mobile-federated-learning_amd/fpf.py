@@ -389,7 +389,9 @@ class FPFTracker:
         if devbuf is None and has_f32:
             raise ValueError("record_round: the round's client dicts are gone; call record_client before aggregate")
         if self._mixed:
-            rows = {dt: (devbuf if dt == torch.float32 else last["dev"][dt][0]) for dt in self.table.groups}
+            # packed on demand where the round read that group's tensors in place
+            rows = {dt: (devbuf if dt == torch.float32 else self._aggregator().materialize_rows(dt))
+                    for dt in self.table.groups}
             if any(v is None for v in rows.values()):
                 raise ValueError("record_round: the round left no device rows for every dtype group; "
                                  "call record_client before aggregate")
