@@ -510,7 +510,7 @@ int fedavg_fpf_end_round_f32(float* diffs, int64_t n_rows, int64_t ld, const uin
   const unsigned nparts = col_blocks(P, kFpfMaxPartials);
   if (workspace_elems < nparts)
     return set_error(FEDAVG_EINVAL, "%s: workspace needs %u doubles", what, nparts);
-  if (!(g2 != 0.f)) return set_error(FEDAVG_EINVAL, "%s: G2 must be nonzero", what);
+  if (!(g2 < 0.f || g2 > 0.f)) return set_error(FEDAVG_EINVAL, "%s: G2 must be nonzero and not NaN", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(fpf_gdiff_partials_kernel, dim3(nparts), dim3(kBlock), 0, s,
                      reinterpret_cast<const f32x4*>(w_glob), reinterpret_cast<const f32x4*>(last_w), P, workspace);
@@ -530,7 +530,7 @@ int fedavg_fpf_update_g(float* g_mat, float* itr_row, float* lru_itr, const uint
   const char* what = "fedavg_fpf_update_g";
   if (n_rows <= 0) return set_error(FEDAVG_EINVAL, "%s: n_rows must be >= 1", what);
   if (!g_mat || !itr_row || !selected) return set_error(FEDAVG_EINVAL, "%s: null buffer", what);
-  if (!(g1 != 0.f)) return set_error(FEDAVG_EINVAL, "%s: G1 must be nonzero", what);
+  if (!(g1 < 0.f || g1 > 0.f)) return set_error(FEDAVG_EINVAL, "%s: G1 must be nonzero and not NaN", what);
   const float c1 = static_cast<float>(1.0 - 1.0 / static_cast<double>(g1));
   hipLaunchKernelGGL(fpf_update_g_kernel, dim3(static_cast<unsigned>((n_rows + kBlock - 1) / kBlock)), dim3(kBlock),
                      0, static_cast<hipStream_t>(stream), g_mat, itr_row, lru_itr, selected, n_rows, local_itr,
@@ -621,7 +621,9 @@ int fedavg_fpf_end_round_promoted(float* diffs, int64_t n_rows, int64_t ld, cons
   if (!keep_rows || !a_mat || !gdiff || !workspace) return set_error(FEDAVG_EINVAL, "%s: null buffer", what);
   const unsigned nparts = col_blocks(P, kFpfMaxPartials);
   if (workspace_elems < nparts) return set_error(FEDAVG_EINVAL, "%s: workspace needs %u doubles", what, nparts);
-  if (!(g2 != 0.f)) return set_error(FEDAVG_EINVAL, "%s: G2 must be nonzero", what);
+  if (!(g2 < 0.f || g2 > 0.f)) return set_error(FEDAVG_EINVAL, "%s: G2 must be nonzero and not NaN", what);
+  if (t_kind < kF32 || t_kind > kF64FromF32)  // refused before the partial sums are launched
+    return set_error(FEDAVG_EINVAL, "%s: t_kind must be 0..4 (got %d)", what, t_kind);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(fpf_sum_f64_kernel, dim3(nparts), dim3(kBlock), 0, s, gdiff, P, workspace);
   rc = launch_status(what);
@@ -651,7 +653,6 @@ int fedavg_fpf_end_round_promoted(float* diffs, int64_t n_rows, int64_t ld, cons
       hipLaunchKernelGGL(fpf_end_round_promoted_kernel<kBF16>, grid, dim3(kBlock), 0, s, diffs, ld, n_rows, keep_rows,
                          a_mat, gdiff, P, workspace, np, static_cast<double>(g2), c2);
       break;
-    default: return set_error(FEDAVG_EINVAL, "%s: t_kind must be 0..4 (got %d)", what, t_kind);
   }
   return launch_status(what);
 }
