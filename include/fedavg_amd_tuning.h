@@ -147,8 +147,8 @@ int fedavg_reduce_segments_f32_variant(const int64_t* client_ptrs, const int64_t
 /*
  * :291 on device-resident clients (fedavg_client_sqdist_segments_f32, same
  * tables and workspaces) with an explicit schedule: unroll client rows per
- * load batch x cols 16-B slices per thread, (U, C) in {(1,4), (2,4), (4,4),
- * (8,4), (4,1), (8,1), (4,2), (8,2), (2,8), (4,8)}; units of 1,024 x cols
+ * load batch x cols 16-B slices per thread, (U, C) in {(1,4), (4,4), (8,4),
+ * (4,1), (8,1), (4,2), (8,2), (4,8)}; units of 1,024 x cols
  * columns; partials: K x units x 4 doubles for that unit size.
  */
 int fedavg_client_sqdist_segments_f32_variant(const int64_t* client_ptrs, const int64_t* key_numel,
@@ -172,13 +172,25 @@ int fedavg_reduce_f32_buf(const float* clients, int64_t K, int64_t P, int64_t ld
  * count ends at the last float4 (lanes past it read 0); (unroll, cols) in
  * {(4,8), (8,4), (2,16), (2,8), (8,8)}; round-split launches of <= max_blocks
  * blocks (0 = one launch).  Same workspace as fedavg_client_sqdist_f32. */
-/* fedavg_reduce_sqdist_f32 with an explicit tile width (cols = 64, 128 or
- * 256 columns) and workgroups per CU (0 = as many as LDS allows); K <= 128,
- * workspace >= K x (blocks per CU x CUs) doubles.  Other codes select the
- * probe kernels listed at the switch in fedavg_dist.hip, among them the
- * wave-owned windows: 70000000 + KMAX x 100 + 40 + VEC (K <= KMAX; KMAX x
- * VEC in 16 x 4, 32 x 4, 48 x 4, 64 x 2, 80 x 2, 100 x 2, 128 x 1; workspace
- * >= K x 4 x workgroups). */
+/* fedavg_reduce_sqdist_f32 with an explicit kernel (cols = the code) and,
+ * for the tile kernels, workgroups per CU (0 = as many as are resident);
+ * workspace >= K x the launch's workgroups (one-wave windows: waves)
+ * doubles.  Any other code returns FEDAVG_EMODE with no launch.
+ *   LDS-DMA tiles: 64, 128, 256 columns; + 1000 double-buffered (1064, 1128,
+ *     1256); + 10000 rows per wave, K <= 128 (10064, 10128, 11128)
+ *   register-staged tiles: 200032, 200064; 16 slots per thread 1800032,
+ *     1800064; two tiles in flight 10200064; loads only (wrong results)
+ *     300064, 310128; over a TILED buffer [ceil(P / S)][K][S] 1200064,
+ *     1300064, 1310128; XCD- / XCD- and CU-contiguous sweeps (256 CUs, full
+ *     grid) 2200064, 2300064 / 4200064, 4300064
+ *   wave-owned windows: 70000000 + KMAX x 100 + 40 + VEC (K <= KMAX; KMAX x
+ *     VEC in 16 x 4, 32 x 4, 48 x 4, 64 x 2, 80 x 2, 100 x 2, 128 x 1); the
+ *     81-100 band's LDS-row form 124000042 (24 < K <= 100), with loads only
+ *     125000042 (wrong results) and fp32 squares 128000042 (sums differ)
+ *   split-row windows with hand-offs: 91000000 + PF x 100 + NSMAX for
+ *     (NSMAX, PF) in (8,8), (8,16), (16,8), (16,16), 2 <= K <= 64 NSMAX;
+ *     91081616: <16, 16> with the timeline stamps (workspace + 1 + 8 x 16 x
+ *     48 x 8 doubles; scripts/winn_timeline.py) */
 int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P, int64_t ld,
                                      const float* weights, float* out, double* workspace,
                                      int64_t workspace_elems, double* sumsq, int cols,

@@ -364,18 +364,15 @@ __global__ __launch_bounds__(kBlock) void client_sqdist_finalize_kernel(const do
 // rows -> LDS for the tile at column c0: slot i = row * V + j (LDS byte
 // 16 i from `buf`) holds slice j ^ (row & 7) of the row segment
 // Load slots per thread at the widest K each tile width serves (fused_cols):
-// 300 x 32, 128 x 64, 64 x 128, 32 x 256 columns
-template <int S>
-constexpr int fused_slots() {
-  return S == 32 ? 10 : 8;
-}
+// 128 x 64, 64 x 128, 32 x 256 columns
+constexpr int kFusedSlots = 8;
 
 // The byte offset (row * ld + slice) of each of this thread's load slots,
 // the same for every tile: computed once per workgroup, so a tile's loads
 // cost one 64-bit add each instead of the row / slice / swizzle arithmetic
 template <int S>
 struct FusedSlots {
-  int64_t off[fused_slots<S>()];
+  int64_t off[kFusedSlots];
 };
 
 template <int S>
@@ -384,7 +381,7 @@ __device__ __forceinline__ FusedSlots<S> fused_slots_of(int K, int64_t ld) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   FusedSlots<S> sl;
 #pragma unroll
-  for (int m = 0; m < fused_slots<S>(); ++m) {
+  for (int m = 0; m < kFusedSlots; ++m) {
     const int i = wave * 64 + m * kBlock + lane;
     const int row = i / V;
     const int c = (i % V) ^ (row & 7);
@@ -403,7 +400,7 @@ __device__ __forceinline__ void fused_load_full(const float* __restrict__ X, int
   const int nload = K * V;
   const char* base = reinterpret_cast<const char*>(X + c0);
 #pragma unroll
-  for (int m = 0; m < fused_slots<S>(); ++m) {
+  for (int m = 0; m < kFusedSlots; ++m) {
     const int i0 = wave * 64 + m * kBlock;
     if (i0 < nload && i0 + lane < nload)
       __builtin_amdgcn_global_load_lds((fused_gbl_t)(base + sl.off[m]), (fused_lds_t)(buf + 4 * i0), 16, 0, 2 /* nt */);
@@ -429,13 +426,15 @@ __device__ __forceinline__ void fused_load_tile(const float* __restrict__ X, int
 }
 
 
-template <int S, bool DB, int RW = 0, bool LOADS_ONLY = false, int RM = 1>
+// (the fourth template argument was the retired loads-only probe: always
+// false, it stays because the pinned instance names carry it)
+template <int S, bool DB, int RW = 0, bool = false, int RM = 1>
 __global__ __launch_bounds__(kBlock) void reduce_sqdist_f32_kernel(const float* __restrict__ X, int K, int64_t ld,
                                                                    int64_t P, int64_t ntiles,
                                                                    const float* __restrict__ W,
                                                                    float* __restrict__ out,
                                                                    double* __restrict__ partials) {
-  static_assert(S == 32 || S == 64 || S == 128 || S == 256, "tile widths: 32, 64, 128 or 256 columns");
+  static_assert(S == 64 || S == 128 || S == 256, "tile widths: 64, 128 or 256 columns");
   // one tile buffer [K][S] (swizzled slots) -- two when DB -- then the tile's average [S]
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tile_floats = K * S;
@@ -459,16 +458,11 @@ __global__ __launch_bounds__(kBlock) void reduce_sqdist_f32_kernel(const float* 
       // 1. the next tile's rows stream into the other buffer while this one is used
       if (t + gridDim.x < ntiles) fused_load_tile<S>(X, K, ld, P, (t + gridDim.x) * S, lds + (cur ^ 1) * tile_floats);
     } else {
-      if (ncols == S && !RW && K * (S / 4) <= fused_slots<S>() * kBlock)  // 1. rows -> LDS
+      if (ncols == S && !RW && K * (S / 4) <= kFusedSlots * kBlock)  // 1. rows -> LDS
         fused_load_full<S>(X, K, c0, slots, tile);
       else
         fused_load_tile<S>(X, K, ld, P, c0, tile);
       barrier_loads();
-    }
-    if constexpr (LOADS_ONLY) {  // probe: the tile traffic alone (one column of each tile stored)
-      if (threadIdx.x == 0) out[c0] = tile[0];
-      barrier_lds();
-      continue;
     }
     fused_average<S>(tile, gs, K, W, ncols, out + c0);  // 2. the average of each column
     barrier_lds();
@@ -549,38 +543,38 @@ int fused_launch(const FusedCall& c, int64_t parts, int64_t extra, Launch&& laun
 
 // Workgroups per CU the fused kernel keeps resident at this K (LDS-bound);
 // 0 = the LDS request cannot be granted.
-template <int S, bool DB = false, int RW = 0, bool LO = false, int RM = 1>
+template <int S, bool DB = false, int RW = 0, int RM = 1>
 int fused_per_cu(int64_t K) {
-  return lds_blocks_per_cu(reduce_sqdist_f32_kernel<S, DB, RW, LO, RM>, kBlock, fused_lds_bytes(K, S, DB));
+  return lds_blocks_per_cu(reduce_sqdist_f32_kernel<S, DB, RW, false, RM>, kBlock, fused_lds_bytes(K, S, DB));
 }
 
-template <int S, bool DB = false, int RW = 0, bool LO = false, int RM = 1>
+template <int S, bool DB = false, int RW = 0, int RM = 1>
 int64_t fused_grid(int64_t K, int64_t P, int blocks_per_cu) {
-  return persistent_grid(blocks_per_cu > 0 ? blocks_per_cu : fused_per_cu<S, DB, RW, LO, RM>(K), cu_count(),
+  return persistent_grid(blocks_per_cu > 0 ? blocks_per_cu : fused_per_cu<S, DB, RW, RM>(K), cu_count(),
                          (P + S - 1) / S);
 }
 
 // RM = rows per thread in the squares: 1 up to 256 rows, else 2 (the variants')
-template <int S, bool DB, int RW, bool LO, int RM>
+template <int S, bool DB, int RW, int RM>
 int launch_fused_rm(const FusedCall& c, int blocks_per_cu) {
   if (RW > 0 && c.K > 4 * RW)
     return set_error(FEDAVG_EMODE, "%s: %d rows per wave cover K <= %d", c.what, RW, 4 * RW);
-  if (fused_per_cu<S, DB, RW, LO, RM>(c.K) <= 0)
+  if (fused_per_cu<S, DB, RW, RM>(c.K) <= 0)
     return set_error(FEDAVG_EMODE, "%s: the %d-column tile does not fit LDS at K = %lld", c.what, S, (long long)c.K);
   const int64_t ntiles = (c.P + S - 1) / S;
-  const int64_t grid = fused_grid<S, DB, RW, LO, RM>(c.K, c.P, blocks_per_cu);
+  const int64_t grid = fused_grid<S, DB, RW, RM>(c.K, c.P, blocks_per_cu);
   return fused_launch(c, grid, 0, [&] {
-    hipLaunchKernelGGL((reduce_sqdist_f32_kernel<S, DB, RW, LO, RM>), dim3(static_cast<unsigned>(grid)), dim3(kBlock),
+    hipLaunchKernelGGL((reduce_sqdist_f32_kernel<S, DB, RW, false, RM>), dim3(static_cast<unsigned>(grid)), dim3(kBlock),
                        static_cast<unsigned>(fused_lds_bytes(c.K, S, DB)), c.s, c.clients, static_cast<int>(c.K), c.ld,
                        c.P, ntiles, c.weights, c.out, c.partials);
   });
 }
 
 #ifdef FEDAVG_TUNING  // the variants pick RM by K; production names RM 1 (K <= 128)
-template <int S, bool DB = false, int RW = 0, bool LO = false>
+template <int S, bool DB = false, int RW = 0>
 int launch_fused(const FusedCall& c, int blocks_per_cu) {
-  if (c.K <= kBlock) return launch_fused_rm<S, DB, RW, LO, 1>(c, blocks_per_cu);
-  if constexpr (RW == 0 && !LO) return launch_fused_rm<S, DB, RW, LO, 2>(c, blocks_per_cu);
+  if (c.K <= kBlock) return launch_fused_rm<S, DB, RW, 1>(c, blocks_per_cu);
+  if constexpr (RW == 0) return launch_fused_rm<S, DB, RW, 2>(c, blocks_per_cu);
   return set_error(FEDAVG_EMODE, "%s: this variant covers K <= %d", c.what, kBlock);
 }
 #endif  // FEDAVG_TUNING
@@ -604,28 +598,23 @@ int launch_fused(const FusedCall& c, int blocks_per_cu) {
 //      always belongs to the same row, so one fp64 accumulator per slot lives
 //      across all tiles, and the V threads of a row (one per slice) are added
 //      in a fixed order at the end: partials[row][workgroup].
-// MODE 1 / 2 are traffic probes (1: loads only; 2: loads + LDS writes).
+// MODE 1 is a traffic probe (loads only: wrong results).
 // ---------------------------------------------------------------------------
 // FLAGS (probes): 1 = TILED buffer [ntiles][K][S] (each tile's rows contiguous);
 // 2 = the workgroups of one XCD take contiguous tiles of a sweep (dispatch
 // puts workgroup b on XCD b % 8); 4 = and the workgroups of one CU too
 // (b, b + 256, ... share a CU).  Both remaps are bijections of the sweep: a
 // different placement only changes the speed.
-// DEPTH 2: two tiles' loads in flight per workgroup (two register stages,
-// the tile in LDS a third).  MODE 3: loads only with no LDS at all (probe:
-// the tile walk at the occupancy registers alone allow).
-constexpr int rs_min_waves(int S, int DEPTH) {
-  return DEPTH == 1 || S == 256 ? 1 : (S <= 64 ? 4 : (DEPTH == 2 ? 3 : 2));
-}
-
+// DEPTH 2 (64 columns): two tiles' loads in flight per workgroup (two register
+// stages, the tile in LDS a third), four waves per SIMD.
 template <int S, int SLOTS, int MODE = 0, int FLAGS = 0, int DEPTH = 1>
-__global__ __launch_bounds__(kBlock, rs_min_waves(S, DEPTH)) void reduce_sqdist_rs_kernel(const float* __restrict__ X, int K, int64_t ld,
+__global__ __launch_bounds__(kBlock, DEPTH == 1 ? 1 : 4) void reduce_sqdist_rs_kernel(const float* __restrict__ X, int K, int64_t ld,
                                                                   int64_t P, int64_t ntiles,
                                                                   const float* __restrict__ W,
                                                                   float* __restrict__ out,
                                                                   double* __restrict__ partials) {
   static_assert(S == 32 || S == 64 || S == 128 || S == 256, "tile widths: 32, 64, 128 or 256 columns");
-  static_assert(DEPTH >= 1 && DEPTH <= 3, "one to three tiles in flight");
+  static_assert(DEPTH == 1 || (DEPTH == 2 && S == 64), "one tile in flight, or two of 64 columns");
   constexpr int V = S / 4;
   constexpr int R = kBlock / V;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -657,7 +646,7 @@ __global__ __launch_bounds__(kBlock, rs_min_waves(S, DEPTH)) void reduce_sqdist_
   const auto body = [&](f32x4 (&xs)[SLOTS], int64_t tt, int64_t next) {
     const int64_t c0 = tt * S;
     const int ncols = P - c0 < S ? static_cast<int>(P - c0) : S;
-    if constexpr (MODE == 1 || MODE == 3) {
+    if constexpr (MODE == 1) {
       float probe = 0.f;
 #pragma unroll
       for (int m = 0; m < SLOTS; ++m)
@@ -672,10 +661,6 @@ __global__ __launch_bounds__(kBlock, rs_min_waves(S, DEPTH)) void reduce_sqdist_
       if (m < nslot) tile4[t + kBlock * m] = xs[m];  // 1. (a ragged slice keeps stale data: never used)
     barrier_lds();
     if (next < ntiles) issue(xs, next);  // 2. that stage's next tile in flight
-    if constexpr (MODE == 2) {
-      if (t == 0) out[c0] = lds[0];
-      return;
-    }
     if (t < S) {  // 3. the average of column t, in the reference's order
       float a = lds[t] * W[0];
       constexpr int kUnroll = S == 64 ? 32 : 16;
@@ -730,24 +715,13 @@ __global__ __launch_bounds__(kBlock, rs_min_waves(S, DEPTH)) void reduce_sqdist_
   if (first < ntiles) issue(xa, first);
   if constexpr (DEPTH == 1) {
     for (int64_t tt = first; tt < ntiles; tt += G) body(xa, tt, tt + G);
-  } else if constexpr (DEPTH == 2) {
+  } else {
     f32x4 xb[SLOTS];
     if (first + G < ntiles) issue(xb, first + G);
     for (int64_t tt = first; tt < ntiles; tt += 2 * G) {
       body(xa, tt, tt + 2 * G);
       if (tt + G >= ntiles) break;
       body(xb, tt + G, tt + 3 * G);
-    }
-  } else {
-    f32x4 xb[SLOTS], xc[SLOTS];
-    if (first + G < ntiles) issue(xb, first + G);
-    if (first + 2 * G < ntiles) issue(xc, first + 2 * G);
-    for (int64_t tt = first; tt < ntiles; tt += 3 * G) {
-      body(xa, tt, tt + 3 * G);
-      if (tt + G >= ntiles) break;
-      body(xb, tt + G, tt + 4 * G);
-      if (tt + 2 * G >= ntiles) break;
-      body(xc, tt + 2 * G, tt + 5 * G);
     }
   }
   if constexpr (MODE != 0) return;
@@ -768,12 +742,11 @@ __global__ __launch_bounds__(kBlock, rs_min_waves(S, DEPTH)) void reduce_sqdist_
 
 // LDS of a register-staged tile: [K][S] + the average [S]; the final per-row
 // sums need K * V doubles (= K * S * 2 bytes, inside the tile)
-inline int64_t fused_rs_lds_bytes(int64_t K, int S, int mode = 0) { return mode == 3 ? 0 : (K + 1) * S * 4; }
+inline int64_t fused_rs_lds_bytes(int64_t K, int S) { return (K + 1) * S * 4; }
 
 template <int S, int SLOTS, int MODE, int FLAGS = 0, int DEPTH = 1>
 int fused_rs_per_cu(int64_t K) {
-  return lds_blocks_per_cu(reduce_sqdist_rs_kernel<S, SLOTS, MODE, FLAGS, DEPTH>, kBlock,
-                           fused_rs_lds_bytes(K, S, MODE));
+  return lds_blocks_per_cu(reduce_sqdist_rs_kernel<S, SLOTS, MODE, FLAGS, DEPTH>, kBlock, fused_rs_lds_bytes(K, S));
 }
 
 template <int S, int SLOTS, int MODE, int FLAGS = 0, int DEPTH = 1>
@@ -799,7 +772,7 @@ int launch_fused_rs(const FusedCall& c, int blocks_per_cu) {
     return set_error(FEDAVG_EMODE, "%s: the XCD / CU remaps need a full grid on 256 CUs", c.what);
   return fused_launch(c, grid, 0, [&] {
     hipLaunchKernelGGL((reduce_sqdist_rs_kernel<S, SLOTS, MODE, FLAGS, DEPTH>), dim3(static_cast<unsigned>(grid)),
-                       dim3(kBlock), static_cast<unsigned>(fused_rs_lds_bytes(K, S, MODE)), c.s, c.clients,
+                       dim3(kBlock), static_cast<unsigned>(fused_rs_lds_bytes(K, S)), c.s, c.clients,
                        static_cast<int>(K), c.ld, c.P, ntiles, c.weights, c.out, c.partials);
   }, MODE == 0);  // the probe modes' partials are not sums
 }
@@ -832,9 +805,6 @@ int launch_fused_rs(const FusedCall& c, int blocks_per_cu) {
 // slice (num_records 0 past the last window: the tail's reloads are dropped
 // in the address unit, no traffic), columns past P inside the last slice are
 // zeroed before the chain.
-// MODE 256 (probe): the chain's weights by row broadcast (lane 16r + j of
-// wvb[k] = row 16k + j's weight) in hand-pipelined 8-row blocks
-// (chain8_row_bcast2): no v_readlane / LDS weight reads, four VALU a row.
 // MODE 1: loads only (a traffic probe: wrong results).  MODE 4 (probe):
 // squares in fp32 (the VEC columns' fl32(d*d) summed in fp32, widened once
 // per row): the fp64 VALU stream's share of time and clock, measured.
@@ -854,7 +824,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_win_kernel(
   const uint32_t voff = static_cast<uint32_t>(lane) * VEC * 4;
   const int64_t P4 = (P + 3) & ~static_cast<int64_t>(3);  // rows are read up to their last 16-B slice
   const int64_t row_bytes = ld * 4;
-  const uint32_t rb32 = static_cast<uint32_t>(row_bytes);  // MODE 128: soffset steps
   const bool upper = (lane & 8) != 0;
 
   // window w's bytes per row (0: no such window -- its loads return 0 and move nothing)
@@ -877,21 +846,11 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_win_kernel(
   __shared__ double accl[NW][NB][64];
   for (int i = threadIdx.x; i < ((KMAX + 3) & ~3); i += 64 * NW) wl[i] = i < K ? W[i] : -0.0f;
   float wv0 = lane < K ? W[lane] : -0.0f, wv1 = 64 + lane < K ? W[64 + lane] : -0.0f;  // LROWS: lane l = W[l], W[64 + l]
-  constexpr bool BCW = (MODE & 256) != 0;
-  static_assert(!BCW || (VEC == 2 && KMAX >= 16), "broadcast weights: VEC 2, 8-row blocks");
-  float wvb[BCW ? (KMAX + 15) / 16 : 1];
-  if constexpr (BCW) {
-#pragma unroll
-    for (int k = 0; k < (KMAX + 15) / 16; ++k) {
-      const int row = 16 * k + (lane & 15);
-      wvb[k] = row < K ? W[row] : -0.0f;
-    }
-  }
   double* acc = &accl[threadIdx.x >> 6][0][lane];
 #pragma unroll
   for (int b = 0; b < NB; ++b) acc[64 * b] = 0.0;
   __syncthreads();
-  // MODE 64 (probe): rows 0..E-1 of the next window are staged in LDS by
+  // MODE 64 (the 81-100 band's form): rows 0..E-1 of the next window are staged in LDS by
   // LDS-DMA before this window's chain (the VGPR rows free up only in the
   // squares), so E rows stay in flight through the chain; K > E
   constexpr bool LROWS = (MODE & 64) != 0;
@@ -954,29 +913,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_win_kernel(
       }
       rp += E * row_bytes;  // the VGPR rows start at row E
     }
-    // MODE 128 (probe): one descriptor per 8 rows with the row in soffset.
-    // The range check covers soffset + voffset, so a group's record count
-    // ends at its last existing row's window bytes (rows past K, and the
-    // window past the model's last slice on that row, read 0); the other
-    // rows of a ragged window read their padding (zeroed before the chain).
-    // Needs 7 row pitches + a window < 4 GiB (the launcher checks).
-    __amdgpu_buffer_rsrc_t grs;
-    const char* gp = reinterpret_cast<const char*>(X + (w + GW) * WC) + E * row_bytes;
     const auto reload = [&](int i) {  // row i of the next window into x[i]
-      if constexpr ((MODE & 128) != 0) {
-        const int j = i & 7;
-        if (j == 0) {
-          asm volatile("" : "+s"(gp));
-          const int rows = Kw - (i & ~7);  // rows of this group that exist
-          const uint32_t nr = (nbn == 0 || rows <= 0)
-                                  ? 0u
-                                  : static_cast<uint32_t>((rows < 8 ? rows : 8) - 1) * rb32 + static_cast<uint32_t>(nbn);
-          grs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(gp), 0, static_cast<int>(nr), 0x00020000);
-          gp += 8 * row_bytes;
-        }
-        x[i] = win_load<VEC>(grs, voff, static_cast<uint32_t>(j) * rb32);
-        return;
-      }
       asm volatile("" : "+s"(rp));
       x[i] = win_load<VEC>(__builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(rp), 0, i < Kw ? nbn : 0, 0x00020000),
                            voff);
@@ -1002,30 +939,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_win_kernel(
     }
     // the reference's chain, per lane: fl32(x_0 w_0), then + fl32(x_i w_i) in client order
     V a;
-    if constexpr (BCW) {
-      float a0 = -0.0f, a1 = -0.0f;  // fl32(-0.0 + p) is p, bit for bit
-      float tc0 = mul_row_bcast<0>(wvb[0], x[0][0]), tc1 = mul_row_bcast<0>(wvb[0], x[0][1]);
-      constexpr int NBLK = KMAX / 8, REM = KMAX % 8;
-      static_for<NBLK>([&](auto bc) {
-        constexpr int b = decltype(bc)::value;
-        constexpr bool last = b == NBLK - 1 && REM == 0;
-        chain8_row_bcast2<b % 2, last>(a0, a1, tc0, tc1, wvb[b / 2], wvb[last ? b / 2 : (b + 1) / 2], x + 8 * b);
-      });
-      static_for<REM>([&](auto rc) {  // the rows past the last 8-row block (tc: row 8 NBLK + r's product)
-        constexpr int i = 8 * NBLK + decltype(rc)::value;
-        float n0 = 0.f, n1 = 0.f;
-        if constexpr (i + 1 < KMAX) {
-          n0 = mul_row_bcast<i + 1>(wvb[(i + 1) / 16], x[i + 1][0]);
-          n1 = mul_row_bcast<i + 1>(wvb[(i + 1) / 16], x[i + 1][1]);
-        }
-        a0 = a0 + tc0;
-        a1 = a1 + tc1;
-        tc0 = n0;
-        tc1 = n1;
-      });
-      a[0] = a0;
-      a[1] = a1;
-    } else if constexpr (LROWS) {
+    if constexpr (LROWS) {
       // weights from VGPR lanes (v_readlane): an LDS read here would wait for
       // the LDS-DMA just issued (the compiler cannot tell the arrays apart)
       asm volatile("" : "+v"(wv0), "+v"(wv1));  // re-read per window: not hoisted into SGPRs
@@ -1065,8 +979,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_win_kernel(
         if (cl + v < P) out[cl + v] = a[v];
     }
     // squares of fl32(x - g), each row reloaded with the next window's row as soon as it is squared
-    if constexpr ((MODE & 2) != 0) __builtin_amdgcn_s_setprio(2);  // probe: the reload issue first (no effect)
-    if constexpr ((MODE & 16) != 0) __builtin_amdgcn_s_barrier();  // probe: the workgroup's waves reload in step
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       double p[8];
@@ -1087,13 +999,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void reduce_sqdist_win_kernel(
           if (i >= E) reload(i);
         }
       }
-      if constexpr ((MODE & 8) != 0) {  // probe: no folds (rows mixed: timing only)
-        acc[64 * b] += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-        continue;
-      }
       acc[64 * b] += win_fold_batch(p, upper);
     }
-    if constexpr ((MODE & 2) != 0) __builtin_amdgcn_s_setprio(0);
   }
   if constexpr ((MODE & 1) != 0) {
     if (probe == 12345.f) out[0] = probe;  // keep the loads
@@ -1121,8 +1028,6 @@ template <int KMAX, int VEC, int NW, int MODE = 0, int MINW = win_min_waves(KMAX
 int launch_fused_win(const FusedCall& c, int blocks_per_cu) {
   if (c.K > KMAX) return set_error(FEDAVG_EMODE, "%s: this window kernel covers K <= %d", c.what, KMAX);
   if ((MODE & 64) != 0 && c.K <= 24) return set_error(FEDAVG_EMODE, "%s: LDS rows need K > 24", c.what);
-  if ((MODE & 128) != 0 && c.ld * 4 * 7 + 64 * VEC * 4 >= (int64_t(1) << 32))
-    return set_error(FEDAVG_EMODE, "%s: 8-row descriptors need 7 row pitches + a window < 4 GiB", c.what);
   const int64_t waves = fused_win_waves<KMAX, VEC, NW, MODE, MINW>(c.P, blocks_per_cu);
   if (waves <= 0) return set_error(FEDAVG_EMODE, "%s: the window kernel is not resident", c.what);
   const int64_t nwin = (c.P + 64 * VEC - 1) / (64 * VEC);
@@ -1134,284 +1039,20 @@ int launch_fused_win(const FusedCall& c, int blocks_per_cu) {
 }
 
 // ---------------------------------------------------------------------------
-// Split-row windows (round 5) for 369-1024 rows.  The register-staged tiles
-// ran 500 x 11.2M at 5.4 ms (52 % of HBM peak; a tile's K-step chain runs on
-// 32 lanes only) and the two passes took over beyond 512 rows.  A workgroup of ns = ceil(K / KH) <=
-// NSMAX waves owns a window of 64 x VEC columns; wave h holds rows h*KH ..
-// h*KH + KH - 1 in registers.  The chain keeps the reference's order: wave 0
-// runs its rows, hands its fp32 partial over LDS to wave 1, ... wave ns-1
-// ends it and stores the average; then every wave squares its own rows
-// against it and reloads them from the next window (as reduce_sqdist_win2).
-// Rows past K load through an empty descriptor (+0) with weight -0.0, which
-// leaves every chain value unchanged.
-// PF > 0: the first PF rows of the next window are loaded into spare
-// registers as the window starts, so HBM has work while the chain runs (at
-// one workgroup per CU nothing else is in flight then: the reloads wait for
-// the squares, the squares for the chain's last wave); after squaring row
-// i < PF the wave takes the prefetched row instead of reloading it.
-// LE > 0 (round 6 probe): rows PF .. PF+LE-1 of the next window go to LDS by
-// LDS-DMA as the window starts (no registers: the row loads stream through
-// the chain), and are read back in the squares in place of their reloads.
-// MODE (probe, timing only): 1 = no chain (every wave takes x[0] as the
-// average, no hand-offs), 2 = no squares (rows reloaded, nothing summed),
-// 16 = the chain's weights by DPP broadcast: lane 16r + j of wv[k] holds row
-// 16k + j's weight (every r), read once per launch, and row_newbcast:j hands
-// it to the v_mul (no LDS reads and no lgkmcnt waits inside a turn),
-// 8 = timeline: lane 0 of every wave of the first kStampBlocks workgroups
-// stores s_memtime at five points of its first kStampWins windows, after the
-// K x G partials (winn_stamp_elems; scripts/winn_timeline.py reads them).
-// ---------------------------------------------------------------------------
-// s_waitcnt vmcnt(0) expcnt(7) lgkmcnt(15) (gfx9 encoding: vmcnt in [3:0] and [15:14])
-constexpr int kWaitVmcnt0 = 0x0F70;
-
-#ifdef FEDAVG_TUNING  // probe library only: production runs the hand-off form below (reduce_sqdist_winf_kernel)
-template <int KH, int VEC, int NSMAX, int PF = 0, int LE = 0, int MODE = 0>
-__global__ __launch_bounds__(64 * NSMAX, win_min_waves(KH, VEC)) void reduce_sqdist_winn_kernel(
-    const float* __restrict__ X, int K, int64_t ld, int64_t P, int64_t nwin, const float* __restrict__ W,
-    float* __restrict__ out, double* __restrict__ partials) {
-  typedef typename WinVec<VEC>::T V;
-  constexpr int WC = 64 * VEC;
-  constexpr int NB = (KH + 7) / 8;
-  constexpr int KP = (KH + 3) & ~3;
-  const int lane = threadIdx.x & 63;
-  const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ns = __builtin_amdgcn_readfirstlane(static_cast<int>(blockDim.x >> 6));
-  const int r0 = h * KH;
-  const int64_t G = gridDim.x;
-  const uint32_t voff = static_cast<uint32_t>(lane) * VEC * 4;
-  const int64_t P4 = (P + 3) & ~static_cast<int64_t>(3);
-  const int64_t row_bytes = ld * 4;
-  const bool upper = (lane & 8) != 0;
-  const auto win_bytes = [&](int64_t w) -> int {
-    if (w >= nwin) return 0;
-    const int64_t n = P4 - w * WC;
-    return static_cast<int>((n < WC ? n : WC) * 4);
-  };
-  __shared__ __attribute__((aligned(16))) float wl[NSMAX][KP];
-  __shared__ double accl[NSMAX][NB][64];
-  __shared__ __attribute__((aligned(16))) V xa[64];
-  static_assert(LE == 0 || VEC == 1, "LDS rows: 256-B row segments");
-  static_assert(PF + LE <= KH, "prefetched rows");
-  __shared__ __attribute__((aligned(16))) float rowl[LE > 0 ? NSMAX : 1][LE > 0 ? LE : 1][64];
-  uint64_t* const stamps = reinterpret_cast<uint64_t*>(partials + static_cast<int64_t>(K) * G);
-  int wi = 0;  // window count (timeline probe)
-  const auto stamp = [&](int ph) __attribute__((always_inline)) {
-    if constexpr ((MODE & 8) != 0) {
-      if (blockIdx.x < kStampBlocks && wi < kStampWins) {
-        const uint64_t t = __builtin_amdgcn_s_memtime();
-        if (lane == 0) stamps[1 + ((int64_t(blockIdx.x) * NSMAX + h) * kStampWins + wi) * kStampSlots + ph] = t;
-      }
-    }
-  };
-  if constexpr ((MODE & 8) != 0) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) stamps[0] = kStampMagic;
-  }
-  for (int i = threadIdx.x; i < ns * KP; i += blockDim.x) {
-    const int hh = i / KP, j = i % KP, row = hh * KH + j;
-    wl[hh][j] = (j < KH && row < K) ? W[row] : -0.0f;
-  }
-  double* acc = &accl[h][0][lane];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) acc[64 * b] = 0.0;
-  __syncthreads();
-  constexpr bool kBcastW = (MODE & 16) != 0;
-  constexpr int NWV = kBcastW ? (KP + 15) / 16 : 1;
-  float wv[NWV];
-  if constexpr (kBcastW) {
-#pragma unroll
-    for (int k = 0; k < NWV; ++k) {
-      const int j = 16 * k + (lane & 15);
-      wv[k] = j < KP ? wl[h][j < KP ? j : 0] : 0.f;
-    }
-  }
-  V x[KH];
-  V xp[PF > 0 ? PF : 1];
-  {
-    int Kw = K;
-    asm volatile("" : "+s"(Kw));
-    const int nb = win_bytes(blockIdx.x);
-    const char* rp = reinterpret_cast<const char*>(X + static_cast<int64_t>(blockIdx.x) * WC) + r0 * row_bytes;
-#pragma unroll
-    for (int i = 0; i < KH; ++i) {
-      asm volatile("" : "+s"(rp));
-      x[i] = win_load<VEC>(
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(rp), 0, r0 + i < Kw ? nb : 0, 0x00020000), voff);
-      rp += row_bytes;
-    }
-  }
-  const auto chain = [&](V& a, bool first) {
-    if constexpr (kBcastW) {
-      static_assert(VEC == 1 && KH % 16 == 0, "broadcast weights: one column per lane, 16-row groups");
-      // the first turn starts from -0.0: fl32(-0.0 + p) is p, bit for bit
-      float ac = first ? -0.0f : a[0];
-      float tc = mul_row_bcast<0>(wv[0], x[0][0]);
-      float xs[KH];
-#pragma unroll
-      for (int i = 0; i < KH; ++i) xs[i] = x[i][0];
-      static_for<KH / 8>([&](auto bc) {
-        constexpr int b = decltype(bc)::value;
-        constexpr bool last = b == KH / 8 - 1;
-        chain8_row_bcast<b % 2, last>(ac, tc, wv[b / 2], wv[last ? b / 2 : (b + 1) / 2], xs + 8 * b);
-      });
-      a[0] = ac;
-      return;
-    }
-    int wo = h * KP;  // opaque: the weights are re-read per window, not held in registers
-    asm volatile("" : "+v"(wo));
-    const float* wp = &wl[0][0] + wo;
-#pragma unroll
-    for (int q = 0; q < KP / 4; ++q) {
-      const f32x4 w4 = *reinterpret_cast<const f32x4*>(wp + 4 * q);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = 4 * q + j;
-        if (i >= KH) continue;
-        if (first && i == 0) {
-          a = x[0] * w4[0];
-        } else {
-          const V t = x[i] * w4[j];
-          a = a + t;
-        }
-      }
-    }
-  };
-  for (int64_t w = blockIdx.x; w < nwin; w += G) {
-    int Kw = K;
-    asm volatile("" : "+s"(Kw));
-    const int64_t c0 = w * WC;
-    const int64_t cl = c0 + lane * VEC;
-    const int nbn = win_bytes(w + G);
-    const char* rp = reinterpret_cast<const char*>(X + (w + G) * WC) + r0 * row_bytes;
-    stamp(0);
-    if constexpr (PF > 0) {
-      // this window's rows (reloaded in the last window's squares) first: a
-      // pre-existing wait the compiler's waitcnt pass accounts for, so the
-      // chain's uses of x[] need no wait on the prefetches issued below (it
-      // otherwise entered the turn loop with vmcnt(0): every wave waited for
-      // its prefetched rows of the NEXT window before its turn)
-      __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
-      stamp(1);
-#pragma unroll
-      for (int i = 0; i < PF; ++i) {
-        asm volatile("" : "+s"(rp));
-        xp[i] = win_load<VEC>(
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(rp), 0, r0 + i < Kw ? nbn : 0, 0x00020000), voff);
-        rp += row_bytes;
-      }
-    }
-    if constexpr (LE > 0) {
-      // the last window's LDS rows have been read out (their ds_reads done)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      typedef __attribute__((address_space(3))) void* lds_ptr_t;
-#pragma unroll
-      for (int i = 0; i < LE; ++i) {
-        asm volatile("" : "+s"(rp));
-        const __amdgpu_buffer_rsrc_t r =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(rp), 0, r0 + PF + i < Kw ? nbn : 0, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)&rowl[h][i][0], 4, lane * 4, 0, 0, 2);
-        rp += row_bytes;
-      }
-    }
-    const bool ragged = c0 + WC > P;
-    if (ragged) {
-#pragma unroll
-      for (int i = 0; i < KH; ++i) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-          if (cl + v >= P) x[i][v] = 0.f;
-      }
-    }
-    V a;
-    if constexpr ((MODE & 1) != 0) {  // probe: no chain
-      a = x[0];
-    } else
-    for (int st = 0; st < ns; ++st) {  // the chain, wave by wave in row order
-      if (h == st) {
-        stamp(2);
-        if (st > 0) a = xa[lane];
-        chain(a, st == 0);
-        xa[lane] = a;
-        stamp(3);
-        if (st == ns - 1) {
-          if (!ragged) {
-            __builtin_nontemporal_store(static_cast<typename WinVec<VEC>::TA>(a),
-                                        reinterpret_cast<typename WinVec<VEC>::TA*>(out + cl));
-          } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v)
-              if (cl + v < P) out[cl + v] = a[v];
-          }
-        }
-      }
-      __syncthreads();
-    }
-    if constexpr ((MODE & 1) == 0) {
-      if (h != ns - 1) a = xa[lane];
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      double p[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = 8 * b + j;
-        p[j] = 0.0;
-        if (i < KH) {
-          if constexpr ((MODE & 2) == 0) p[j] = win_sq<VEC>(x[i] - a);
-          if (i < PF) {
-            x[i] = xp[i < PF ? i : 0];
-          } else if (i < PF + LE) {
-            x[i][0] = rowl[h][i - PF < LE ? i - PF : 0][lane];
-          } else {
-            asm volatile("" : "+s"(rp));
-            x[i] = win_load<VEC>(
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(rp), 0, r0 + i < Kw ? nbn : 0, 0x00020000), voff);
-            rp += row_bytes;
-          }
-        }
-      }
-      acc[64 * b] += win_fold_batch(p, upper);
-    }
-    stamp(4);
-    __syncthreads();  // xa is read by every wave before the next window's chain rewrites it
-    stamp(5);
-    ++wi;
-  }
-  const int row_in = win_batch_row(lane);
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const double s = win_row_sum(acc[64 * b]);
-    const int row = 8 * b + row_in;
-    if ((lane & 7) == 0 && row < KH && r0 + row < K) partials[static_cast<int64_t>(r0 + row) * G + blockIdx.x] = s;
-  }
-}
-
-// workgroups of the split window launch: the resident ones (ceil(K / KH)
-// waves each) rounded down to a power of two per CU (split_per_cu), at most
-// one per window
-template <int KH, int VEC, int NSMAX, int PF = 0, int LE = 0, int MODE = 0>
-int launch_fused_winn(const FusedCall& c, int blocks_per_cu) {
-  const int64_t K = c.K;
-  if (K > NSMAX * KH) return set_error(FEDAVG_EMODE, "%s: this split window kernel covers K <= %d", c.what, NSMAX * KH);
-  const int ns = static_cast<int>((K + KH - 1) / KH);
-  const int64_t nwin = (c.P + 64 * VEC - 1) / (64 * VEC);
-  const auto kern = reduce_sqdist_winn_kernel<KH, VEC, NSMAX, PF, LE, MODE>;
-  const int64_t grid = persistent_grid(blocks_per_cu > 0 ? blocks_per_cu : split_per_cu(resident_blocks(kern, 64 * ns)),
-                                       cu_count(), nwin);
-  if (grid <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", c.what);
-  return fused_launch(c, grid, (MODE & 8) != 0 ? winn_stamp_elems(NSMAX) : 0, [&] {
-    hipLaunchKernelGGL((reduce_sqdist_winn_kernel<KH, VEC, NSMAX, PF, LE, MODE>), dim3(static_cast<unsigned>(grid)),
-                       dim3(static_cast<unsigned>(64 * ns)), 0, c.s, c.clients, static_cast<int>(K), c.ld, c.P, nwin,
-                       c.weights, c.out, c.partials);
-  });
-}
-#endif  // FEDAVG_TUNING
-
-// ---------------------------------------------------------------------------
-// Split-row windows with point-to-point hand-offs (round 6).  The same work as
-// reduce_sqdist_winn_kernel<64, 1, NSMAX, PF> -- wave h holds rows 64h ..
-// 64h + 63 of a 64-column window, the chain runs wave by wave in row order,
-// then every wave squares its rows against the average and reloads them from
-// the next window -- without a workgroup barrier anywhere in the window loop:
+// Split-row windows with point-to-point hand-offs (round 6) for 160-1024 rows
+// (fused_plan).  The register-staged tiles ran 500 x 11.2M at 5.4 ms (52 % of
+// HBM peak; a tile's K-step chain runs on 32 lanes only).  Here a workgroup of
+// ns = ceil(K / 64) <= NSMAX waves owns a window of 64 columns; wave h holds
+// rows 64h .. 64h + 63 in registers.  The chain keeps the reference's order:
+// it runs wave by wave in row order, each wave handing its fp32 partial over
+// LDS to the next, the last one storing the average; then every wave squares
+// its rows against the average and reloads them from the next window.  Rows
+// past K load through an empty descriptor (+0) with weight -0.0, which leaves
+// every chain value unchanged.  The first PF rows of the next window are
+// loaded into spare registers as the window starts, so HBM has work while the
+// chain runs; after squaring row i < PF the wave takes the prefetched row
+// instead of reloading it.  No workgroup barrier anywhere in the window loop
+// (round 5's form had one per turn; retired, its figures: profiles/r05/winn/):
 //   * wave h > 0 starts its turn when wave h - 1's partial for this window is
 //     in LDS (part[h - 1], flag[h - 1] = the window's sequence number), wave
 //     ns - 1 publishes the average (avg, flag[NSMAX]); every other wave waits
@@ -1422,9 +1063,9 @@ int launch_fused_winn(const FusedCall& c, int blocks_per_cu) {
 //   * the squares and reloads run at a priority by wave (waves 0-3 first), so
 //     the first waves' rows of the next window arrive first and their turns
 //     start while the later waves' rows are still streaming.
-// The timeline probe (winn, MODE 8) measured the barrier form's window as
-// chain (14.4k cycles with the broadcast weights) + reload phase (9-12k)
-// end to end: every turn waited at a barrier for the slowest wave's reloads.
+// The timeline build of the retired barrier form measured its window as chain
+// (14.4k cycles with the broadcast weights) + reload phase (9-12k) end to end:
+// every turn waited at a barrier for the slowest wave's reloads.
 // Hand-off safety: wave h writes part[h] for window s + 1 only after its
 // squares of window s, i.e. after the average of s, i.e. after wave h + 1
 // read part[h] for s; wave ns - 1 writes avg for s + 1 only after every other
@@ -1432,10 +1073,11 @@ int launch_fused_winn(const FusedCall& c, int blocks_per_cu) {
 // the same windows, so every flag a wave waits for is set; the polls are
 // bounded (kHandoffSpinMax) so a broken protocol ends in wrong sums (the parity
 // tests), never in a hung grid.  Weights by row broadcast (chain8_row_bcast).
-// MODE 8: the timeline stamps of the winn kernel.  Probes: MODE 1 polls
-// with s_sleep 1 (the first form), 2 keeps every priority at 0, 4 keeps the
-// turn at the squares' priority, 16 runs every wave's squares at priority 2, 32 by
-// halves (waves 0-7 at 2, the rest at 1).
+// MODE 8 (probe), the timeline build: lane 0 of every wave of the first
+// kStampBlocks workgroups stores s_memtime at four points of its first
+// kStampWins windows (0 window top, 2 turn starts, 3 partial handed on,
+// 4 squared), after the K x G partials (winn_stamp_elems;
+// scripts/winn_timeline.py reads them).
 // ---------------------------------------------------------------------------
 // (kHandoffSpinMax: window.hpp, shared with the zero-copy form)
 
@@ -1484,9 +1126,8 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   handoff_weights(wv, W, r0, lane, K);
   __syncthreads();
   // (handoff_wait / handoff_publish / handoff_weights: window.hpp, one text for both forms)
-  const auto wait_flag = [&](int idx, int seq) __attribute__((always_inline)) { handoff_wait<MODE>(flag, idx, seq); };
+  const auto wait_flag = [&](int idx, int seq) __attribute__((always_inline)) { handoff_wait(flag, idx, seq); };
   const auto publish = [&](int idx, int seq) __attribute__((always_inline)) { handoff_publish(flag, idx, seq); };
-  constexpr bool kPrio = (MODE & 2) == 0, kTurnPrio = kPrio && (MODE & 4) == 0;
   float x[KH];
   float xp[PF];
   {
@@ -1535,7 +1176,7 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
       a = part[h - 1][lane];
     }
     stamp(2);
-    if constexpr (kTurnPrio) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     {
       float tc = mul_row_bcast<0>(wv[0], x[0]);
       static_for<KH / 8>([&](auto bc) {
@@ -1558,26 +1199,17 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
     }
     stamp(3);
     if (h < ns - 1) {
-      if constexpr (kTurnPrio) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       wait_flag(NSMAX, seq);
       a = avg[lane];
     }
     // the squares, the next window's rows reloaded behind them: waves 0-3 first
-    if constexpr ((MODE & 16) != 0) {  // probe: every wave's squares at priority 2
+    if (h < 4)
       __builtin_amdgcn_s_setprio(2);
-    } else if constexpr ((MODE & 32) != 0) {  // probe: halves (waves 0-7 first)
-      if (h < 8)
-        __builtin_amdgcn_s_setprio(2);
-      else
-        __builtin_amdgcn_s_setprio(1);
-    } else if constexpr (kPrio) {
-      if (h < 4)
-        __builtin_amdgcn_s_setprio(2);
-      else if (h < 8)
-        __builtin_amdgcn_s_setprio(1);
-      else
-        __builtin_amdgcn_s_setprio(0);
-    }
+    else if (h < 8)
+      __builtin_amdgcn_s_setprio(1);
+    else
+      __builtin_amdgcn_s_setprio(0);
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       double p[8];
@@ -1638,166 +1270,6 @@ int launch_fused_winf(const FusedCall& c) {
   });
 }
 
-#ifdef FEDAVG_TUNING
-// ---------------------------------------------------------------------------
-// Probe (round 3): split-row windows.  With K = 100 rows in one wave the
-// window kernel above keeps more loads than the hardware's 63-load vmcnt cap
-// can hold, so each window's reloads go out in two generations and the wave
-// sits with nothing in flight between its last row's arrival and the first
-// reload.  Here a workgroup of TWO waves owns a window: wave h holds rows
-// h*KH .. h*KH + KH - 1 (KH <= 63: every reload of a window is in flight at
-// once; KH x VEC registers, so three waves per SIMD at KH 50, VEC 2).  The
-// chain stays the reference's sequential order: wave 0 runs rows 0..KH-1,
-// hands its fp32 partial over LDS, wave 1 continues with rows KH..2KH-1 and
-// returns the final average (two barriers per window).  Each wave squares and
-// reloads its own rows; row sums as in reduce_sqdist_win_kernel, one partial
-// per (row, workgroup).
-// ---------------------------------------------------------------------------
-template <int KH, int VEC>
-__global__ __launch_bounds__(128, win_min_waves(KH, VEC)) void reduce_sqdist_win2_kernel(
-    const float* __restrict__ X, int K, int64_t ld, int64_t P, int64_t nwin, const float* __restrict__ W,
-    float* __restrict__ out, double* __restrict__ partials) {
-  typedef typename WinVec<VEC>::T V;
-  constexpr int WC = 64 * VEC;
-  constexpr int NB = (KH + 7) / 8;
-  constexpr int KP = (KH + 3) & ~3;
-  const int lane = threadIdx.x & 63;
-  const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r0 = h * KH;
-  const int64_t G = gridDim.x;
-  const uint32_t voff = static_cast<uint32_t>(lane) * VEC * 4;
-  const int64_t P4 = (P + 3) & ~static_cast<int64_t>(3);
-  const int64_t row_bytes = ld * 4;
-  const bool upper = (lane & 8) != 0;
-  const auto win_bytes = [&](int64_t w) -> int {
-    if (w >= nwin) return 0;
-    const int64_t n = P4 - w * WC;
-    return static_cast<int>((n < WC ? n : WC) * 4);
-  };
-  __shared__ __attribute__((aligned(16))) float wl[2][KP];
-  __shared__ double accl[2][NB][64];
-  __shared__ __attribute__((aligned(16))) V xa[64];
-  for (int i = threadIdx.x; i < 2 * KP; i += 128) {
-    const int hh = i / KP, j = i % KP, row = hh * KH + j;
-    wl[hh][j] = (j < KH && row < K) ? W[row] : -0.0f;
-  }
-  double* acc = &accl[h][0][lane];
-#pragma unroll
-  for (int b = 0; b < NB; ++b) acc[64 * b] = 0.0;
-  __syncthreads();
-  V x[KH];
-  {
-    int Kw = K;
-    asm volatile("" : "+s"(Kw));
-    const int nb = win_bytes(blockIdx.x);
-    const char* rp = reinterpret_cast<const char*>(X + static_cast<int64_t>(blockIdx.x) * WC) + r0 * row_bytes;
-#pragma unroll
-    for (int i = 0; i < KH; ++i) {
-      asm volatile("" : "+s"(rp));
-      x[i] = win_load<VEC>(
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(rp), 0, r0 + i < Kw ? nb : 0, 0x00020000), voff);
-      rp += row_bytes;
-    }
-  }
-  // a = a + fl32(x_i w_i) over this wave's rows (first: a = fl32(x_0 w_0) first)
-  const auto chain = [&](V& a, bool first) {
-    int wo = h * KP;  // opaque: the weights are re-read per window, not held in registers
-    asm volatile("" : "+v"(wo));
-    const float* wp = &wl[0][0] + wo;
-#pragma unroll
-    for (int q = 0; q < KP / 4; ++q) {
-      const f32x4 w4 = *reinterpret_cast<const f32x4*>(wp + 4 * q);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = 4 * q + j;
-        if (i >= KH) continue;
-        if (first && i == 0) {
-          a = x[0] * w4[0];
-        } else {
-          const V t = x[i] * w4[j];
-          a = a + t;
-        }
-      }
-    }
-  };
-  for (int64_t w = blockIdx.x; w < nwin; w += G) {
-    int Kw = K;
-    asm volatile("" : "+s"(Kw));
-    const int64_t c0 = w * WC;
-    const int64_t cl = c0 + lane * VEC;
-    const int nbn = win_bytes(w + G);
-    const char* rp = reinterpret_cast<const char*>(X + (w + G) * WC) + r0 * row_bytes;
-    const bool ragged = c0 + WC > P;
-    if (ragged) {
-#pragma unroll
-      for (int i = 0; i < KH; ++i) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-          if (cl + v >= P) x[i][v] = 0.f;
-      }
-    }
-    V a;
-    if (h == 0) {
-      chain(a, true);
-      xa[lane] = a;
-    }
-    __syncthreads();
-    if (h == 1) {
-      a = xa[lane];
-      chain(a, false);
-      xa[lane] = a;
-      if (!ragged) {
-        __builtin_nontemporal_store(static_cast<typename WinVec<VEC>::TA>(a), reinterpret_cast<typename WinVec<VEC>::TA*>(out + cl));
-      } else {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-          if (cl + v < P) out[cl + v] = a[v];
-      }
-    }
-    __syncthreads();
-    if (h == 0) a = xa[lane];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      double p[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = 8 * b + j;
-        p[j] = 0.0;
-        if (i < KH) {
-          p[j] = win_sq<VEC>(x[i] - a);
-          asm volatile("" : "+s"(rp));
-          x[i] = win_load<VEC>(
-              __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(rp), 0, r0 + i < Kw ? nbn : 0, 0x00020000), voff);
-          rp += row_bytes;
-        }
-      }
-      acc[64 * b] += win_fold_batch(p, upper);
-    }
-  }
-  const int row_in = win_batch_row(lane);
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const double s = win_row_sum(acc[64 * b]);
-    const int row = 8 * b + row_in;
-    if ((lane & 7) == 0 && row < KH && r0 + row < K) partials[static_cast<int64_t>(r0 + row) * G + blockIdx.x] = s;
-  }
-}
-
-template <int KH, int VEC>
-int launch_fused_win2(const FusedCall& c, int blocks_per_cu) {
-  if (c.K > 2 * KH) return set_error(FEDAVG_EMODE, "%s: this split window kernel covers K <= %d", c.what, 2 * KH);
-  const auto kern = reduce_sqdist_win2_kernel<KH, VEC>;
-  const int64_t nwin = (c.P + 64 * VEC - 1) / (64 * VEC);
-  const int64_t grid = persistent_grid(blocks_per_cu > 0 ? blocks_per_cu : resident_blocks(kern, 128) / cu_count(),
-                                       cu_count(), nwin);
-  if (grid <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", c.what);
-  return fused_launch(c, grid, 0, [&] {
-    hipLaunchKernelGGL((reduce_sqdist_win2_kernel<KH, VEC>), dim3(static_cast<unsigned>(grid)), dim3(128), 0, c.s,
-                       c.clients, static_cast<int>(c.K), c.ld, c.P, nwin, c.weights, c.out, c.partials);
-  });
-}
-#endif  // FEDAVG_TUNING
-
 // Which one-read kernel serves K rows (production), from interleaved
 // measurements of every candidate against the others and the two passes on
 // ~4 GB of rows (scripts/fused_probe.py, profiles/r03/fused_rule/*.jsonl and
@@ -1832,23 +1304,20 @@ int launch_fused_win2(const FusedCall& c, int blocks_per_cu) {
 // Beyond 1024 rows the two passes (a workgroup holds at most 16 x 64 rows).
 constexpr int kFusedNone = 0, kFusedLds = 1, kFusedRs = 2, kFusedWin = 3, kFusedWinn = 4;
 constexpr int64_t kFusedRowsMaxK = 1024;
-// split-row windows (reduce_sqdist_winn_kernel, 64 rows per wave, 64 columns)
-// from 369 rows (round 5, scripts/fused_probe.py, profiles/r05/winn/, ms:
+// split-row windows (64 rows per wave, 64 columns) from 369 rows (round 5's
+// barrier form, since retired; scripts/fused_probe.py, profiles/r05/winn/, ms:
 // 384 x 5M 1.455 vs 1.494 register-staged; 448 x 5M 1.60 vs 2.30; 500 x
 // 11.2M 3.71 vs 5.37; 500 x 1.4M 0.54 vs 0.72; 512 x 5M 1.69 vs 2.59; but
 // 352 x 5M 1.42 vs 1.36 and 300 x 5M 1.10 vs 1.05), up to 8 waves per
 // workgroup to 512 rows, 16 beyond (640 x 3M 1.77 vs 2.46 for the two
 // passes; 1000 x 12.5M 9.99 vs 15.05; 520 x 5M 2.71 vs 3.34)
 constexpr int64_t kFusedWinnMinK = 369;
-// (round 5: the barrier form with 8 prefetched rows, reduce_sqdist_winn_kernel:
-// probe library only since)
 // Round 6: the split windows run reduce_sqdist_winf_kernel (point-to-point
 // hand-offs, broadcast weights) with 8 prefetched rows at <= 8 waves and 16
 // beyond (profiles/r06/winf/, ms, barrier form vs winf: 1000 x 12.5M 9.06 vs
 // 8.02; 999 x 10M+3 7.75 vs 6.44; 600 x 10M 5.13 vs 4.28; 513 x 3M 1.48 vs
 // 1.26; 500 x 11.2M 3.66 vs 3.57; 400 x 10M 2.73 vs 2.60; 370 x 5M 1.25 vs
-// 1.18; every output bit-identical).  The barrier form is a variant of the
-// probe library (fedavg_reduce_sqdist_f32_variant), never a production plan.
+// 1.18; every output bit-identical).
 // (kSplitForms, window.hpp: for_split gives <8, PF 8> or <16, PF 16>)
 // With the prefetch the split windows also beat the register-staged tiles at
 // 161-256 and 289-368 rows on long rows (profiles/r05/prefetch/, ms, tiles vs
@@ -1911,8 +1380,8 @@ struct SplitInstance {  // split-row windows, hand-off form
 };
 template <int S>
 struct LdsInstance {  // LDS-DMA tiles, K <= 128: one row per thread in the squares (RM 1)
-  static int64_t parts(int64_t K, int64_t P) { return fused_grid<S, false, 0, false, 1>(K, P, 0); }
-  static int launch(const FusedCall& c) { return launch_fused_rm<S, false, 0, false, 1>(c, 0); }
+  static int64_t parts(int64_t K, int64_t P) { return fused_grid<S, false, 0, 1>(K, P, 0); }
+  static int launch(const FusedCall& c) { return launch_fused_rm<S, false, 0, 1>(c, 0); }
 };
 template <int S, int SLOTS>
 struct RsInstance {  // register-staged tiles
@@ -2323,7 +1792,6 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
 #define FEDAVG_FUSED_CASE(C, DBUF, RWS)                                                                           \
   case C + (DBUF ? 1000 : 0) + (RWS ? 10000 : 0):                                                                \
     return launch_fused<C, DBUF, RWS>(call, blocks_per_cu);
-    FEDAVG_FUSED_CASE(32, false, 0)
     FEDAVG_FUSED_CASE(64, false, 0)
     FEDAVG_FUSED_CASE(128, false, 0)
     FEDAVG_FUSED_CASE(256, false, 0)
@@ -2332,32 +1800,15 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     FEDAVG_FUSED_CASE(256, true, 0)
     FEDAVG_FUSED_CASE(64, false, 32)
     FEDAVG_FUSED_CASE(128, false, 32)
-    FEDAVG_FUSED_CASE(256, false, 32)
     FEDAVG_FUSED_CASE(128, true, 32)
 #undef FEDAVG_FUSED_CASE
-    // + 100000: the tile loads alone (no average, no sums: a traffic probe, wrong results)
-    case 100064: return launch_fused<64, false, 0, true>(call, blocks_per_cu);
-    case 100128: return launch_fused<128, false, 0, true>(call, blocks_per_cu);
-    case 101064: return launch_fused<64, true, 0, true>(call, blocks_per_cu);
-    // register-staged tiles (reduce_sqdist_rs_kernel): 200000 + S; 210000 + S
-    // with the slots of K = 100 at 128 / 256 columns; + 100000: loads only,
-    // + 200000: loads + LDS writes (traffic probes, wrong results)
-#define FEDAVG_RS_CASE(CODE, C, SL, MODE)                                                                         \
-  case CODE:                                                                                                     \
-    return launch_fused_rs<C, SL, MODE>(call, blocks_per_cu);
-    FEDAVG_RS_CASE(200032, 32, 10, 0)
-    FEDAVG_RS_CASE(200064, 64, 8, 0)
-    FEDAVG_RS_CASE(200128, 128, 8, 0)
-    FEDAVG_RS_CASE(200256, 256, 8, 0)
-    FEDAVG_RS_CASE(210128, 128, 13, 0)
-    FEDAVG_RS_CASE(210256, 256, 25, 0)
-    FEDAVG_RS_CASE(300064, 64, 8, 1)
-    FEDAVG_RS_CASE(310128, 128, 13, 1)
-    FEDAVG_RS_CASE(310256, 256, 25, 1)
-    FEDAVG_RS_CASE(400064, 64, 8, 2)
-    FEDAVG_RS_CASE(410128, 128, 13, 2)
-    FEDAVG_RS_CASE(410256, 256, 25, 2)
-#undef FEDAVG_RS_CASE
+    // register-staged tiles (reduce_sqdist_rs_kernel): 200000 + S; + 100000:
+    // loads only (a traffic probe, wrong results); 310128: the slots of K = 100
+    // at 128 columns
+    case 200032: return launch_fused_rs<32, 10>(call, blocks_per_cu);
+    case 200064: return launch_fused_rs<64, 8>(call, blocks_per_cu);
+    case 300064: return launch_fused_rs<64, 8, 1>(call, blocks_per_cu);
+    case 310128: return launch_fused_rs<128, 13, 1>(call, blocks_per_cu);
     // + 1000000: the same over a TILED buffer [ceil(P / S)][K][S] (probe: is the
     // row-major tile walk limited by the spread of its K row segments?)
     case 1200064: return launch_fused_rs<64, 8, 0, 1>(call, blocks_per_cu);
@@ -2368,49 +1819,20 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     case 2300064: return launch_fused_rs<64, 8, 1, 2>(call, blocks_per_cu);
     case 4200064: return launch_fused_rs<64, 8, 0, 4>(call, blocks_per_cu);
     case 4300064: return launch_fused_rs<64, 8, 1, 4>(call, blocks_per_cu);
-    case 4200032: return launch_fused_rs<32, 10, 0, 4>(call, blocks_per_cu);
-    // + 10000000: two tiles in flight per workgroup; 5300064 / 5310128: loads
-    // only, no LDS (occupancy from registers alone)
+    // + 10000000: two tiles in flight per workgroup
     case 10200064: return launch_fused_rs<64, 8, 0, 0, 2>(call, blocks_per_cu);
-    case 10200032: return launch_fused_rs<32, 10, 0, 0, 2>(call, blocks_per_cu);
-    case 10200128: return launch_fused_rs<128, 8, 0, 0, 2>(call, blocks_per_cu);
-    case 10300064: return launch_fused_rs<64, 8, 1, 0, 2>(call, blocks_per_cu);
-    // many clients: S = 32 with 16 / 32 slots per thread (K <= 512 / 1024), S = 64 with 16 (K <= 256)
+    // many clients: 16 slots per thread at S = 32 (K <= 512) and S = 64 (K <= 256)
     case 200032 + 1600000: return launch_fused_rs<32, 16>(call, blocks_per_cu);
-    case 200032 + 3200000: return launch_fused_rs<32, 32>(call, blocks_per_cu);
     case 200064 + 1600000: return launch_fused_rs<64, 16>(call, blocks_per_cu);
-    case 5300064: return launch_fused_rs<64, 8, 3>(call, blocks_per_cu);
-    // wide tiles with 2-3 tiles in flight (registers) beside the one in LDS:
-    // 20000000 + DEPTH * 1000000 + S (K = 100: 13 slots at 128, 25 at 256)
-    case 22000128: return launch_fused_rs<128, 13, 0, 0, 2>(call, blocks_per_cu);
-    case 23000128: return launch_fused_rs<128, 13, 0, 0, 3>(call, blocks_per_cu);
-    case 22000256: return launch_fused_rs<256, 25, 0, 0, 2>(call, blocks_per_cu);
-    case 23000256: return launch_fused_rs<256, 25, 0, 0, 3>(call, blocks_per_cu);
-    case 5310128: return launch_fused_rs<128, 13, 3>(call, blocks_per_cu);
-    case 5310256: return launch_fused_rs<256, 25, 3>(call, blocks_per_cu);
-    case 15300064: return launch_fused_rs<64, 8, 3, 0, 2>(call, blocks_per_cu);
-    // wave-owned windows (reduce_sqdist_win_kernel): 60000000 + MODE *
-    // 1000000 + NW * 10 + VEC at K <= 100; 70000000 + KMAX * 100 + NW * 10 + VEC
-#define FEDAVG_WIN_CASE(VEC, NW, MODE)                                                                            \
-  case 60000000 + MODE * 1000000 + NW * 10 + VEC:                                                                \
-    return launch_fused_win<100, VEC, NW, MODE>(call, blocks_per_cu);
-    FEDAVG_WIN_CASE(2, 4, 1)
-    FEDAVG_WIN_CASE(4, 4, 1)
-    FEDAVG_WIN_CASE(2, 4, 2)
-    FEDAVG_WIN_CASE(2, 4, 8)
-    FEDAVG_WIN_CASE(2, 4, 16)
-    FEDAVG_WIN_CASE(2, 8, 16)
-    FEDAVG_WIN_CASE(2, 8, 0)
-    FEDAVG_WIN_CASE(2, 4, 64)
-    FEDAVG_WIN_CASE(2, 1, 64)
-    FEDAVG_WIN_CASE(2, 2, 64)
-    FEDAVG_WIN_CASE(2, 4, 128)
-    FEDAVG_WIN_CASE(2, 4, 65)  // LDS rows, loads only (round 6 clock attribution)
-    FEDAVG_WIN_CASE(2, 4, 68)  // LDS rows, fp32 squares
-    FEDAVG_WIN_CASE(2, 4, 256)  // broadcast weights (round 6)
-    FEDAVG_WIN_CASE(2, 4, 320)  // LDS rows + broadcast weights (round 6)
-    case 60000000 + 192 * 1000000 + 42:  // LDS rows + 8-row descriptors
-      return launch_fused_win<100, 2, 4, 192>(call, blocks_per_cu);
+    // wave-owned windows (reduce_sqdist_win_kernel): 60000000 + MODE * 1000000
+    // + 42 at K <= 100 (4 waves, VEC 2); 70000000 + KMAX * 100 + 40 + VEC
+#define FEDAVG_WIN_CASE(MODE)                                                                                     \
+  case 60000000 + MODE * 1000000 + 42:                                                                           \
+    return launch_fused_win<100, 2, 4, MODE>(call, blocks_per_cu);
+    FEDAVG_WIN_CASE(64)  // LDS rows: the 81-100 band's production form
+    FEDAVG_WIN_CASE(65)  // LDS rows, loads only (round 6 clock attribution)
+    FEDAVG_WIN_CASE(68)  // LDS rows, fp32 squares
+#undef FEDAVG_WIN_CASE
 #define FEDAVG_WINK_CASE(KMAX, VEC, MINW)                                                                         \
   case 70000000 + KMAX * 100 + 40 + VEC:                                                                         \
     return launch_fused_win<KMAX, VEC, 4, 0, MINW>(call, blocks_per_cu);
@@ -2422,108 +1844,18 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
     FEDAVG_WINK_CASE(16, 4, 4)
     FEDAVG_WINK_CASE(128, 1, 2)
 #undef FEDAVG_WINK_CASE
-#undef FEDAVG_WIN_CASE
-    // split-row windows (reduce_sqdist_win2_kernel): 80000000 + KH * 100 + VEC, K <= 2 KH
-#define FEDAVG_WIN2_CASE(KH, VEC)                                                                                 \
-  case 80000000 + KH * 100 + VEC:                                                                                \
-    return launch_fused_win2<KH, VEC>(call, blocks_per_cu);
-    FEDAVG_WIN2_CASE(50, 2)
-    FEDAVG_WIN2_CASE(40, 2)
-    FEDAVG_WIN2_CASE(32, 2)
-    FEDAVG_WIN2_CASE(25, 4)
-    FEDAVG_WIN2_CASE(60, 2)
-    FEDAVG_WIN2_CASE(50, 4)
-#undef FEDAVG_WIN2_CASE
-    // split-row windows over ceil(K / KH) <= NSMAX waves (reduce_sqdist_winn_kernel):
-    // 85000000 + NSMAX * 10000 + KH * 10 + VEC
-#define FEDAVG_WINN_CASE(KH, VEC, NSMAX)                                                                          \
-  case 85000000 + NSMAX * 10000 + KH * 10 + VEC:                                                                 \
-    return launch_fused_winn<KH, VEC, NSMAX>(call, blocks_per_cu);
-    FEDAVG_WINN_CASE(64, 1, 8)
-    FEDAVG_WINN_CASE(64, 2, 8)
-    FEDAVG_WINN_CASE(32, 2, 16)
-    FEDAVG_WINN_CASE(128, 1, 4)
-    FEDAVG_WINN_CASE(64, 1, 16)
-#undef FEDAVG_WINN_CASE
-    // the same (64 rows per wave, one column per lane) with PF rows of the next
-    // window prefetched: 87000000 + PF * 100 + NSMAX
-#define FEDAVG_WINNPF_CASE(NSMAX, PF)                                                                             \
-  case 87000000 + PF * 100 + NSMAX:                                                                              \
-    return launch_fused_winn<64, 1, NSMAX, PF>(call, blocks_per_cu);
-    FEDAVG_WINNPF_CASE(8, 4)
-    FEDAVG_WINNPF_CASE(8, 8)
-    FEDAVG_WINNPF_CASE(8, 12)
-    FEDAVG_WINNPF_CASE(8, 16)
-    FEDAVG_WINNPF_CASE(16, 2)
-    FEDAVG_WINNPF_CASE(16, 4)
-    FEDAVG_WINNPF_CASE(16, 6)
-    FEDAVG_WINNPF_CASE(16, 8)
-    FEDAVG_WINNPF_CASE(16, 10)
-    FEDAVG_WINNPF_CASE(16, 12)
-    FEDAVG_WINNPF_CASE(16, 16)
-    FEDAVG_WINNPF_CASE(16, 24)
-#undef FEDAVG_WINNPF_CASE
-    // round 6: 128 rows per wave (2 waves per SIMD: 256 registers), half the
-    // chain's hand-offs of the 64-row form and room for a deep prefetch:
-    // 89000000 + PF * 100 + NSMAX
-#define FEDAVG_WINN128_CASE(NSMAX, PF)                                                                            \
-  case 89000000 + PF * 100 + NSMAX:                                                                              \
-    return launch_fused_winn<128, 1, NSMAX, PF>(call, blocks_per_cu);
-    FEDAVG_WINN128_CASE(8, 0)
-    FEDAVG_WINN128_CASE(8, 16)
-    FEDAVG_WINN128_CASE(8, 32)
-    FEDAVG_WINN128_CASE(8, 48)
-    FEDAVG_WINN128_CASE(8, 64)
-    FEDAVG_WINN128_CASE(8, 80)
-#undef FEDAVG_WINN128_CASE
-    // round 6: 64-row split windows with LE rows of the next window in LDS
-    // (LDS-DMA through the chain) and timing modes: 88000000 + MODE * 100000
-    // + LE * 100 + PF (NSMAX 16)
-#define FEDAVG_WINNLE_CASE(PF, LE, MODE)                                                                         \
-  case 88000000 + MODE * 100000 + LE * 100 + PF:                                                                 \
-    return launch_fused_winn<64, 1, 16, PF, LE, MODE>(call, blocks_per_cu);
-    FEDAVG_WINNLE_CASE(8, 0, 1)
-    FEDAVG_WINNLE_CASE(8, 0, 2)
-    FEDAVG_WINNLE_CASE(8, 0, 3)
-    FEDAVG_WINNLE_CASE(8, 8, 0)
-    FEDAVG_WINNLE_CASE(8, 16, 0)
-    FEDAVG_WINNLE_CASE(8, 22, 0)
-    FEDAVG_WINNLE_CASE(0, 22, 0)
-    FEDAVG_WINNLE_CASE(16, 22, 0)
-    FEDAVG_WINNLE_CASE(8, 0, 8)
-    FEDAVG_WINNLE_CASE(0, 0, 8)
-    FEDAVG_WINNLE_CASE(16, 0, 8)
-    FEDAVG_WINNLE_CASE(8, 0, 16)
-    FEDAVG_WINNLE_CASE(8, 0, 24)
-    FEDAVG_WINNLE_CASE(16, 0, 16)
-#undef FEDAVG_WINNLE_CASE
-    // round 6: split-row windows with point-to-point hand-offs
-    // (reduce_sqdist_winf_kernel): 91000000 + MODE * 10000 + PF * 100 + NSMAX
+    // split-row windows with point-to-point hand-offs (reduce_sqdist_winf_kernel):
+    // 91000000 + MODE * 10000 + PF * 100 + NSMAX (MODE 8: the timeline build)
 #define FEDAVG_WINF_CASE(NSMAX, PF, MODE)                                                                        \
   case 91000000 + MODE * 10000 + PF * 100 + NSMAX:                                                              \
     return launch_fused_winf<NSMAX, PF, MODE>(call);
-    FEDAVG_WINF_CASE(16, 8, 0)
-    FEDAVG_WINF_CASE(16, 16, 0)
-    FEDAVG_WINF_CASE(16, 8, 8)
     FEDAVG_WINF_CASE(8, 8, 0)
     FEDAVG_WINF_CASE(8, 16, 0)
-    FEDAVG_WINF_CASE(16, 16, 1)
-    FEDAVG_WINF_CASE(16, 16, 2)
-    FEDAVG_WINF_CASE(16, 16, 4)
-    FEDAVG_WINF_CASE(16, 24, 0)
-    FEDAVG_WINF_CASE(16, 32, 0)
+    FEDAVG_WINF_CASE(16, 8, 0)
+    FEDAVG_WINF_CASE(16, 16, 0)
     FEDAVG_WINF_CASE(16, 16, 8)
-    FEDAVG_WINF_CASE(16, 16, 9)
-    FEDAVG_WINF_CASE(8, 8, 1)
-    FEDAVG_WINF_CASE(8, 8, 2)
-    FEDAVG_WINF_CASE(8, 16, 1)
-    FEDAVG_WINF_CASE(8, 8, 8)
-    FEDAVG_WINF_CASE(16, 16, 16)
-    FEDAVG_WINF_CASE(16, 16, 32)
-    FEDAVG_WINF_CASE(8, 8, 16)
-    FEDAVG_WINF_CASE(8, 8, 32)
 #undef FEDAVG_WINF_CASE
-    default: return set_error(FEDAVG_EMODE, "%s: cols must be 32, 64, 128 or 256 (+1000: double-buffered)", what);
+    default: return set_error(FEDAVG_EMODE, "%s: %d is no variant code (include/fedavg_amd_tuning.h lists them)", what, cols);
   }
 }
 #endif  // FEDAVG_TUNING

@@ -160,10 +160,6 @@ __device__ __forceinline__ float load_cvt(const void* base, int64_t kind, int64_
 // one unit of an fp32 key: FULL units (all kSegSpan columns) take the
 // unconditional 16-B path with U rows per batch; the last unit of a key
 // masks its tail slice element by element
-// STYLE 1: the row reduce's loop shape (reduce_f32x4_buf_kernel): each
-// batch's client addresses read from the table as the batch starts, the
-// batch's loads then consume_batch -- the compiler interleaves loads and
-// products as it does there (probe variants)
 template <int U, int C, bool FULL, int STYLE = 0>
 __device__ __forceinline__ void reduce_raw_unit(const int64_t* __restrict__ P, int K, int64_t c0, int64_t n,
                                                 const float* __restrict__ W, float* __restrict__ o) {
@@ -180,11 +176,12 @@ __device__ __forceinline__ void reduce_raw_unit(const int64_t* __restrict__ P, i
   }
   const int nb = (K - 1) / U;
   int k = 1;
-  if constexpr (FULL && STYLE >= 2) {
-    // STYLE 2/3/4: loads and products interleaved in (row, slice) order with
-    // at most L = 2/4/8 loads of this wave in flight (sched_barrier keeps the
+  static_assert(STYLE == 0 || STYLE == 2, "unit loops: 0 (batches) or 2 (interleaved)");
+  if constexpr (FULL && STYLE == 2) {
+    // STYLE 2: loads and products interleaved in (row, slice) order with at
+    // most L = 2 loads of this wave in flight (sched_barrier keeps the
     // compiler from hoisting the batch's loads into one burst)
-    constexpr int L = STYLE == 2 ? 2 : (STYLE == 3 ? 4 : 8);
+    constexpr int L = 2;
     constexpr int N = U * C;
     for (int b = 0; b < nb; ++b, k += U) {
       __amdgpu_buffer_rsrc_t rr[U];
@@ -205,30 +202,6 @@ __device__ __forceinline__ void reduce_raw_unit(const int64_t* __restrict__ P, i
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-    }
-    for (; k < K; ++k) {
-      const __amdgpu_buffer_rsrc_t rr = unit_rsrc(reinterpret_cast<const float*>(P[k]) + c0);
-      const float w = W[k];
-#pragma unroll
-      for (int s = 0; s < C; ++s) {
-        const f32x4 term = ldb(rr, off[s]) * w;
-        acc[s] = acc[s] + term;
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < C; ++s) *reinterpret_cast<f32x4_a4*>(o + 4 * (threadIdx.x + s * kBlock)) = acc[s];
-    return;
-  }
-  if constexpr (FULL && STYLE == 1) {
-    for (int b = 0; b < nb; ++b, k += U) {
-      f32x4 xs[U][C];
-#pragma unroll
-      for (int r = 0; r < U; ++r) {
-        const __amdgpu_buffer_rsrc_t rr = unit_rsrc(reinterpret_cast<const float*>(P[k + r]) + c0);
-#pragma unroll
-        for (int s = 0; s < C; ++s) xs[r][s] = ldb(rr, off[s]);
-      }
-      consume_batch<U, C>(acc, xs, W, k);
     }
     for (; k < K; ++k) {
       const __amdgpu_buffer_rsrc_t rr = unit_rsrc(reinterpret_cast<const float*>(P[k]) + c0);
@@ -1016,7 +989,7 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   handoff_weights(wv, W, r0, lane, K);
   __syncthreads();
   // (handoff_wait / handoff_publish / handoff_weights: window.hpp, one text for both forms)
-  const auto wait_flag = [&](int idx, int seq) __attribute__((always_inline)) { handoff_wait<MODE>(flag, idx, seq); };
+  const auto wait_flag = [&](int idx, int seq) __attribute__((always_inline)) { handoff_wait(flag, idx, seq); };
   const auto publish = [&](int idx, int seq) __attribute__((always_inline)) { handoff_publish(flag, idx, seq); };
   const auto load_ptrs = [&](const int64_t* P) __attribute__((always_inline)) -> int64_t {
     const gptr<int64_t> q = to_global<int64_t>(P);
@@ -1827,8 +1800,7 @@ int fedavg_client_sqdist_segments_f32_variant(const int64_t* client_ptrs, const 
   if (!glob || !partials || !sumsq || !key_numel || n_keys <= 0 || K <= 0)
     return set_error(FEDAVG_EINVAL, "%s: bad arguments", what);
   const int uc = unroll * 100 + cols;
-  if (uc != 104 && uc != 204 && uc != 404 && uc != 804 && uc != 401 && uc != 801 && uc != 402 && uc != 802 &&
-      uc != 208 && uc != 408)
+  if (uc != 104 && uc != 404 && uc != 804 && uc != 401 && uc != 801 && uc != 402 && uc != 802 && uc != 408)
     return set_error(FEDAVG_EMODE, "%s: unsupported (unroll, cols) = (%d, %d)", what, unroll, cols);
   const int64_t span = static_cast<int64_t>(kBlock) * cols * 4;
   const int64_t need = K * units_of(key_numel, n_keys, span) * (kBlock / 64);
@@ -1851,14 +1823,12 @@ int fedavg_client_sqdist_segments_f32_variant(const int64_t* client_ptrs, const 
                          k, glob, partials, nparts);                                                                   \
       break;
       FEDAVG_SQSEG_CASE(1, 4)
-      FEDAVG_SQSEG_CASE(2, 4)
       FEDAVG_SQSEG_CASE(4, 4)
       FEDAVG_SQSEG_CASE(8, 4)
       FEDAVG_SQSEG_CASE(4, 1)
       FEDAVG_SQSEG_CASE(8, 1)
       FEDAVG_SQSEG_CASE(4, 2)
       FEDAVG_SQSEG_CASE(8, 2)
-      FEDAVG_SQSEG_CASE(2, 8)
       FEDAVG_SQSEG_CASE(4, 8)
 #undef FEDAVG_SQSEG_CASE
     }
@@ -1875,13 +1845,8 @@ int fedavg_reduce_segments_f32_variant(const int64_t* client_ptrs, const int64_t
   const char* what = "fedavg_reduce_segments_f32_variant";
   if (!weights || !out) return set_error(FEDAVG_EINVAL, "%s: null weights/out", what);
   if (!is_device_memory(out)) return set_error(FEDAVG_EINVAL, "%s: out must be device memory", what);
-  // unroll >= 100: STYLE unroll / 100 (1: the row reduce's loop shape; 2-4:
-  // interleaved with 2 / 4 / 8 loads in flight) at unroll % 100
   const int uc = unroll * 100 + cols;
-  if (uc != 408 && uc != 804 && uc != 208 && uc != 404 && uc != 802 && uc != 1602 && uc != 216 && uc != 116 &&
-      uc != 801 && uc != 401 && uc != 1601 && uc != 402 && uc != 10216 && uc != 10404 && uc != 10408 &&
-      uc != 10208 && uc != 10804 && uc != 20216 && uc != 30216 && uc != 40216 && uc != 20404 && uc != 30404 &&
-      uc != 30408 && uc != 40408 && uc != 20401 && uc != 30401 && uc != 20408)
+  if (uc != 408 && uc != 804 && uc != 208 && uc != 404 && uc != 802 && uc != 1602 && uc != 216 && uc != 116)
     return set_error(FEDAVG_EMODE, "%s: unsupported (unroll, cols) = (%d, %d)", what, unroll, cols);
   if (blocks_per_cu < 0) return set_error(FEDAVG_EINVAL, "%s: blocks_per_cu < 0", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1901,25 +1866,6 @@ int fedavg_reduce_segments_f32_variant(const int64_t* client_ptrs, const int64_t
     case 802: launch_reduce_segments<8, 2>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
     case 1602: launch_reduce_segments<16, 2>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
     case 216: launch_reduce_segments<2, 16>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 10216: launch_reduce_segments<2, 16, 1>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 10404: launch_reduce_segments<4, 4, 1>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 10408: launch_reduce_segments<4, 8, 1>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 10208: launch_reduce_segments<2, 8, 1>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 10804: launch_reduce_segments<8, 4, 1>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 20216: launch_reduce_segments<2, 16, 2>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 30216: launch_reduce_segments<2, 16, 3>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 40216: launch_reduce_segments<2, 16, 4>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 20404: launch_reduce_segments<4, 4, 2>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 30404: launch_reduce_segments<4, 4, 3>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 30408: launch_reduce_segments<4, 8, 3>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 40408: launch_reduce_segments<4, 8, 4>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 20408: launch_reduce_segments<4, 8, 2>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 20401: launch_reduce_segments<4, 1, 2>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 30401: launch_reduce_segments<4, 1, 3>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 801: launch_reduce_segments<8, 1>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 401: launch_reduce_segments<4, 1>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 1601: launch_reduce_segments<16, 1>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 402: launch_reduce_segments<4, 2>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
     default: launch_reduce_segments<1, 16>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
   }
   return launch_status(what);

@@ -102,7 +102,7 @@ __device__ __forceinline__ double win_fold_batch(const double (&p)[8], bool uppe
 // lanes (quad_perm / half-mirror DPP); lane 8g of the wave then holds the sum
 // of batch row win_batch_row(8g).  (The loop over the batches with its guarded
 // store is each kernel's own: as one inlined helper it changed the code of
-// all six window kernels.)
+// every window kernel.)
 __device__ __forceinline__ double win_row_sum(double s) {
   s += dpp_move_f64<0xB1, 0xF>(s);   // quad_perm [1,0,3,2]
   s += dpp_move_f64<0x4E, 0xF>(s);   // quad_perm [2,3,0,1]
@@ -116,7 +116,7 @@ __device__ __forceinline__ double win_row_sum(double s) {
 // argument: fedavg_dist.hip), the parts that share with unchanged kernel code
 // (what does not, with the figures: DESIGN.md section 3).
 // ---------------------------------------------------------------------------
-// bound on one wait for a flag: x 16 polls of ~100 clocks (or x s_sleep 1):
+// bound on one wait for a flag: x 16 polls of ~100 clocks:
 // < 50 ms, a window is ~13 us
 constexpr int kHandoffSpinMax = 1 << 16;
 
@@ -125,15 +125,13 @@ constexpr int kHandoffSpinMax = 1 << 16;
 typedef __attribute__((address_space(3))) volatile int lds_flag_t;
 
 // wait until flag[idx] (LDS) holds `seq`; bounded, so a broken protocol ends
-// in wrong sums (the parity tests), never in a hung grid.  MODE 1 (probe):
-// polls with s_sleep 1
-template <int MODE>
+// in wrong sums (the parity tests), never in a hung grid
 __device__ __forceinline__ void handoff_wait(int* flag, int idx, int seq) {
   lds_flag_t* f = (lds_flag_t*)&flag[idx];
   // tight polls (no s_sleep): 600 x 10M 4.20 -> 4.09 ms, 1000 x 12.5M 7.97 -> 7.93
   // (profiles/r06/winf_modes/)
-  for (int it = 0; __builtin_amdgcn_readfirstlane(*f) != seq && it < kHandoffSpinMax * ((MODE & 1) ? 1 : 16); ++it)
-    if constexpr ((MODE & 1) != 0) __builtin_amdgcn_s_sleep(1);
+  for (int it = 0; __builtin_amdgcn_readfirstlane(*f) != seq && it < kHandoffSpinMax * 16; ++it) {
+  }
   asm volatile("" ::: "memory");
 }
 // flag[idx] = seq once the payload's ds_write is done

@@ -1,16 +1,18 @@
-"""Per-wave timeline of the split-row window kernel (probe MODE 8).
+"""Per-wave timeline of the split-row window kernel (the hand-off kernel's
+timeline build, probe MODE 8).
 
-    python scripts/winn_timeline.py [--shapes 1000x12500000 500x11227812] [--codes 88800008 88800016]
+    python scripts/winn_timeline.py [--shapes 1000x12500000 500x11227812] [--codes 91081616]
 
 Lane 0 of every wave of the first 8 workgroups stores s_memtime (shader
-clock) at five points of each of its first 48 windows
-(reduce_sqdist_winn_kernel, fedavg_dist.hip):
+clock) at four points of each of its first 48 windows
+(reduce_sqdist_winf_kernel<16, 16, 8>, fedavg_dist.hip):
   0 top       window loop entry
-  1 arrived   after the wait for the wave's own rows of this window (PF > 0)
-  2 turn      the wave's chain turn starts (after the hand-off barrier)
+  2 turn      the wave's chain turn starts (the partial before it has arrived)
   3 handed    its partial is written to LDS for the next wave
   4 squared   its squares done and the next window's reloads issued
-  5 released  past the end-of-window barrier
+(slots 1 "arrived" and 5 "released" were the retired barrier form's: the wait
+for a wave's own rows and the end-of-window barrier.  They stay zero, and
+summarize() leaves out what it derives from them.)
 One JSON line per (shape, code): cycle budget per window (median over the
 steady-state windows 4..47 of the 8 workgroups) and the kernel time.
 """
@@ -69,7 +71,7 @@ def summarize(st, ns, wins):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="*", default=["1000x12500000", "500x11227812"])
-    ap.add_argument("--codes", nargs="*", type=int, default=[88800008])
+    ap.add_argument("--codes", nargs="*", type=int, default=[91081616])
     ap.add_argument("--nsmax", type=int, default=16)
     ap.add_argument("--out", default=None, help="npz of the raw stamps")
     args = ap.parse_args()
