@@ -9,7 +9,7 @@ import ctypes
 import threading
 from pathlib import Path
 
-from .build import FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH
+from .build import CLIENTVEC_LIB_PATH, FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -134,9 +134,27 @@ SEGVEC_SIGNATURES = {
     "fedavg_device_round_bf16": _SEGVEC_ROUND,
 }
 
+# libfedavg_amd_clientvec.so (include/fedavg_amd_clientvec.h)
+_CLIENTVEC_STATS = (_c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp])
+_CLIENTVEC_TRACK = (_c_int, [_vp, _vp, _vp, ctypes.c_double, _vp])
+CLIENTVEC_SIGNATURES = {
+    "fedavg_clientvec_abi_version": (_c_int, []),
+    "fedavg_clientvec_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_stats_vec_span": (_c_i64, [_c_i64]),
+    "fedavg_client_stats_vec_workspace": (_c_i64, [_c_i64]),
+    "fedavg_client_stats_vec_partials": (_c_i64, [_vp, _c_i64, _c_i64]),
+    "fedavg_client_stats_bf16": _CLIENTVEC_STATS,
+    "fedavg_client_stats_f16": _CLIENTVEC_STATS,
+    "fedavg_client_stats_f64": _CLIENTVEC_STATS,
+    "fedavg_client_track_bf16": _CLIENTVEC_TRACK,
+    "fedavg_client_track_f16": _CLIENTVEC_TRACK,
+    "fedavg_client_track_f64": _CLIENTVEC_TRACK,
+}
+
 ABI_VERSION = 1
 FUSEDVEC_ABI_VERSION = 1
 SEGVEC_ABI_VERSION = 1
+CLIENTVEC_ABI_VERSION = 1
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -159,6 +177,7 @@ _lib = None
 _probe = None
 _fusedvec = None
 _segvec = None
+_clientvec = None
 
 
 def library_path() -> Path:
@@ -281,6 +300,45 @@ def load_segvec() -> ctypes.CDLL:
             raise FedAvgLibraryError(f"ABI version {ver} != expected {SEGVEC_ABI_VERSION}; rebuild the library")
         _segvec = lib
     return _segvec
+
+
+def load_clientvec() -> ctypes.CDLL:
+    """The client-statistics library for bf16 / fp16 / fp64 models
+    (include/fedavg_amd_clientvec.h).  It calls no other library.  No
+    fallback: a missing or stale library raises ``FedAvgLibraryError``."""
+    global _clientvec
+    if _clientvec is not None:
+        return _clientvec
+    with _lock:
+        if _clientvec is not None:
+            return _clientvec
+        if not CLIENTVEC_LIB_PATH.exists():
+            raise FedAvgLibraryError(
+                f"{CLIENTVEC_LIB_PATH} not built: run __graft_entry__.build(); there is no fallback for the "
+                "fused client statistics of bf16 / fp16 / fp64 models")
+        try:
+            lib = ctypes.CDLL(str(CLIENTVEC_LIB_PATH))
+        except OSError as e:
+            raise FedAvgLibraryError(f"{CLIENTVEC_LIB_PATH} does not load: {e}") from e
+        for name, (res, args) in CLIENTVEC_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise FedAvgLibraryError(f"{CLIENTVEC_LIB_PATH} does not export {name}") from e
+            fn.restype = res
+            fn.argtypes = args
+        ver = lib.fedavg_clientvec_abi_version()
+        if ver != CLIENTVEC_ABI_VERSION:
+            raise FedAvgLibraryError(f"ABI version {ver} != expected {CLIENTVEC_ABI_VERSION}; rebuild the library")
+        _clientvec = lib
+    return _clientvec
+
+
+def check_clientvec(rc: int, what: str) -> None:
+    """``check`` for a call into libfedavg_amd_clientvec.so (its own message)."""
+    if rc != 0:
+        msg = load_clientvec().fedavg_clientvec_last_error().decode(errors="replace")
+        raise FedAvgLibraryError(f"{what} failed (rc={rc}): {msg}")
 
 
 def check_segvec(rc: int, what: str) -> None:

@@ -1,5 +1,6 @@
 """Build recipe for libfedavg_amd.so, libfedavg_amd_probe.so,
-libfedavg_amd_fusedvec.so and libfedavg_amd_segvec.so (gfx950 only).
+libfedavg_amd_fusedvec.so, libfedavg_amd_segvec.so and
+libfedavg_amd_clientvec.so (gfx950 only).
 
     python -m mfl_amd.build           # or __graft_entry__.build()
 
@@ -29,6 +30,11 @@ two-pass route.
 group from the clients' own tensors, ``include/fedavg_amd_segvec.h``) is the
 third product library, ``lib/libfedavg_amd_segvec.so``: same flags, no
 ``FEDAVG_TUNING``; it calls no other library, so it links none.
+
+``csrc/fedavg_client_vec.hip`` (the client's per-iteration statistics for
+bf16 / fp16 / fp64 models, ``include/fedavg_amd_clientvec.h``) is the fourth,
+``lib/libfedavg_amd_clientvec.so``: same flags, no ``FEDAVG_TUNING``, no
+other library linked.
 """
 from __future__ import annotations
 
@@ -48,6 +54,7 @@ HIP_SOURCES = [CSRC_DIR / "fedavg_reduce.hip", CSRC_DIR / "fedavg_dist.hip",
 PROBE_SOURCES = [CSRC_DIR / "fedavg_variants.hip"]  # probe library only
 FUSEDVEC_SOURCES = [CSRC_DIR / "fedavg_fused_vec.hip"]  # libfedavg_amd_fusedvec.so only
 SEGVEC_SOURCES = [CSRC_DIR / "fedavg_segments_vec.hip"]  # libfedavg_amd_segvec.so only
+CLIENTVEC_SOURCES = [CSRC_DIR / "fedavg_client_vec.hip"]  # libfedavg_amd_clientvec.so only
 CSRC_HOST = CSRC_DIR / "fedavg_host.cpp"
 CSRC_COMMON = CSRC_DIR / "common.hpp"
 CSRC_WINDOW = CSRC_DIR / "window.hpp"  # what the rows and zero-copy window kernels share
@@ -63,6 +70,7 @@ LIB_PATH = LIB_DIR / "libfedavg_amd.so"
 PROBE_LIB_PATH = LIB_DIR / "libfedavg_amd_probe.so"
 FUSEDVEC_LIB_PATH = LIB_DIR / "libfedavg_amd_fusedvec.so"
 SEGVEC_LIB_PATH = LIB_DIR / "libfedavg_amd_segvec.so"
+CLIENTVEC_LIB_PATH = LIB_DIR / "libfedavg_amd_clientvec.so"
 ARCH = "gfx950"
 
 HIPCC_FLAGS = [
@@ -85,13 +93,14 @@ def hipcc_path() -> str:
 
 
 def sources():
-    return [*HIP_SOURCES, *PROBE_SOURCES, *FUSEDVEC_SOURCES, *SEGVEC_SOURCES, CSRC_HOST, CSRC_COMMON, CSRC_WINDOW,
-            CSRC_STAGING, CSRC_VEC_RULES, INCLUDE / "fedavg_amd.h", INCLUDE / "fedavg_amd_tuning.h",
-            INCLUDE / "fedavg_amd_fusedvec.h", INCLUDE / "fedavg_amd_segvec.h", Path(__file__)]
+    return [*HIP_SOURCES, *PROBE_SOURCES, *FUSEDVEC_SOURCES, *SEGVEC_SOURCES, *CLIENTVEC_SOURCES, CSRC_HOST,
+            CSRC_COMMON, CSRC_WINDOW, CSRC_STAGING, CSRC_VEC_RULES, INCLUDE / "fedavg_amd.h",
+            INCLUDE / "fedavg_amd_tuning.h", INCLUDE / "fedavg_amd_fusedvec.h", INCLUDE / "fedavg_amd_segvec.h",
+            INCLUDE / "fedavg_amd_clientvec.h", Path(__file__)]
 
 
 def up_to_date() -> bool:
-    for lib in (LIB_PATH, PROBE_LIB_PATH, FUSEDVEC_LIB_PATH, SEGVEC_LIB_PATH):
+    for lib in (LIB_PATH, PROBE_LIB_PATH, FUSEDVEC_LIB_PATH, SEGVEC_LIB_PATH, CLIENTVEC_LIB_PATH):
         if not lib.exists():
             return False
         t = lib.stat().st_mtime
@@ -152,8 +161,8 @@ def _link(objs, lib_path, verbose, extra=()):
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Build the product library, the probe library, the fused-vec library
-    and the seg-vec library; returns the product path."""
+    """Build the product library, the probe library, the fused-vec library,
+    the seg-vec library and the client-vec library; returns the product path."""
     if not force and up_to_date():
         return LIB_PATH
     OBJ_DIR.mkdir(parents=True, exist_ok=True)
@@ -178,6 +187,11 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         obj = OBJ_DIR / (src.name + ".o")
         jobs.append((src, obj, []))
         segvec_objs.append(obj)
+    clientvec_objs = []
+    for src in CLIENTVEC_SOURCES:
+        obj = OBJ_DIR / (src.name + ".o")
+        jobs.append((src, obj, []))
+        clientvec_objs.append(obj)
     _compile_all(jobs, verbose)
     _link(objs, LIB_PATH, verbose)
     _link(probe_objs, PROBE_LIB_PATH, verbose)
@@ -185,6 +199,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     _link(fusedvec_objs, FUSEDVEC_LIB_PATH, verbose,
           extra=[f"-L{LIB_DIR}", f"-l:{LIB_PATH.name}", "-Wl,-rpath,$ORIGIN"])
     _link(segvec_objs, SEGVEC_LIB_PATH, verbose)  # calls no other library
+    _link(clientvec_objs, CLIENTVEC_LIB_PATH, verbose)  # calls no other library
     return LIB_PATH
 
 

@@ -16,9 +16,18 @@ The norms are fl32(sqrt()) of fp64 sums of exact squares, i.e. the exactly
 rounded values of what the reference's fp32 ``torch.norm`` approximates; rho
 and beta then follow in the reference's fp32 arithmetic.
 
+The dtype rule: the fused pass takes parameters that are all contiguous, on
+one GPU and all of ONE dtype among fp32, bf16, fp16 and fp64.  bf16, fp16 and
+fp64 models go through ``libfedavg_amd_clientvec.so``
+(``fedavg_client_stats_{bf16,f16,f64}`` / ``fedavg_client_track_{bf16,f16,f64}``):
+snapshots in the model's own type, the difference formed in that type, norms
+``rT(fl32(sqrt()))`` (fp64: ``sqrt()``) and every scalar operation after them
+as ATen does it, in opmath and then rounded once to the type.
+
 ``stats="torch"`` computes the same quantities with the reference's own torch
 expressions on whatever device the parameters are on; it is what CPU
-parameters and models with a non-fp32 parameter get under ``stats="auto"``.
+parameters, models of mixed dtypes and any other dtype get under
+``stats="auto"``.
 
 :func:`client_train` is ``Client.train`` written against this class and
 :func:`patch` binds it to a ``Client`` class (opt in; ``install()`` does not).
@@ -33,15 +42,57 @@ import torch
 
 from . import _lib
 
-ALIGN = 4  # snapshot key offsets are multiples of 4 elements (16 B)
+ALIGN = 4  # fp32 snapshot key offsets are multiples of 4 elements (16 B)
+
+# dtype -> (entry suffix, numpy type of the snapshot's bits); fp32 is the product library's
+_VEC_DTYPES = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float64: "f64"}
+FUSED_DTYPES = (torch.float32, *_VEC_DTYPES)
+_RULE = "contiguous parameters on one GPU, all of one dtype among fp32, bf16, fp16 and fp64"
 
 # rec: one device record of doubles, read back in one D2H
 _W, _G, _STATE, _LOSS, _REC = 0, 4, 8, 12, 16
 
 
 def _fused_ok(params) -> bool:
-    return bool(params) and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in params) and \
-        len({p.device for p in params}) == 1
+    return bool(params) and all(p.is_cuda and p.is_contiguous() for p in params) and \
+        len({p.device for p in params}) == 1 and len({p.dtype for p in params}) == 1 and \
+        params[0].dtype in FUSED_DTYPES
+
+
+def _round_to(x, dtype):
+    """rT(fl32(x)) as a Python float: x rounded to fp32, then to ``dtype``
+    (nearest even both times), as ATen casts an opmath result.  fp64: x."""
+    if dtype == torch.float64:
+        return float(x)
+    with np.errstate(all="ignore"):
+        f = np.float32(x)
+        if dtype == torch.float32:
+            return float(f)
+        if dtype == torch.float16:
+            return float(np.float16(f))
+    if math.isnan(f):
+        return math.nan
+    u = int(f.view(np.uint32))
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000  # bf16: the upper half of the fp32 word
+    return float(np.uint32(u).view(np.float32))
+
+
+def _norm_of(sumsq, dtype):
+    """norm(S) = rT(fl32(sqrt(S))) (fp64: sqrt(S)): the exactly rounded value
+    of what ATen's norm approximates in opmath."""
+    if math.isnan(sumsq):
+        return math.nan
+    return _round_to(math.sqrt(sumsq), dtype)
+
+
+def _guard_bound(n_w, lr_ratio, dtype):
+    """``lr * ratio * norm(last_w)`` (:71): python_float * tensor, the scalar
+    rounded to opmath, the product to the tensor's type."""
+    if dtype == torch.float64:
+        return n_w * lr_ratio
+    with np.errstate(all="ignore"):
+        # the fp64 product of two fp32 values is exact: one rounding to fp32
+        return _round_to(np.float64(n_w) * np.float64(np.float32(lr_ratio)), dtype)
 
 
 class ClientStepStats:
@@ -61,7 +112,7 @@ class ClientStepStats:
             raise ValueError(f"stats must be 'auto', 'hip' or 'torch', not {stats!r}")
         fused = _fused_ok(self.params)
         if stats == "hip" and not fused:
-            raise TypeError("stats='hip' needs contiguous fp32 parameters on one GPU")
+            raise TypeError(f"stats='hip' needs {_RULE}")
         self.mode = "hip" if (fused and stats != "torch") else "torch"
         self.trace = trace
         self.stream = stream
@@ -76,8 +127,18 @@ class ClientStepStats:
 
     # ------------------------------------------------------------------ fused
     def _init_hip(self):
-        self.lib = _lib.load()
         self.device = self.params[0].device
+        self.dtype = dt = self.params[0].dtype
+        es = self.params[0].element_size()
+        if dt == torch.float32:
+            self.lib, self._check = _lib.load(), lambda rc, what: _lib.check(rc, what, self.lib)
+            self._stats_name, self._track_name = "fedavg_client_stats_f32", "fedavg_client_track"
+        else:
+            self.lib, self._check = _lib.load_clientvec(), _lib.check_clientvec
+            self._stats_name = f"fedavg_client_stats_{_VEC_DTYPES[dt]}"
+            self._track_name = f"fedavg_client_track_{_VEC_DTYPES[dt]}"
+        self._stats_fn, self._track_fn = getattr(self.lib, self._stats_name), getattr(self.lib, self._track_name)
+        ALIGN = 16 // es  # snapshot key offsets are multiples of 16 B
         n = len(self.params)
         self._numel = np.array([p.numel() for p in self.params], dtype=np.int64)
         padded = (self._numel + (ALIGN - 1)) // ALIGN * ALIGN
@@ -86,9 +147,13 @@ class ClientStepStats:
         self._ptrs = {"w": np.array([p.data_ptr() for p in self.params], dtype=np.int64),
                       "g": np.zeros(n, dtype=np.int64)}
         with torch.cuda.device(self.device):
-            nparts = int(self.lib.fedavg_client_stats_partials(self._numel.ctypes.data, n))
-            self._ws_bytes = int(self.lib.fedavg_client_stats_workspace(n))
-            self._snap = {k: torch.zeros(max(self.P, ALIGN), dtype=torch.float32, device=self.device) for k in "wg"}
+            if dt == torch.float32:
+                nparts = int(self.lib.fedavg_client_stats_partials(self._numel.ctypes.data, n))
+                self._ws_bytes = int(self.lib.fedavg_client_stats_workspace(n))
+            else:
+                nparts = int(self.lib.fedavg_client_stats_vec_partials(self._numel.ctypes.data, n, es))
+                self._ws_bytes = int(self.lib.fedavg_client_stats_vec_workspace(n))
+            self._snap = {k: torch.zeros(max(self.P, ALIGN), dtype=dt, device=self.device) for k in "wg"}
             self._partials = {k: torch.empty(max(nparts, 1), dtype=torch.float64, device=self.device) for k in "wg"}
             self._host_ws = {k: torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, pin_memory=True) for k in "wg"}
             self._dev_ws = {k: torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, device=self.device)
@@ -108,9 +173,10 @@ class ClientStepStats:
             g = p.grad
             if g is None:
                 raise RuntimeError(f"parameter {j} has no grad (client.py:57 / :69 read every param.grad)")
-            if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.device == self.device
+            if not (g.is_cuda and g.dtype == self.dtype and g.is_contiguous() and g.device == self.device
                     and g.numel() == self._numel[j]):
-                raise TypeError(f"parameter {j}: the fused statistics need a contiguous fp32 grad on {self.device}")
+                raise TypeError(f"parameter {j}: the fused statistics need a contiguous grad of the parameters' "
+                                f"dtype ({self.dtype}) on {self.device}")
             out[j] = g.data_ptr()
         return out
 
@@ -124,13 +190,13 @@ class ClientStepStats:
             ev.synchronize()  # host_ws gets new bytes below (already passed after an iteration's sync)
         self._staged[which] = table
         with torch.cuda.device(self.device):
-            rc = self.lib.fedavg_client_stats_f32(
+            rc = self._stats_fn(
                 ptrs.ctypes.data, self._numel.ctypes.data, self._offset.ctypes.data, len(self.params),
                 self._snap[which].data_ptr(), self.P, has_snap, self._partials[which].data_ptr(),
                 self._partials[which].numel(), self._rec.data_ptr() + 8 * (_W if which == "w" else _G),
                 self._host_ws[which].data_ptr(), self._dev_ws[which].data_ptr(), self._host_ws[which].numel(),
                 st.cuda_stream)
-            _lib.check(rc, "fedavg_client_stats_f32", self.lib)
+            self._check(rc, self._stats_name)
             if ev is None:
                 ev = self._ws_free[which] = torch.cuda.Event()
             ev.record(st)
@@ -184,11 +250,15 @@ class ClientStepStats:
                 self._rec[_LOSS:_LOSS + 1].copy_(loss_tensor.detach().reshape(1))
             rec = self._read_record()
             self.loss = float(rec[_LOSS])
-            n_g = np.float32(math.sqrt(rec[_G + 1])) if not math.isnan(rec[_G + 1]) else np.float32("nan")
-            n_w = np.float32(math.sqrt(rec[_W + 1])) if not math.isnan(rec[_W + 1]) else np.float32("nan")
+            if self.dtype == torch.float32:
+                n_g = np.float32(math.sqrt(rec[_G + 1])) if not math.isnan(rec[_G + 1]) else np.float32("nan")
+                n_w = np.float32(math.sqrt(rec[_W + 1])) if not math.isnan(rec[_W + 1]) else np.float32("nan")
+                with np.errstate(all="ignore"):
+                    bound = np.float32(lr * ratio) * n_w  # python_float * fp32 tensor: the scalar rounded to fp32
+            else:
+                n_g, n_w = _norm_of(float(rec[_G + 1]), self.dtype), _norm_of(float(rec[_W + 1]), self.dtype)
+                bound = _guard_bound(n_w, lr * ratio, self.dtype)
             self.grad_norm, self.weight_norm = float(n_g), float(n_w)
-            with np.errstate(all="ignore"):
-                bound = np.float32(lr * ratio) * n_w  # python_float * fp32 tensor: the scalar rounded to fp32
             trip = bool(rec[_G] > 0 or math.isnan(self.loss) or n_g > bound)
         else:
             with torch.no_grad():
@@ -207,9 +277,9 @@ class ClientStepStats:
             self._pass("w", 1)
             base = self._rec.data_ptr()
             with torch.cuda.device(self.device):
-                rc = self.lib.fedavg_client_track(base + 8 * _STATE, base + 8 * _W, base + 8 * _G,
-                                                  abs(loss - last_loss), self._torch_stream().cuda_stream)
-            _lib.check(rc, "fedavg_client_track", self.lib)
+                rc = self._track_fn(base + 8 * _STATE, base + 8 * _W, base + 8 * _G, abs(loss - last_loss),
+                                    self._torch_stream().cuda_stream)
+            self._check(rc, self._track_name)
         else:
             with torch.no_grad():
                 w = self._flat(False)

@@ -3,19 +3,22 @@ two ways on the same device and tensors:
 
   torch : the reference's own expression sequence (ClientStepStats(stats="torch"):
           torch.cat, isnan().sum(), norms, tensor truth tests) -- the baseline;
-  hip   : the fused passes (fedavg_client_stats_f32 twice + fedavg_client_track)
+  hip   : the fused passes (fedavg_client_stats_f32 twice + fedavg_client_track,
+          or their bf16 / fp16 / fp64 forms of libfedavg_amd_clientvec.so)
           with their one sync.
 
-    python scripts/bench_client_stats.py [--reps 30] [--out profiles/client_stats/NAME.jsonl]
+    python scripts/bench_client_stats.py [--dtype f32|bf16|f16|f64] [--reps 30]
+                                         [--out profiles/client_stats/NAME.jsonl]
 
 Per shape: the median over --reps repetitions (after warm-up) of the hipEvent
 time around after_backward() + after_step(), the host syncs per iteration,
 and for the fused pass alone the median time of one pass (10 back-to-back
 passes between two events, table staging and finalize included) with the
-achieved bytes/s on the algorithmic 12 B per element against 8 TB/s.  A pass
-whose tensors and snapshot (8 B per element) fit the 256 MB Infinity Cache is
-labelled cache-resident; larger models rotate over several parameter sets so
-that every pass reads from HBM.
+achieved bytes/s on the algorithmic bytes per element (read cur, read snap,
+write snap: 12 B for fp32, 6 B for bf16 / fp16, 24 B for fp64) against 8 TB/s.
+A pass whose tensors and snapshot (two elements' bytes per element) fit the
+256 MB Infinity Cache is labelled cache-resident; larger models rotate over
+several parameter sets so that every pass reads from HBM.
 """
 from __future__ import annotations
 
@@ -37,6 +40,7 @@ from model_shapes import CONFIGS  # noqa: E402
 
 PEAK = 8.0e12
 MALL = 256 << 20
+DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "f64": torch.float64}
 
 
 def param_shapes(name):
@@ -54,12 +58,12 @@ SHAPES = {
 }
 
 
-def make_params(shapes, dev, seed):
+def make_params(shapes, dev, seed, dtype=torch.float32):
     g = torch.Generator(device=dev).manual_seed(seed)
     params = []
     for s in shapes:
-        p = torch.nn.Parameter(torch.randn(s, device=dev, generator=g) * 0.05)
-        p.grad = torch.randn(s, device=dev, generator=g) * 1e-3
+        p = torch.nn.Parameter((torch.randn(s, device=dev, generator=g) * 0.05).to(dtype))
+        p.grad = (torch.randn(s, device=dev, generator=g) * 1e-3).to(dtype)
         params.append(p)
     return params
 
@@ -116,8 +120,11 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    dtype = DTYPES[args.dtype]
+    es = torch.empty((), dtype=dtype).element_size()
     assert args.reps >= 20, "medians of at least 20 repetitions"
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -125,31 +132,31 @@ def main():
     for name in args.shapes.split(","):
         shapes = SHAPES[name]()
         P = sum(math.prod(s) for s in shapes)
-        params = make_params(shapes, dev, 0)
+        params = make_params(shapes, dev, 0, dtype)
         t_torch, t_torch_min, _ = time_iteration(mfl_amd.ClientStepStats(params, stats="torch"), params, args.reps,
                                                  args.warmup)
         fused = mfl_amd.ClientStepStats(params, stats="hip")
         t_hip, t_hip_min, syncs = time_iteration(fused, params, args.reps, args.warmup)
-        resident = 8 * P <= MALL
-        n_sets = 1 if 8 * P < (32 << 20) else max(2, math.ceil((512 << 20) / (8 * P)))
+        resident = 2 * es * P <= MALL
+        n_sets = 1 if 2 * es * P < (32 << 20) else max(2, math.ceil((512 << 20) / (2 * es * P)))
         sets = [fused]
         for r in range(1, n_sets):
-            extra = mfl_amd.ClientStepStats(make_params(shapes, dev, r), stats="hip")
+            extra = mfl_amd.ClientStepStats(make_params(shapes, dev, r, dtype), stats="hip")
             extra.begin(1.3)
             sets.append(extra)
         t_pass, t_pass_min = time_pass(sets, args.reps, args.warmup)
         line = {
-            "shape": name, "P": P, "keys": len(shapes), "reps": args.reps,
+            "shape": name, "dtype": args.dtype, "P": P, "keys": len(shapes), "reps": args.reps,
             "torch_us_median": round(t_torch, 2), "torch_us_min": round(t_torch_min, 2),
             # :71 isnan().sum() > 0, isnan(loss), the norm test; :75 item(); :79 and :83 one or two truth tests each
             "torch_host_syncs": "6-8",
             "hip_us_median": round(t_hip, 2), "hip_us_min": round(t_hip_min, 2), "hip_host_syncs": syncs,
             "speedup": round(t_torch / t_hip, 3),
             "pass_us_median": round(t_pass, 2), "pass_us_min": round(t_pass_min, 2),
-            "pass_bytes": 12 * P, "pass_gbps": round(12 * P / (t_pass * 1e-6) / 1e9, 1),
-            "pass_frac_of_8tbps": round(12 * P / (t_pass * 1e-6) / PEAK, 4),
+            "pass_bytes": 3 * es * P, "pass_gbps": round(3 * es * P / (t_pass * 1e-6) / 1e9, 1),
+            "pass_frac_of_8tbps": round(3 * es * P / (t_pass * 1e-6) / PEAK, 4),
             "pass_parameter_sets": n_sets,
-            "memory": ("cache-resident" if n_sets == 1 else f"rotating over {n_sets} sets of {8 * P >> 20} MB"
+            "memory": ("cache-resident" if n_sets == 1 else f"rotating over {n_sets} sets of {2 * es * P >> 20} MB"
                        + (" (one set fits the Infinity Cache)" if resident else "")),
             "device": torch.cuda.get_device_name(0), "torch": torch.__version__,
         }

@@ -1,0 +1,167 @@
+"""The bf16 / fp16 / fp64 client statistics on the CPU.
+
+(a) The dtype oracle (tests/client_stats_vec_oracle.py) is pinned to the
+    reference's own expressions: ClientStepStats(stats="torch") on CPU
+    parameters of each dtype, fed the recorded (w_t, g_t, loss_t) sequences of
+    tests/golden/client cast to the dtype, takes the oracle's guard decisions
+    and ends within 4 units in the last place of T of its rho / beta (one ulp
+    of a norm, ATen's opmath accumulation against the exact sum, passes
+    through at most three roundings).  A fixture whose norm(g) lies within
+    2 ulp of its bound has no well-defined decision and is dropped; the two
+    tripping and at least two non-tripping fixtures must remain.
+(b) Mode selection on CPU tensors, the refusal text of stats="hip", and the
+    host-side rounding helpers against torch's CPU casts.
+"""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import client_stats_oracle as O
+import client_stats_vec_oracle as V
+import mfl_amd
+from mfl_amd import client_stats
+
+CASES = O.client_case_names()
+TRIPPING = ("nan_input_trips", "tiny_weights_trip")
+_replays = {}
+
+
+def _replay(name, key):
+    """(case, w, g, trip, beta, rho, margins) of the oracle, once per (fixture, dtype)."""
+    if (name, key) not in _replays:
+        dt = V.DTYPES[key]
+        case = O.load_client_case(name)
+        w, g = V.cast_sequence(case, dt)
+        margins = []
+        trip, beta, rho = V.replay(w, g, case["loss"], case["meta"]["lr"], case["meta"]["ratio"], dt, margins)
+        _replays[(name, key)] = (case, w, g, trip, beta, rho, margins)
+    return _replays[(name, key)]
+
+
+def _well_defined(name, key):
+    return all(m >= 2.0 for m in _replay(name, key)[6])
+
+
+@pytest.mark.parametrize("key", sorted(V.DTYPES))
+def test_enough_fixtures_have_a_well_defined_guard(key):
+    kept = [n for n in CASES if _well_defined(n, key)]
+    print(f"{key}: kept {kept}; margins {[(n, [round(m, 1) for m in _replay(n, key)[6]]) for n in CASES]}")
+    tripping = [n for n in kept if _replay(n, key)[3] is not None]
+    assert set(TRIPPING) <= set(tripping)
+    assert len(kept) - len(tripping) >= 2
+
+
+def _set(params, flat, grads):
+    off = 0
+    with torch.no_grad():
+        for p in params:
+            n = p.numel()
+            t = flat[off:off + n].view_as(p)
+            if grads:
+                p.grad = t.clone()
+            else:
+                p.copy_(t)
+            off += n
+
+
+@pytest.mark.parametrize("key", sorted(V.DTYPES))
+@pytest.mark.parametrize("name", CASES)
+def test_torch_mode_on_cpu_agrees_with_the_oracle(name, key):
+    dt = V.DTYPES[key]
+    case, w, g, o_trip, o_beta, o_rho, margins = _replay(name, key)
+    if not _well_defined(name, key):
+        # no skip: the fixture is simply not among those this dtype relies on (see the test above)
+        assert min(margins) < 2.0
+        return
+    meta, loss = case["meta"], case["loss"]
+    net = O.build_model(meta["model"]).to(dt)
+    params = list(net.parameters())
+    _set(params, w[0], False)
+    _set(params, g[0], True)
+    stats = mfl_amd.ClientStepStats(params, stats="torch")
+    assert stats.mode == "torch"
+    stats.begin(float(loss[0]))
+    tripped_at = None
+    for t in range(1, len(g)):
+        _set(params, g[t], True)
+        if stats.after_backward(torch.tensor(float(loss[t])), meta["lr"], meta["ratio"]):
+            tripped_at = t - 1
+            break
+        _set(params, w[t], False)
+        stats.after_step(float(loss[t]), float(loss[t - 1]))
+    beta, rho = stats.result()
+    print(f"{name} {key}: trip {tripped_at} oracle {o_trip}; beta {beta!r} oracle {o_beta!r}; rho {rho!r} "
+          f"oracle {o_rho!r}")
+    assert tripped_at == o_trip
+    assert (tripped_at is not None) == meta["tripped"]
+    if tripped_at is not None:
+        return
+    assert V.within_ulps(beta, o_beta, 4, dt), (beta, o_beta)
+    assert V.within_ulps(rho, o_rho, 4, dt), (rho, o_rho)
+
+
+def test_mode_selection_on_cpu_and_the_refusal_text():
+    net = O.build_model({"sizes": [4, 3]})
+    for dt in (torch.float32, torch.bfloat16, torch.float16, torch.float64):
+        params = list(net.to(dt).parameters())
+        assert mfl_amd.ClientStepStats(params).mode == "torch"  # CPU parameters stay on torch
+        assert not client_stats._fused_ok(params)
+        with pytest.raises(TypeError, match="one dtype among fp32, bf16, fp16 and fp64"):
+            mfl_amd.ClientStepStats(params, stats="hip")
+    mixed = [torch.nn.Parameter(torch.zeros(3, dtype=torch.bfloat16)), torch.nn.Parameter(torch.zeros(3))]
+    assert mfl_amd.ClientStepStats(mixed).mode == "torch"
+    with pytest.raises(TypeError, match="all of one dtype"):
+        mfl_amd.ClientStepStats(mixed, stats="hip")
+    assert not client_stats._fused_ok([])
+    assert set(client_stats.FUSED_DTYPES) == {torch.float32, torch.bfloat16, torch.float16, torch.float64}
+
+
+class _Fake:
+    """Stands in for a CUDA parameter: _fused_ok reads attributes only."""
+
+    def __init__(self, dtype, device="cuda:0", contiguous=True):
+        self.dtype, self.device, self.is_cuda, self._c = dtype, device, True, contiguous
+
+    def is_contiguous(self):
+        return self._c
+
+
+def test_the_dtype_rule():
+    ok = client_stats._fused_ok
+    for dt in (torch.float32, torch.bfloat16, torch.float16, torch.float64):
+        assert ok([_Fake(dt), _Fake(dt)])
+        assert not ok([_Fake(dt), _Fake(dt, contiguous=False)])
+        assert not ok([_Fake(dt), _Fake(dt, device="cuda:1")])
+    assert not ok([_Fake(torch.bfloat16), _Fake(torch.float16)])
+    assert not ok([_Fake(torch.float32), _Fake(torch.float64)])
+    for dt in (torch.int64, torch.float8_e4m3fn, torch.complex64):
+        assert not ok([_Fake(dt)])
+
+
+@pytest.mark.parametrize("key", ["bf16", "f16"])
+def test_host_rounding_equals_torch_cpu_casts(key):
+    """client_stats._round_to / _norm_of / _guard_bound (the host side of the
+    :71 guard) against torch's CPU casts and the oracle's guard terms."""
+    dt = V.DTYPES[key]
+    rng = np.random.default_rng(5)
+    xs = np.concatenate([rng.normal(0, 1, 500) * 10.0 ** rng.integers(-12, 6, 500),
+                         [0.0, -0.0, math.inf, -math.inf, 65504.0, 65520.0, 65519.99, 3.3895e38, 3.4e38, 1e-45, 6e-8,
+                          2.98e-8, 1.0 + 2.0 ** -8, 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -9]])
+    for x in xs:
+        assert V.same(client_stats._round_to(float(x), dt), V.rT(float(x), dt)), x
+    assert math.isnan(client_stats._round_to(math.nan, dt)) and math.isnan(client_stats._norm_of(math.nan, dt))
+    for s_g, s_w, lr_ratio in zip(rng.uniform(0, 50, 300) ** 2, rng.uniform(0, 50, 300) ** 2,
+                                  rng.uniform(1e-3, 30.0, 300)):
+        n_g, bound = V.guard_terms(s_g, s_w, lr_ratio, 1.0, dt)
+        assert client_stats._norm_of(s_g, dt) == n_g
+        assert client_stats._guard_bound(client_stats._norm_of(s_w, dt), lr_ratio, dt) == bound
+    assert client_stats._norm_of(math.inf, dt) == math.inf
+
+
+def test_host_rounding_fp64_is_plain_fp64():
+    dt = torch.float64
+    assert client_stats._round_to(0.1, dt) == 0.1
+    assert client_stats._norm_of(2.0, dt) == math.sqrt(2.0)
+    assert client_stats._guard_bound(3.0, 0.1, dt) == 3.0 * 0.1 == V.guard_terms(1.0, 9.0, 0.1, 1.0, dt)[1]
