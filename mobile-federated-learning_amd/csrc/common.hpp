@@ -35,12 +35,14 @@
 
 #include "fedavg_amd.h"
 #include "fedavg_amd_tuning.h"
+#include "reduce_plan.hpp"
 
 #pragma clang fp contract(off)
 
 namespace fedavg_impl {
 
 constexpr int kBlock = 256;  // 4 waves of 64
+static_assert(kBlock == kReduceBlock, "reduce_plan.hpp plans for this block size");
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
@@ -499,37 +501,50 @@ int64_t resident_blocks(Kern kernel, int block = kBlock) {
   return static_cast<int64_t>(per_cu > 0 ? per_cu : 1) * cu_count();
 }
 
-// Round-split dispatch: the column range is cut into the fewest EQUAL
-// launches whose blocks all fit on the chip at once (one resident round
-// each).  Within a launch every block starts together and the running blocks
-// sweep one compact window of every client row; the stream boundary between
-// launches re-aligns them (a multi-round launch lets blocks drift apart and
-// leaves a half-empty last round).
-template <int U, int C, bool NT>
-void launch_split_ev(const float* clients, int K, int64_t ld, int64_t P, const float* W, float* out, int max_blocks,
-                     hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
-  const int64_t nvec = (P + 3) / 4;
-  const int64_t span = static_cast<int64_t>(kBlock) * C;
-  const int64_t resident = max_blocks > 0 ? max_blocks : resident_blocks(reduce_f32x4_var_kernel<U, C, NT, false>);
-  const int64_t blocks = (nvec + span - 1) / span;
-  const int64_t nl = (blocks + resident - 1) / resident;
-  const int64_t per = ((nvec + nl - 1) / nl + span - 1) / span * span;  // float4 columns per launch
-  const f32x4* X = reinterpret_cast<const f32x4*>(clients);
-  for (int64_t v0 = 0; v0 < nvec; v0 += per) {
-    const int64_t n = (nvec - v0) < per ? (nvec - v0) : per;
-    const int tail = (v0 + n == nvec) ? static_cast<int>(P & 3) : 0;
-    // launch-attached timing events: the first launch's start, the last one's end
-    hipExtLaunchKernelGGL((reduce_f32x4_var_kernel<U, C, NT, false>), dim3(static_cast<unsigned>((n + span - 1) / span)),
-                          dim3(kBlock), 0, s, v0 == 0 ? ev_start : nullptr, v0 + n >= nvec ? ev_stop : nullptr, 0,
-                          X + v0, K, ld / 4, n, tail, W, out + v0 * 4);
-  }
+// One call of a row reduce: [K, ld] rows of P elements on stream s; the
+// timing events, when given, ride on the first launch's start and the last
+// one's end
+struct ReduceCall {
+  const void* clients;
+  int K;
+  int64_t ld, P;
+  const void* W;
+  void* out;
+  hipStream_t s;
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+};
+
+// Round-split launches (reduce_plan.hpp: round_split) of one kernel instance.
+// An instance says what differs between the kernels: kLanes elements per
+// 16-B slice, kSpan slices per block, resident() blocks the chip holds at
+// once, and launch(v0, n, tail, ev_start, ev_stop) of slices [v0, v0 + n).
+// max_blocks: blocks per launch, 0 = the resident ones.
+template <class Inst>
+RoundSplit split_of(const Inst& k, int64_t P, int max_blocks) {
+  return round_split((P + Inst::kLanes - 1) / Inst::kLanes, Inst::kSpan, max_blocks > 0 ? max_blocks : k.resident());
+}
+template <class Inst>
+void launch_round_split(const Inst& k, int max_blocks) {
+  const ReduceCall& c = k.c;
+  for_each_launch(split_of(k, c.P, max_blocks), (c.P + Inst::kLanes - 1) / Inst::kLanes,
+                  static_cast<int>(c.P % Inst::kLanes), [&](int64_t v0, int64_t n, int tail, bool first, bool last) {
+                    k.launch(v0, n, tail, first ? c.ev_start : nullptr, last ? c.ev_stop : nullptr);
+                  });
 }
 
+// reduce_f32x4_var_kernel<U, C, NT>, launch-attached timing events
 template <int U, int C, bool NT>
-void launch_split(const float* clients, int K, int64_t ld, int64_t P, const float* W, float* out, int max_blocks,
-                  hipStream_t s) {
-  launch_split_ev<U, C, NT>(clients, K, ld, P, W, out, max_blocks, s, nullptr, nullptr);
-}
+struct VarSplit {
+  static constexpr int kLanes = 4;
+  static constexpr int kSpan = kBlock * C;  // float4 columns per block
+  const ReduceCall& c;
+  int64_t resident() const { return resident_blocks(reduce_f32x4_var_kernel<U, C, NT, false>); }
+  void launch(int64_t v0, int64_t n, int tail, hipEvent_t ev_start, hipEvent_t ev_stop) const {
+    hipExtLaunchKernelGGL((reduce_f32x4_var_kernel<U, C, NT, false>), dim3(grid_for(n, kSpan)), dim3(kBlock), 0, c.s,
+                          ev_start, ev_stop, 0, static_cast<const f32x4*>(c.clients) + v0, c.K, c.ld / 4, n, tail,
+                          static_cast<const float*>(c.W), static_cast<float*>(c.out) + v0 * 4);
+  }
+};
 
 // Row reduce through buffer descriptors: a full column group reads client
 // row k through one descriptor whose base (row k + the group's first column)
@@ -617,28 +632,21 @@ __global__ __launch_bounds__(BS) void reduce_f32x4_buf_kernel(const f32x4* __res
   }
 }
 
-// launch_split's round-split schedule with the buffer-descriptor kernel, in
-// blocks of BS threads (BS = 64: one wave per workgroup, for short rows whose
-// 256-thread groups would leave the CUs unevenly loaded)
+// reduce_f32x4_buf_kernel<U, C, BS, REMAP> in blocks of BS threads (BS = 64:
+// one wave per workgroup, for short rows whose 256-thread groups would leave
+// the CUs unevenly loaded), launch-attached timing events
 template <int U, int C, int BS = kBlock, int REMAP = 0>
-void launch_split_buf(const float* clients, int K, int64_t ld, int64_t P, const float* W, float* out, int max_blocks,
-                      hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
-  const int64_t nvec = (P + 3) / 4;
-  const int64_t span = static_cast<int64_t>(BS) * C;
-  const int64_t resident =
-      max_blocks > 0 ? max_blocks : resident_blocks(reduce_f32x4_buf_kernel<U, C, BS, REMAP>, BS);
-  const int64_t blocks = (nvec + span - 1) / span;
-  const int64_t nl = (blocks + resident - 1) / resident;
-  const int64_t per = ((nvec + nl - 1) / nl + span - 1) / span * span;
-  const f32x4* X = reinterpret_cast<const f32x4*>(clients);
-  for (int64_t v0 = 0; v0 < nvec; v0 += per) {
-    const int64_t n = (nvec - v0) < per ? (nvec - v0) : per;
-    const int tail = (v0 + n == nvec) ? static_cast<int>(P & 3) : 0;
-    hipExtLaunchKernelGGL((reduce_f32x4_buf_kernel<U, C, BS, REMAP>), dim3(static_cast<unsigned>((n + span - 1) / span)),
-                          dim3(BS), 0, s, v0 == 0 ? ev_start : nullptr, v0 + n >= nvec ? ev_stop : nullptr, 0,
-                          X + v0, K, ld / 4, n, tail, W, out + v0 * 4);
+struct BufSplit {
+  static constexpr int kLanes = 4;
+  static constexpr int kSpan = BS * C;
+  const ReduceCall& c;
+  int64_t resident() const { return resident_blocks(reduce_f32x4_buf_kernel<U, C, BS, REMAP>, BS); }
+  void launch(int64_t v0, int64_t n, int tail, hipEvent_t ev_start, hipEvent_t ev_stop) const {
+    hipExtLaunchKernelGGL((reduce_f32x4_buf_kernel<U, C, BS, REMAP>), dim3(grid_for(n, kSpan)), dim3(BS), 0, c.s,
+                          ev_start, ev_stop, 0, static_cast<const f32x4*>(c.clients) + v0, c.K, c.ld / 4, n, tail,
+                          static_cast<const float*>(c.W), static_cast<float*>(c.out) + v0 * 4);
   }
-}
+};
 
 // ---------------------------------------------------------------------------
 // Fused aggregate + :291 tiles (fedavg_dist.hip: [K, ld] rows;

@@ -1,6 +1,7 @@
-// fedavg_reduce.hip -- production kernels, schedule and C ABI of
-// libfedavg_amd.so (include/fedavg_amd.h).  Shared device code and the
-// reference semantics: common.hpp.
+// fedavg_reduce.hip -- production kernels, the walk from a plan to its kernel
+// instance and the C ABI of libfedavg_amd.so (include/fedavg_amd.h).  Shared
+// device code and the reference semantics: common.hpp; the plan, the form
+// tables and the round-split cut: reduce_plan.hpp.
 #include "common.hpp"
 
 namespace fedavg_impl {
@@ -358,24 +359,6 @@ __global__ __launch_bounds__(64 * SPLITS) void reduce_splitk_f32x4_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Production schedule for the exact fp32 reduce (fedavg_reduce_f32), chosen
-// from the in-process A/B sweeps in profiles/ (scripts/kernel_variants.py):
-//   * column slices per thread C: the widest of 8/4/2/1 that still gives a
-//     launch >= 512 blocks (a block then reads C*4 KiB contiguous bytes of
-//     each client row per step); U (rows per load batch) = 4 for C = 8, else 8
-//     (32 and 32/16/8 16-B loads in flight per thread);
-//   * round-split dispatch: the column range is cut into the fewest equal
-//     launches of <= 768 blocks (2-3 blocks per CU) -- one resident round
-//     each, so every launch's blocks start together and sweep one compact
-//     window of every row (88% of HBM peak at K=100 x P=25M vs 76% for one
-//     multi-round launch of the same kernel);
-//   * nontemporal loads (the rows are read once), except for working sets of
-//     64-240 MiB, which stay resident in the 256 MiB Infinity Cache across
-//     back-to-back rounds when loaded with the default policy (there U = 16,
-//     C = 4 was fastest: 89% vs 81% for C = 1).
-// ---------------------------------------------------------------------------
-
-// ---------------------------------------------------------------------------
 // Small-round kernel (fedavg_round_f32 for rounds of a few MB): ONE launch
 // instead of H2D + reduce + D2H.  It reads the packed client rows straight
 // from pinned host memory (zero-copy over PCIe), keeps a copy of them in HBM
@@ -420,149 +403,6 @@ __global__ __launch_bounds__(kBlock) void round_small_f32x4_kernel(
   store_slice(out_h, v, nvec, tail, acc);
 }
 
-struct Schedule {
-  int unroll, cols, nt, blocks_per_launch;
-  int buf = 0;  // 1: reduce_f32x4_buf_kernel (per-row buffer descriptors); blocks_per_launch 0 = resident blocks
-};
-
-// Round-split launches hold 3 blocks per CU (768 on the 256-CU MI355X); the
-// CU count is read from the device, so a partitioned GPU (fewer CUs per
-// device) keeps one resident round per launch.
-constexpr int kBlocksPerCU = 3;
-inline int blocks_per_launch() { return kBlocksPerCU * cu_count(); }
-
-constexpr int64_t kManyClients = 64;  // K from which the wider short-row schedules apply
-
-// `resident_rows`: bytes of the row buffer the caller streams (K x ld); the
-// Infinity-Cache band applies only when that whole buffer fits the band, so a
-// column chunk of a wider shard (N > 1 pipeline) streams from HBM instead.
-Schedule choose_schedule(int64_t K, int64_t P, double resident_rows = -1.0) {
-  const int64_t nvec = (P + 3) / 4;
-  Schedule sc{8, 1, 1, blocks_per_launch()};
-  const int64_t full = 2 * static_cast<int64_t>(cu_count());  // blocks for a full-chip launch (512 on MI355X)
-  if (K <= 4) {
-    // a block's work is tiny (K rows): one launch, many short blocks; round
-    // splitting would only add launch boundaries (K=2..3 sweeps: +14-22 %)
-    sc.cols = 1;
-    sc.blocks_per_launch = 1 << 30;
-  } else if (nvec >= full * kBlock * 8) {
-    sc.unroll = 4, sc.cols = 8;
-  } else if (nvec >= full * kBlock * 4) {
-    sc.cols = 4;
-  } else if (nvec >= full * kBlock * 2) {
-    sc.cols = 2;
-  } else {
-    // short rows: few blocks, so each thread's client chain is the critical
-    // path; deeper batches (16 rows) cut its round trips (+11-12 %), and with
-    // many clients 4 slices per thread keep 64 loads in flight
-    sc.unroll = 16;
-    sc.cols = (K >= 500 && nvec >= full / 4 * kBlock * 4) ? 4 : 1;
-  }
-  const double bytes = 4.0 * static_cast<double>(K) * static_cast<double>(P);
-  const double span_bytes = resident_rows > bytes ? resident_rows : bytes;
-  if (K > 4 && bytes > 64.0 * (1 << 20) && span_bytes <= 240.0 * (1 << 20)) {
-    // Infinity-Cache-resident band: default-policy loads, and a deep, wide
-    // per-thread batch (16 rows x 4 slices) measured fastest there
-    sc.nt = 0;
-    sc.unroll = 16;
-    sc.cols = 4;
-  }
-  return sc;
-}
-
-// The fp32 kernel's own refinement (the fp64/fp16/bf16 paths keep
-// choose_schedule): rows long enough for a full-chip launch (2 blocks per
-// CU) of 16-slice groups take U2 x C16 through per-row buffer descriptors
-// (reduce_f32x4_buf_kernel, 32-bit lane offsets shared by every row):
-// 7.09-7.15 vs 6.96-7.05 TB/s at K=100 x 25M and 6.89 vs 6.49 at K=100 x 10M,
-// interleaved (scripts/buf_probe.py, profiles/r01_buf_probe*.jsonl); below
-// that width the 16-slice groups leave the launch short of blocks (4.4 TB/s
-// at K=100 x 5M).
-Schedule choose_f32_schedule(int64_t K, int64_t P, int64_t ld) {
-  // a chunk of a wider row buffer (ld > P) is not cache-resident between
-  // calls: K=100 x 390K chunks of a 3.125M-column shard (the N=8 pipeline)
-  // run 3,971 GB/s in the Infinity-Cache schedule and 5,065 streamed
-  // (U16 x C1 nt; profiles/r01_chunk_rotating.jsonl)
-  Schedule sc = choose_schedule(K, P, 4.0 * static_cast<double>(K) * static_cast<double>(ld > P ? ld : P));
-  const int64_t nvec = (P + 3) / 4;
-  const int64_t full = 2 * static_cast<int64_t>(cu_count());
-  if (sc.nt && sc.unroll == 4 && sc.cols == 8 && nvec >= full * kBlock * 16) {
-    sc.unroll = 2;
-    sc.cols = 16;
-    sc.buf = 1;
-  }
-  // Few clients (5 <= K < 64) on rows below the 8-slice band: per-row buffer
-  // descriptors with 1-2 slices per thread and a launch of every resident
-  // block.  rocprofv3 kernel time, variants interleaved in one process, two
-  // sweeps (scripts/buf_probe.py; profiles/r02/sweeps/small_k_*.json):
-  //   4-slice band (2.1M <= P < 4.2M): U8 x C2 -- K=5 x 2.4M 0.68-0.73 x the
-  //     time of U8 x C4 (nt), K=10 x 2.4M 0.72-0.73 x U16 x C4 (Infinity-Cache
-  //     band), K=32 / 50 x 2.4M 0.89 / 0.94 x;
-  //   shorter rows, 8 <= K <= 32, P >= 262K: U8 x C1 -- K=10 x 1.2M (FEMNIST)
-  //     0.88 x, K=10 x 300K 0.69-0.73 x, K=20 / 32 x 1.2M 0.81-0.85 / 0.73 x,
-  //     K=32 x 300K 0.80 x; K=5 and K=50 gain nothing there.
-  // (K >= 64 keeps the rules above, tuned on the all-gather chunk shapes.)
-  if (K >= 5 && K < kManyClients && nvec < full * kBlock * 8) {
-    if (nvec >= full * kBlock * 4) {
-      sc = Schedule{8, 2, 1, 0, 1};
-    } else if (K >= 8 && K <= 32 && nvec >= full * kBlock / 2) {
-      sc = Schedule{8, 1, 1, 0, 1};
-    }
-  }
-  // short rows with many clients (the N > 1 all-gather chunks): 4 slices per
-  // thread -- K=100 x 1.56M (N=2 chunk) 6,695 vs 6,178 GB/s at U8 x C2, and
-  // K=100 x 781K (N=4 chunk) 6,741 vs 5,668 at U16 x C1
-  // (profiles/r01_chunk_shapes.jsonl, interleaved)
-  if (sc.nt && K >= kManyClients) {
-    if (sc.unroll == 8 && sc.cols == 2) sc.cols = 4;
-    if (sc.unroll == 16 && sc.cols == 1 && nvec >= full / 4 * kBlock * 4) sc.cols = 4;
-    // Rows that give 3/4 to 1 block per CU at 6 (K >= 64) or 3 (K >= 256)
-    // slices per thread: one resident block on (nearly) every CU beats
-    // 1.5 blocks per CU at 4 slices.  Rotating-chunk sweep, interleaved,
-    // bit-identical (profiles/r02/sweeps/short_row_c3_c6.jsonl): K=100 x 1.56M
-    // (the N=2 chunk) 6,822 vs 6,585 GB/s at U8 x C4; K=500 x 702K (cfg4's
-    // N=8 chunk) 6,856 vs 6,627 at U16 x C4.  (K=100 x 781K keeps U16 x C4:
-    // 6,527 vs 6,200 at C3.)
-    const int64_t cus = cu_count();
-    if (nvec >= cus * 3 / 4 * kBlock * 6 && nvec <= cus * kBlock * 6) {
-      sc.unroll = 4;
-      sc.cols = 6;
-    } else if (K >= 256 && nvec >= cus * 3 / 4 * kBlock * 3 && nvec <= cus * kBlock * 3) {
-      sc.unroll = 8;
-      sc.cols = 3;
-    }
-  }
-  return sc;
-}
-
-void launch_production_f32(const float* clients, int K, int64_t ld, int64_t P, const float* W, float* out,
-                           hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-  const Schedule sc = choose_f32_schedule(K, P, ld);
-  const int bpl = sc.blocks_per_launch;
-  const int key = sc.unroll * 100 + sc.cols;
-  if (sc.buf) {
-    switch (key) {
-      case 801: launch_split_buf<8, 1>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-      case 802: launch_split_buf<8, 2>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-      default: launch_split_buf<2, 16>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-    }
-  }
-  if (sc.nt) {
-    switch (key) {
-      case 408: launch_split_ev<4, 8, true>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-      case 804: launch_split_ev<8, 4, true>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-      case 802: launch_split_ev<8, 2, true>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-      case 1604: launch_split_ev<16, 4, true>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-      case 1601: launch_split_ev<16, 1, true>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-      case 406: launch_split_ev<4, 6, true>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-      case 803: launch_split_ev<8, 3, true>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-      default: launch_split_ev<8, 1, true>(clients, K, ld, P, W, out, bpl, s, e0, e1); return;
-    }
-  }
-  // default-policy loads: the Infinity-Cache band, always U16 x C4 (choose_schedule)
-  launch_split_ev<16, 4, false>(clients, K, ld, P, W, out, bpl, s, e0, e1);
-}
-
 // fp32 buffers that are not all 16-B aligned (or an odd row stride): the
 // first-version kernels, same per-element order and bits.
 int reduce_f32_unaligned(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
@@ -581,29 +421,23 @@ int reduce_f32_unaligned(const float* clients, int64_t K, int64_t P, int64_t ld,
   return launch_status(what);
 }
 
-// Round-split launches of reduce_vec_kernel (fp64 / fp16 / bf16).  The
-// schedule is the fp32 one for the same number of 16-B column slices and the
-// same byte footprint (choose_schedule takes fp32-equivalent element counts).
-template <class Op, int U, int C, bool NT>
-void launch_vec_split(const void* clients, int K, int64_t ld, int64_t P, const void* W, void* out, int bpl,
-                      hipStream_t s) {
-  using vec = typename Op::vec;
-  const int64_t lanes = Op::kLanes;
-  const int64_t nvec = (P + lanes - 1) / lanes;
-  const int64_t span = static_cast<int64_t>(kBlock) * C;
-  const int64_t blocks = (nvec + span - 1) / span;
-  const int64_t nl = (blocks + bpl - 1) / bpl;
-  const int64_t per = ((nvec + nl - 1) / nl + span - 1) / span * span;
-  const vec* X = reinterpret_cast<const vec*>(clients);
-  auto* O = reinterpret_cast<typename Op::elem*>(out);
-  for (int64_t v0 = 0; v0 < nvec; v0 += per) {
-    const int64_t n = (nvec - v0) < per ? (nvec - v0) : per;
-    const int tail = (v0 + n == nvec) ? static_cast<int>(P % lanes) : 0;
-    hipLaunchKernelGGL((reduce_vec_kernel<Op, U, C, NT>), dim3(static_cast<unsigned>((n + span - 1) / span)),
-                       dim3(kBlock), 0, s, X + v0, K, ld / lanes, n, tail,
-                       reinterpret_cast<const typename Op::wt*>(W), O + v0 * lanes);
+// Round-split instances (common.hpp: launch_round_split) of the fp64 / fp16 /
+// bf16 kernels, `Kern` one of reduce_vec_kernel / reduce_vec_buf_kernel; no
+// timing events.
+template <class Op, int C, auto Kern>
+struct VecSplitOf {
+  static constexpr int kLanes = Op::kLanes;
+  static constexpr int kSpan = kBlock * C;
+  const ReduceCall& c;
+  int64_t resident() const { return resident_blocks(Kern); }
+  void launch(int64_t v0, int64_t n, int tail, hipEvent_t, hipEvent_t) const {
+    hipLaunchKernelGGL(Kern, dim3(grid_for(n, kSpan)), dim3(kBlock), 0, c.s,
+                       static_cast<const typename Op::vec*>(c.clients) + v0, c.K, c.ld / kLanes, n, tail,
+                       static_cast<const typename Op::wt*>(c.W), static_cast<typename Op::elem*>(c.out) + v0 * kLanes);
   }
-}
+};
+template <class Op, int U, int C, bool NT>
+using VecSplit = VecSplitOf<Op, C, reduce_vec_kernel<Op, U, C, NT>>;
 
 // fp64 / fp16 / bf16 through per-row buffer descriptors (the fp32
 // reduce_f32x4_buf_kernel's addressing: SGPR-held row bases, 32-bit lane
@@ -667,90 +501,120 @@ __global__ __launch_bounds__(kBlock) void reduce_vec_buf_kernel(
   }
 }
 
-template <class Op, int U, int C>
-void launch_vec_split_buf(const void* clients, int K, int64_t ld, int64_t P, const void* W, void* out, int bpl,
-                          hipStream_t s) {
-  using vec = typename Op::vec;
-  const int64_t lanes = Op::kLanes;
-  const int64_t nvec = (P + lanes - 1) / lanes;
-  const int64_t span = static_cast<int64_t>(kBlock) * C;
-  const int64_t blocks = (nvec + span - 1) / span;
-  const int64_t nl = (blocks + bpl - 1) / bpl;
-  const int64_t per = ((nvec + nl - 1) / nl + span - 1) / span * span;
-  const vec* X = reinterpret_cast<const vec*>(clients);
-  auto* O = reinterpret_cast<typename Op::elem*>(out);
-  for (int64_t v0 = 0; v0 < nvec; v0 += per) {
-    const int64_t n = (nvec - v0) < per ? (nvec - v0) : per;
-    const int tail = (v0 + n == nvec) ? static_cast<int>(P % lanes) : 0;
-    hipLaunchKernelGGL((reduce_vec_buf_kernel<Op, U, C>), dim3(static_cast<unsigned>((n + span - 1) / span)),
-                       dim3(kBlock), 0, s, X + v0, K, ld / lanes, n, tail,
-                       reinterpret_cast<const typename Op::wt*>(W), O + v0 * lanes);
+// The instances of a dtype's form tables (reduce_plan.hpp): nontemporal,
+// default-policy and buffer-descriptor.  The fp32 kernels are not written over
+// an element-op policy; OpF32 stands for them in the walk.
+struct OpF32 {
+  static constexpr int kLanes = 4;
+};
+template <class Op>
+struct Forms {
+  template <int U, int C> using Nt = VecSplit<Op, U, C, true>;
+  template <int U, int C> using Default = VecSplit<Op, U, C, false>;
+  template <int U, int C> using Buf = VecSplitOf<Op, C, reduce_vec_buf_kernel<Op, U, C>>;
+};
+template <>
+struct Forms<OpF32> {
+  template <int U, int C> using Nt = VarSplit<U, C, true>;
+  template <int U, int C> using Default = VarSplit<U, C, false>;
+  template <int U, int C> using Buf = BufSplit<U, C>;
+};
+
+template <auto& Table, template <int, int> class Inst, class F>
+bool with_form(const ReducePlan& p, const ReduceCall& c, F&& f) {
+  return for_entry<Table>(p.unroll, p.cols,
+                          [&](auto u, auto cols) { f(Inst<decltype(u)::value, decltype(cols)::value>{c}); });
+}
+
+// The one walk from a plan to its kernel instance: f(instance) for the plan's
+// entry in the dtype's table -- resident() and launch(v0, n, tail, ev_start,
+// ev_stop) of that kernel on call c; false: the tables hold no such form.
+// Only the tables' entries are instantiated.
+template <class Op, class F>
+bool with_reduce_instance(const ReducePlan& p, const ReduceCall& c, F&& f) {
+  using I = Forms<Op>;
+  if constexpr (Op::kLanes == 4) {
+    if (p.buf) return with_form<kF32Buf, I::template Buf>(p, c, f);
+    return p.nt ? with_form<kF32Nt, I::template Nt>(p, c, f) : with_form<kF32Default, I::template Default>(p, c, f);
+  } else if constexpr (Op::kLanes == 2) {
+    if (p.buf) return with_form<kF64Buf, I::template Buf>(p, c, f);
+    return p.nt ? with_form<kF64Nt, I::template Nt>(p, c, f) : with_form<kF64Default, I::template Default>(p, c, f);
+  } else {
+    if (p.buf) return false;  // fp16 / bf16 measured no gain from buffer descriptors
+    return p.nt ? with_form<kHalfNt, I::template Nt>(p, c, f) : with_form<kHalfDefault, I::template Default>(p, c, f);
   }
 }
 
 template <class Op>
-bool launch_vec_buf(int U, int C, const void* clients, int K, int64_t ld, int64_t P, const void* W, void* out,
-                    int bpl, hipStream_t s) {
+int no_instance(const char* what, const ReducePlan& p) {
+  return set_error(FEDAVG_EMODE, "%s: no %s kernel instance for the plan U=%d C=%d nt=%d buf=%d", what,
+                   Op::kLanes == 4 ? "fp32" : (Op::kLanes == 2 ? "fp64" : "fp16/bf16"), p.unroll, p.cols, p.nt, p.buf);
+}
+
+// The production path of every dtype (16-B aligned buffers): the plan for
+// this device, its instance, round-split launches.
+template <class Op>
+int launch_production(const ReduceCall& c, const char* what) {
+  const ReducePlan p = plan_reduce(Op::kLanes, c.K, c.P, c.ld, cu_count());
+  if (!with_reduce_instance<Op>(p, c, [&](auto inst) { launch_round_split(inst, p.blocks_per_launch); }))
+    return no_instance<Op>(what, p);
+  return launch_status(what);
+}
+
+// What launch_production would do, reported: the plan (nontemporal 2 = buffer
+// descriptors) and the launches its loop runs.
+template <class Op>
+int report_production(const char* what, int64_t K, int64_t P, int64_t ld, int* unroll, int* cols, int* nontemporal,
+                      int* launches) {
+  const ReducePlan p = plan_reduce(Op::kLanes, K, P, ld, cu_count());
+  const ReduceCall c{nullptr, static_cast<int>(K), ld, P, nullptr, nullptr, nullptr};
+  int n = 0;
+  if (!with_reduce_instance<Op>(p, c, [&](auto inst) { n = split_of(inst, P, p.blocks_per_launch).launches; }))
+    return no_instance<Op>(what, p);
+  if (unroll) *unroll = p.unroll;
+  if (cols) *cols = p.cols;
+  if (nontemporal) *nontemporal = p.buf ? 2 : p.nt;
+  if (launches) *launches = n;
+  return FEDAVG_OK;
+}
+
+#ifdef FEDAVG_TUNING
+// Benchmarking hooks, deliberately wider than the plan: an explicit (rows per
+// batch U, 16-B slices per thread C) form, nontemporal loads, round-split at
+// bpl blocks per launch; false: no such instance.
+// fedavg_reduce_vec_buf: the buffer-descriptor kernel of fp64 / fp16 / bf16
+template <class Op>
+bool launch_vec_buf(int U, int C, const ReduceCall& c, int bpl) {
+  using I = Forms<Op>;
   switch (U * 100 + C) {
-    case 804: launch_vec_split_buf<Op, 8, 4>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 408: launch_vec_split_buf<Op, 4, 8>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 216: launch_vec_split_buf<Op, 2, 16>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 404: launch_vec_split_buf<Op, 4, 4>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 208: launch_vec_split_buf<Op, 2, 8>(clients, K, ld, P, W, out, bpl, s); return true;
+    case 804: launch_round_split(typename I::template Buf<8, 4>{c}, bpl); return true;
+    case 408: launch_round_split(typename I::template Buf<4, 8>{c}, bpl); return true;
+    case 216: launch_round_split(typename I::template Buf<2, 16>{c}, bpl); return true;
+    case 404: launch_round_split(typename I::template Buf<4, 4>{c}, bpl); return true;
+    case 208: launch_round_split(typename I::template Buf<2, 8>{c}, bpl); return true;
     default: return false;
   }
 }
 
-// fp16/bf16 schedule from the fp32 one for the same bytes per row.  Each 16-B
-// vector unpacks into 8 fp32 lanes of work, so the deep fp32 batches are cut
-// to stay spill-free -- except the large-P key: there the packed kernel wants
-// the fp32 kernel's 32 x 16-B loads in flight per thread as U8 x C4 (158
-// VGPRs), not U2 x C8 (16 loads): 6,543 vs 5,896 GB/s at K=100 x P=25M bf16
-// and 6,641 vs 6,595 at K=500 x P=11.2M (profiles/sweeps/r01_half_*.jsonl).
-inline int half_key(int key) {
-  switch (key) {
-    case 408: return 804;
-    case 804: case 1604: return 404;
-    case 1601: return 801;
-    default: return key;
+// fedavg_reduce_half_variant: the packed fp16 / bf16 kernel
+template <class Op>
+bool launch_half_variant(int U, int C, const ReduceCall& c, int bpl) {
+  switch (U * 100 + C) {
+    case 208: launch_round_split(VecSplit<Op, 2, 8, true>{c}, bpl); return true;
+    case 408: launch_round_split(VecSplit<Op, 4, 8, true>{c}, bpl); return true;
+    case 108: launch_round_split(VecSplit<Op, 1, 8, true>{c}, bpl); return true;
+    case 404: launch_round_split(VecSplit<Op, 4, 4, true>{c}, bpl); return true;
+    case 204: launch_round_split(VecSplit<Op, 2, 4, true>{c}, bpl); return true;
+    case 804: launch_round_split(VecSplit<Op, 8, 4, true>{c}, bpl); return true;
+    case 802: launch_round_split(VecSplit<Op, 8, 2, true>{c}, bpl); return true;
+    case 402: launch_round_split(VecSplit<Op, 4, 2, true>{c}, bpl); return true;
+    case 116: launch_round_split(VecSplit<Op, 1, 16, true>{c}, bpl); return true;
+    case 216: launch_round_split(VecSplit<Op, 2, 16, true>{c}, bpl); return true;
+    case 1601: launch_round_split(VecSplit<Op, 16, 1, true>{c}, bpl); return true;
+    default: return false;
   }
 }
 
-template <class Op, bool NT>
-void launch_vec_nt(const Schedule& sc, const void* clients, int K, int64_t ld, int64_t P, const void* W, void* out,
-                   hipStream_t s) {
-  // Only what choose_schedule can ask for is instantiated.  Its keys: 801
-  // (K <= 4), 408, 804, 802, 1601 and 1604 with nontemporal loads; the
-  // Infinity-Cache band's default-policy loads come with 1604 alone.  The
-  // packed 16-bit types take them through half_key.
-  const int bpl = sc.blocks_per_launch;
-  const int key = sc.unroll * 100 + sc.cols;
-  if constexpr (Op::kLanes == 8) {
-    if constexpr (!NT) {
-      launch_vec_split<Op, 4, 4, false>(clients, K, ld, P, W, out, bpl, s);
-    } else {
-      switch (half_key(key)) {
-        case 804: launch_vec_split<Op, 8, 4, true>(clients, K, ld, P, W, out, bpl, s); break;
-        case 404: launch_vec_split<Op, 4, 4, true>(clients, K, ld, P, W, out, bpl, s); break;
-        case 802: launch_vec_split<Op, 8, 2, true>(clients, K, ld, P, W, out, bpl, s); break;
-        default: launch_vec_split<Op, 8, 1, true>(clients, K, ld, P, W, out, bpl, s); break;
-      }
-    }
-  } else if constexpr (!NT) {
-    launch_vec_split<Op, 16, 4, false>(clients, K, ld, P, W, out, bpl, s);
-  } else {
-    switch (key) {
-      case 408: launch_vec_split<Op, 4, 8, true>(clients, K, ld, P, W, out, bpl, s); break;
-      case 804: launch_vec_split<Op, 8, 4, true>(clients, K, ld, P, W, out, bpl, s); break;
-      case 802: launch_vec_split<Op, 8, 2, true>(clients, K, ld, P, W, out, bpl, s); break;
-      case 801: launch_vec_split<Op, 8, 1, true>(clients, K, ld, P, W, out, bpl, s); break;
-      case 1604: launch_vec_split<Op, 16, 4, true>(clients, K, ld, P, W, out, bpl, s); break;
-      default: launch_vec_split<Op, 16, 1, true>(clients, K, ld, P, W, out, bpl, s); break;
-    }
-  }
-}
-
-#ifdef FEDAVG_TUNING
 // Conversion probe (tests only): out[i] = the 16-bit rounding of the fp32
 // bit pattern in[i] by mode 0 = BF16Pk (hardware), 1 = c10 integer RNE,
 // 2 = F16Pk (hardware, packed), 3 = F16Rule (scalar v_cvt_f16_f32).
@@ -771,52 +635,6 @@ __global__ __launch_bounds__(kBlock) void probe_cvt16_kernel(const unsigned int*
 }
 
 #endif  // FEDAVG_TUNING
-
-// elem_bytes: 8 (fp64) or 2 (fp16/bf16).  The fp32 schedule is chosen for the
-// problem with the same 16-B slice count and byte footprint.
-template <class Op>
-void launch_production_vec(const void* clients, int K, int64_t ld, int64_t P, const void* W, void* out,
-                           hipStream_t s) {
-  const int64_t f32_equiv = P * static_cast<int64_t>(16 / Op::kLanes) / 4;  // same bytes per row
-  if constexpr (Op::kLanes == 2) {
-    // fp64 follows the fp32 kernel onto per-row buffer descriptors for long
-    // rows: 7,113 vs 6,992 GB/s at K=100 x 12.5M fp64 (scripts/vec_buf_probe.py,
-    // profiles/r01_vec_buf_probe.jsonl).  fp16/bf16 measured no gain (+0-1 %).
-    const Schedule f = choose_f32_schedule(K, f32_equiv, ld * static_cast<int64_t>(16 / Op::kLanes) / 4);
-    if (f.cols == 16) {
-      launch_vec_split_buf<Op, 2, 16>(clients, K, ld, P, W, out, f.blocks_per_launch, s);
-      return;
-    }
-  }
-  const int64_t ld_equiv = ld * static_cast<int64_t>(16 / Op::kLanes) / 4;
-  const Schedule sc = choose_schedule(K, f32_equiv, 4.0 * static_cast<double>(K) * static_cast<double>(ld_equiv));
-  if (sc.nt)
-    launch_vec_nt<Op, true>(sc, clients, K, ld, P, W, out, s);
-  else
-    launch_vec_nt<Op, false>(sc, clients, K, ld, P, W, out, s);
-}
-
-// Benchmarking hook (fedavg_reduce_half_variant): the packed fp16/bf16 kernel
-// with an explicit (rows per batch U, 16-B slices per thread C) schedule,
-// nontemporal loads and round-split at max_blocks blocks per launch.
-template <class Op>
-bool launch_half_variant(int U, int C, const void* clients, int K, int64_t ld, int64_t P, const void* W, void* out,
-                         int bpl, hipStream_t s) {
-  switch (U * 100 + C) {
-    case 208: launch_vec_split<Op, 2, 8, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 408: launch_vec_split<Op, 4, 8, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 108: launch_vec_split<Op, 1, 8, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 404: launch_vec_split<Op, 4, 4, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 204: launch_vec_split<Op, 2, 4, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 804: launch_vec_split<Op, 8, 4, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 802: launch_vec_split<Op, 8, 2, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 402: launch_vec_split<Op, 4, 2, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 116: launch_vec_split<Op, 1, 16, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 216: launch_vec_split<Op, 2, 16, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    case 1601: launch_vec_split<Op, 16, 1, true>(clients, K, ld, P, W, out, bpl, s); return true;
-    default: return false;
-  }
-}
 
 }  // namespace
 
@@ -847,8 +665,8 @@ int fedavg_reduce_f32(const float* clients, int64_t K, int64_t P, int64_t ld, co
     int rc = check_common(clients, K, P, ld, weights, out, what);
     if (rc) return rc;
     if (!aligned4(weights)) return set_error(FEDAVG_EALIGN, "%s: weights must be 4-byte aligned", what);
-    launch_production_f32(clients, static_cast<int>(K), ld, P, weights, out, static_cast<hipStream_t>(stream));
-    return launch_status(what);
+    return launch_production<OpF32>({clients, static_cast<int>(K), ld, P, weights, out, static_cast<hipStream_t>(stream)},
+                                    what);
   }
   return reduce_f32_unaligned(clients, K, P, ld, weights, out, static_cast<hipStream_t>(stream), what);
 }
@@ -862,48 +680,20 @@ int fedavg_reduce_f32_timed(const float* clients, int64_t K, int64_t P, int64_t 
   int rc = check_common(clients, K, P, ld, weights, out, what);
   if (rc) return rc;
   if (!aligned4(weights)) return set_error(FEDAVG_EALIGN, "%s: weights must be 4-byte aligned", what);
-  launch_production_f32(clients, static_cast<int>(K), ld, P, weights, out, static_cast<hipStream_t>(stream),
-                        static_cast<hipEvent_t>(start_event), static_cast<hipEvent_t>(stop_event));
-  return launch_status(what);
+  return launch_production<OpF32>({clients, static_cast<int>(K), ld, P, weights, out, static_cast<hipStream_t>(stream),
+                                   static_cast<hipEvent_t>(start_event), static_cast<hipEvent_t>(stop_event)},
+                                  what);
 }
-
-namespace {
-// launches of launch_production_f32 for this schedule (buffer-descriptor
-// schedules without a cap launch every resident block at once)
-int production_launches(const Schedule& sc, int64_t P) {
-  const int64_t nvec = (P + 3) / 4;
-  const int64_t span = static_cast<int64_t>(kBlock) * sc.cols;
-  const int64_t blocks = (nvec + span - 1) / span;
-  int64_t per = sc.blocks_per_launch;
-  if (per <= 0) {
-    switch (sc.unroll * 100 + sc.cols) {
-      case 801: per = resident_blocks(reduce_f32x4_buf_kernel<8, 1, kBlock, 0>, kBlock); break;
-      case 802: per = resident_blocks(reduce_f32x4_buf_kernel<8, 2, kBlock, 0>, kBlock); break;
-      default: per = resident_blocks(reduce_f32x4_buf_kernel<2, 16, kBlock, 0>, kBlock); break;
-    }
-  }
-  return static_cast<int>((blocks + per - 1) / per);
-}
-
-void report_schedule(const Schedule& sc, int64_t P, int* unroll, int* cols, int* nontemporal, int* launches) {
-  if (unroll) *unroll = sc.unroll;
-  if (cols) *cols = sc.cols;
-  if (nontemporal) *nontemporal = sc.buf ? 2 : sc.nt;
-  if (launches) *launches = production_launches(sc, P);
-}
-}  // namespace
 
 int fedavg_f32_schedule_ld(int64_t K, int64_t P, int64_t ld, int* unroll, int* cols, int* nontemporal,
                            int* launches) {
   if (K <= 0 || P < 0 || ld < P) return set_error(FEDAVG_EINVAL, "fedavg_f32_schedule_ld: bad sizes");
-  report_schedule(choose_f32_schedule(K, P, ld), P, unroll, cols, nontemporal, launches);
-  return FEDAVG_OK;
+  return report_production<OpF32>("fedavg_f32_schedule_ld", K, P, ld, unroll, cols, nontemporal, launches);
 }
 
 int fedavg_f32_schedule(int64_t K, int64_t P, int* unroll, int* cols, int* nontemporal, int* launches) {
   if (K <= 0 || P < 0) return set_error(FEDAVG_EINVAL, "fedavg_f32_schedule: bad sizes");
-  report_schedule(choose_f32_schedule(K, P, P), P, unroll, cols, nontemporal, launches);
-  return FEDAVG_OK;
+  return report_production<OpF32>("fedavg_f32_schedule", K, P, P, unroll, cols, nontemporal, launches);
 }
 
 int fedavg_reduce_f64(const double* clients, int64_t K, int64_t P, int64_t ld, const double* weights,
@@ -917,12 +707,10 @@ int fedavg_reduce_f64(const double* clients, int64_t K, int64_t P, int64_t ld, c
   if ((reinterpret_cast<uintptr_t>(clients) | reinterpret_cast<uintptr_t>(out) |
        reinterpret_cast<uintptr_t>(weights)) & m)
     return set_error(FEDAVG_EALIGN, "%s: fp64 buffers must be 8-byte aligned", what);
-  if (aligned16(clients) && aligned16(out) && (ld % 2) == 0) {
-    launch_production_vec<OpF64>(clients, static_cast<int>(K), ld, P, weights, out, s);
-  } else {
-    hipLaunchKernelGGL(reduce_f64_scalar_kernel, dim3(grid_for(P, kBlock)), dim3(kBlock), 0, s, clients,
-                       static_cast<int>(K), ld, P, weights, out);
-  }
+  if (aligned16(clients) && aligned16(out) && (ld % 2) == 0)
+    return launch_production<OpF64>({clients, static_cast<int>(K), ld, P, weights, out, s}, what);
+  hipLaunchKernelGGL(reduce_f64_scalar_kernel, dim3(grid_for(P, kBlock)), dim3(kBlock), 0, s, clients,
+                     static_cast<int>(K), ld, P, weights, out);
   return launch_status(what);
 }
 
@@ -936,11 +724,8 @@ static int reduce_half_entry(bool bf16, const uint16_t* clients, int64_t K, int6
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool vec = aligned16(clients) && aligned16(out) && (ld % 8) == 0;
   if (vec) {
-    if (bf16)
-      launch_production_vec<OpHalfPk<BF16Pk>>(clients, static_cast<int>(K), ld, P, weights, out, s);
-    else
-      launch_production_vec<OpHalfPk<F16Pk>>(clients, static_cast<int>(K), ld, P, weights, out, s);
-    return launch_status(what);
+    const ReduceCall c{clients, static_cast<int>(K), ld, P, weights, out, s};
+    return bf16 ? launch_production<OpHalfPk<BF16Pk>>(c, what) : launch_production<OpHalfPk<F16Pk>>(c, what);
   }
   const int64_t items = P;
   const auto* X = reinterpret_cast<const unsigned short*>(clients);
@@ -977,21 +762,18 @@ int fedavg_reduce_vec_buf(int dtype, const void* clients, int64_t K, int64_t P, 
   if (!aligned16(clients) || !aligned16(out) || (ld % lanes) != 0)
     return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned clients/out and ld %% %d == 0", what, lanes);
   const int bpl = max_blocks > 0 ? max_blocks : (1 << 30);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int k = static_cast<int>(K);
+  const ReduceCall c{clients, static_cast<int>(K), ld, P, weights, out, static_cast<hipStream_t>(stream)};
   bool ok;
   if (dtype == 2)
-    ok = launch_vec_buf<OpF64>(unroll, cols, clients, k, ld, P, weights, out, bpl, s);
+    ok = launch_vec_buf<OpF64>(unroll, cols, c, bpl);
   else if (dtype == 1)
-    ok = launch_vec_buf<OpHalfPk<BF16Pk>>(unroll, cols, clients, k, ld, P, weights, out, bpl, s);
+    ok = launch_vec_buf<OpHalfPk<BF16Pk>>(unroll, cols, c, bpl);
   else
-    ok = launch_vec_buf<OpHalfPk<F16Pk>>(unroll, cols, clients, k, ld, P, weights, out, bpl, s);
+    ok = launch_vec_buf<OpHalfPk<F16Pk>>(unroll, cols, c, bpl);
   if (!ok) return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", what, unroll, cols);
   return launch_status(what);
 }
-#endif  // FEDAVG_TUNING
 
-#ifdef FEDAVG_TUNING  // probe library only (libfedavg_amd_probe.so)
 int fedavg_reduce_half_variant(int bf16, const uint16_t* clients, int64_t K, int64_t P, int64_t ld,
                                const float* weights, uint16_t* out, int unroll, int cols, int max_blocks,
                                void* stream) {
@@ -1002,29 +784,17 @@ int fedavg_reduce_half_variant(int bf16, const uint16_t* clients, int64_t K, int
   if (!aligned16(clients) || !aligned16(out) || (ld % 8) != 0)
     return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned clients/out and ld %% 8 == 0", what);
   const int bpl = max_blocks > 0 ? max_blocks : (1 << 30);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool ok = bf16 ? launch_half_variant<OpHalfPk<BF16Pk>>(unroll, cols, clients, static_cast<int>(K), ld, P,
-                                                               weights, out, bpl, s)
-                       : launch_half_variant<OpHalfPk<F16Pk>>(unroll, cols, clients, static_cast<int>(K), ld, P,
-                                                              weights, out, bpl, s);
+  const ReduceCall c{clients, static_cast<int>(K), ld, P, weights, out, static_cast<hipStream_t>(stream)};
+  const bool ok = bf16 ? launch_half_variant<OpHalfPk<BF16Pk>>(unroll, cols, c, bpl)
+                       : launch_half_variant<OpHalfPk<F16Pk>>(unroll, cols, c, bpl);
   if (!ok) return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", what, unroll, cols);
   return launch_status(what);
 }
-#endif  // FEDAVG_TUNING
 
-#ifdef FEDAVG_TUNING  // probe library only (libfedavg_amd_probe.so)
 int fedavg_half_schedule(int64_t K, int64_t P, int* unroll, int* cols, int* nontemporal, int* launches) {
   if (K <= 0 || P < 0) return set_error(FEDAVG_EINVAL, "fedavg_half_schedule: bad sizes");
-  const Schedule sc = choose_schedule(K, P * 2 / 4);  // the fp32 problem with the same bytes per row
-  const int key = half_key(sc.unroll * 100 + sc.cols);
-  const int64_t nvec = (P + 7) / 8;
-  const int64_t span = static_cast<int64_t>(kBlock) * (key % 100);
-  const int64_t blocks = (nvec + span - 1) / span;
-  if (unroll) *unroll = key / 100;
-  if (cols) *cols = key % 100;
-  if (nontemporal) *nontemporal = sc.nt;
-  if (launches) *launches = static_cast<int>((blocks + sc.blocks_per_launch - 1) / sc.blocks_per_launch);
-  return FEDAVG_OK;
+  // fp16 and bf16 share their plan and their instances' shapes
+  return report_production<OpHalfPk<BF16Pk>>("fedavg_half_schedule", K, P, P, unroll, cols, nontemporal, launches);
 }
 #endif  // FEDAVG_TUNING
 

@@ -249,6 +249,14 @@ void launch_window(const float* clients, int K, int64_t ld, int64_t P, const flo
   }
 }
 
+// pipe 4: production's round-split launches of the plain kernel
+template <int U, int C, bool NT>
+void launch_split(const float* clients, int K, int64_t ld, int64_t P, const float* W, float* out, int max_blocks,
+                  hipStream_t s) {
+  const ReduceCall c{clients, K, ld, P, W, out, s};
+  launch_round_split(VarSplit<U, C, NT>{c}, max_blocks);
+}
+
 typedef void (*var_launcher)(const float*, int, int64_t, int64_t, const float*, float*, int, hipStream_t);
 
 // pipe: 0 = plain register batches, 1 = register double-buffering, 2 = LDS-DMA staging,
@@ -453,24 +461,19 @@ __global__ __launch_bounds__(64) void probe_clock_kernel(unsigned long long* __r
   }
 }
 
-// launch_split's equal round-split launches, with the XCD-aware order
+// VarSplit's equal round-split launches, with the XCD-aware order (no events)
 template <int U, int C, bool NT>
-void launch_split_xcd(const float* clients, int K, int64_t ld, int64_t P, const float* W, float* out, int max_blocks,
-                      hipStream_t s) {
-  const int64_t nvec = (P + 3) / 4;
-  const int64_t span = static_cast<int64_t>(kBlock) * C;
-  const int64_t resident = max_blocks > 0 ? max_blocks : resident_blocks(reduce_f32x4_xcd_kernel<U, C, NT>);
-  const int64_t blocks = (nvec + span - 1) / span;
-  const int64_t nl = (blocks + resident - 1) / resident;
-  const int64_t per = ((nvec + nl - 1) / nl + span - 1) / span * span;
-  const f32x4* X = reinterpret_cast<const f32x4*>(clients);
-  for (int64_t v0 = 0; v0 < nvec; v0 += per) {
-    const int64_t n = (nvec - v0) < per ? (nvec - v0) : per;
-    const int tail = (v0 + n == nvec) ? static_cast<int>(P & 3) : 0;
-    hipLaunchKernelGGL((reduce_f32x4_xcd_kernel<U, C, NT>), dim3(static_cast<unsigned>((n + span - 1) / span)),
-                       dim3(kBlock), 0, s, X + v0, K, ld / 4, n, tail, W, out + v0 * 4);
+struct XcdSplit {
+  static constexpr int kLanes = 4;
+  static constexpr int kSpan = kBlock * C;
+  const ReduceCall& c;
+  int64_t resident() const { return resident_blocks(reduce_f32x4_xcd_kernel<U, C, NT>); }
+  void launch(int64_t v0, int64_t n, int tail, hipEvent_t, hipEvent_t) const {
+    hipLaunchKernelGGL((reduce_f32x4_xcd_kernel<U, C, NT>), dim3(grid_for(n, kSpan)), dim3(kBlock), 0, c.s,
+                       static_cast<const f32x4*>(c.clients) + v0, c.K, c.ld / 4, n, tail,
+                       static_cast<const float*>(c.W), static_cast<float*>(c.out) + v0 * 4);
   }
-}
+};
 
 }  // namespace
 
@@ -598,8 +601,8 @@ int fedavg_reduce_f32_xcd(const float* clients, int64_t K, int64_t P, int64_t ld
     return set_error(FEDAVG_EINVAL, "%s: bad arguments", what);
   if (!aligned16(clients) || !aligned16(out) || (ld % 4) != 0)
     return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned clients/out and ld %% 4 == 0", what);
-  launch_split_xcd<4, 8, true>(clients, static_cast<int>(K), ld, P, weights, out, max_blocks,
-                               static_cast<hipStream_t>(stream));
+  const ReduceCall c{clients, static_cast<int>(K), ld, P, weights, out, static_cast<hipStream_t>(stream)};
+  launch_round_split(XcdSplit<4, 8, true>{c}, max_blocks);
   return launch_status(what);
 }
 
@@ -610,10 +613,9 @@ int fedavg_reduce_f32_buf(const float* clients, int64_t K, int64_t P, int64_t ld
     return set_error(FEDAVG_EINVAL, "%s: bad arguments", what);
   if (!aligned16(clients) || !aligned16(out) || (ld % 4) != 0)
     return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned clients/out and ld %% 4 == 0", what);
-  const int k = static_cast<int>(K);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ReduceCall c{clients, static_cast<int>(K), ld, P, weights, out, static_cast<hipStream_t>(stream)};
 #define FEDAVG_BUF_CASE(U, C, B) \
-  case (B) * 10000 + (U) * 100 + (C): launch_split_buf<U, C, B>(clients, k, ld, P, weights, out, max_blocks, s); break;
+  case (B) * 10000 + (U) * 100 + (C): launch_round_split(BufSplit<U, C, B>{c}, max_blocks); break;
   switch (block * 10000 + unroll * 100 + cols) {
     FEDAVG_BUF_CASE(4, 8, 256)
     FEDAVG_BUF_CASE(8, 4, 256)
@@ -659,8 +661,8 @@ int fedavg_reduce_f32_buf(const float* clients, int64_t K, int64_t P, int64_t ld
     // block 1256 / 1512: the 256-thread U2 x C16 kernel with co-resident
     // workgroups remapped to adjacent column groups (cu_contiguous_group,
     // 256 / 512 slots per round)
-    case 1256 * 10000 + 216: launch_split_buf<2, 16, 256, 256>(clients, k, ld, P, weights, out, max_blocks, s); break;
-    case 1512 * 10000 + 216: launch_split_buf<2, 16, 256, 512>(clients, k, ld, P, weights, out, max_blocks, s); break;
+    case 1256 * 10000 + 216: launch_round_split(BufSplit<2, 16, 256, 256>{c}, max_blocks); break;
+    case 1512 * 10000 + 216: launch_round_split(BufSplit<2, 16, 256, 512>{c}, max_blocks); break;
     default:
       return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d block=%d", what, unroll, cols, block);
   }

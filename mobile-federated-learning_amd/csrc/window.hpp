@@ -8,6 +8,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "plan_table.hpp"
 
 #include <type_traits>
 
@@ -151,30 +152,9 @@ __device__ __forceinline__ void handoff_weights(float (&wv)[4], const float* W, 
 }
 
 // ---------------------------------------------------------------------------
-// Plan tables (host).  A plan family is one constexpr table of {a, b} template
-// arguments; for_entry calls a generic lambda with the matching entry's two
-// values as std::integral_constants and says whether there was one, so the
-// lambda is instantiated for the table's entries and nothing else (the
-// product library holds plan-reachable kernels only), and every use of a
-// family -- plan, grid, workspace, launch -- names its instances through the
-// same table.
+// Plan tables of the window kernels (host; PlanEntry and for_entry:
+// plan_table.hpp).
 // ---------------------------------------------------------------------------
-struct PlanEntry {
-  int a, b;
-};
-constexpr int kAnyB = -1;
-
-template <auto& T, class F, size_t... I>
-bool for_entry_impl(int a, int b, F&& f, std::index_sequence<I...>) {
-  return ((a == T[I].a && (b == kAnyB || b == T[I].b) &&
-           (f(std::integral_constant<int, T[I].a>{}, std::integral_constant<int, T[I].b>{}), true)) ||
-          ...);
-}
-template <auto& T, class F>
-bool for_entry(int a, int b, F&& f) {
-  return for_entry_impl<T>(a, b, f, std::make_index_sequence<std::extent_v<std::remove_reference_t<decltype(T)>>>{});
-}
-
 // One-wave windows, 17..128 rows: {KMAX, VEC} by band (measurements:
 // fedavg_dist.hip's fused_plan notes).  The only place the bands are written.
 constexpr PlanEntry kWinBands[] = {{48, 4}, {64, 2}, {80, 2}, {100, 2}, {128, 1}};

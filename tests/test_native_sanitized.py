@@ -10,6 +10,9 @@
   the reserved room and below the bytes the H2D ships.  Reintroducing round
   5's descriptor-table overrun (dropping ``dbytes <= L.desc_room``) makes
   ASan abort here.
+* ``tests/native/reduce_plan_check.cpp`` (always): the row reduce's HIP-free
+  plan header (``csrc/reduce_plan.hpp``) against the plans recorded in
+  ``tests/reduce_plan_cases.txt``, its form tables and the round-split cut.
 * ``fedavg_collect_ext`` (the state_dict walk, ``verify_rows``) built with
   ``-fsanitize=address,undefined`` and the CPU suites that drive it run under
   ``LD_PRELOAD=libasan`` -- opt-in (``MFL_ASAN_TESTS=1``; it compiles a torch
@@ -43,6 +46,23 @@ def test_staging_and_packer_fuzz_under_asan_ubsan(tmp_path):
         r = subprocess.run([str(exe), "60", str(seed)], capture_output=True, text=True, timeout=300, env=env)
         assert r.returncode == 0, r.stdout + r.stderr
         assert "0 failures" in r.stdout and "ERROR" not in r.stderr, r.stdout + r.stderr
+
+
+@pytest.mark.skipif(_gxx() is None, reason="g++ not found")
+def test_reduce_plan_under_asan_ubsan(tmp_path):
+    """csrc/reduce_plan.hpp against tests/reduce_plan_cases.txt: the plan equals
+    every recorded line, every plan has a form-table entry, round_split keeps
+    its invariants and its launch count (tests/native/reduce_plan_check.cpp)."""
+    exe = tmp_path / "reduce_plan_check"
+    cmd = [_gxx(), "-std=c++17", "-O1", "-g", *SAN, f"-I{ROOT / 'include'}", f"-I{CSRC}",
+           str(ROOT / "tests" / "native" / "reduce_plan_check.cpp"), "-o", str(exe)]
+    subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    for seed in (1234, 99):
+        r = subprocess.run([str(exe), str(ROOT / "tests" / "reduce_plan_cases.txt"), str(seed)], capture_output=True,
+                           text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert " 0 failures" in r.stdout and "ERROR" not in r.stderr, r.stdout + r.stderr
 
 
 def _gcc_lib(name):
