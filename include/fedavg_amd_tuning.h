@@ -109,27 +109,12 @@ int fedavg_fpf_index_variant(const float* diffs, int64_t n_rows, int64_t ld, int
                              const float* g_mat, float* fpf, double* workspace, int64_t workspace_elems, int unroll,
                              int cols, int row_groups, void* stream);
 
-/*
- * HBM read-ceiling probe (measurement only): stream `nvec` 16-B vectors of a
- * device buffer with no reduction structure, in `launches` equal launches of
- * `blocks` workgroups each.  mode 0: grid-stride, nontemporal; 1: one
- * contiguous range per block, nontemporal; 2: as 1 with default-policy loads.
- * `sink` needs `blocks` floats (written only on an impossible value match).
- */
 /* The production U4 x C8 nt reduce with an XCD-aware workgroup order (XCD x
  * takes one contiguous run of column slices); same round-split launches, same
  * bits.  Measurement only. */
 int fedavg_reduce_f32_xcd(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
                           int max_blocks, void* stream);
 
-/*
- * Zero-copy device-client reduce (fedavg_reduce_segments_f32, same tables and
- * workspaces) with an explicit schedule: unroll client pointers per load
- * batch x cols 16-B slices per thread, (U, C) in {(4,8) production, (8,4),
- * (2,8), (4,4), (8,2), (16,2), (2,16), (1,16)}; units of 1,024 x cols
- * columns; round-split launches of <= blocks_per_cu x CUs workgroups
- * (0 = one launch).  Same bits as the production call.
- */
 /*
  * Host-side phase times of this thread's last fedavg_device_round_f32 call
  * (probe library build only): cumulative microseconds at up to `cap` marks
@@ -139,6 +124,15 @@ int fedavg_reduce_f32_xcd(const float* clients, int64_t K, int64_t P, int64_t ld
  * reduce launches.  Returns the number of marks written.
  */
 int fedavg_device_round_phases(double* us, int cap);
+
+/*
+ * Zero-copy device-client reduce (fedavg_reduce_segments_f32, same tables and
+ * workspaces) with an explicit schedule: unroll client pointers per load
+ * batch x cols 16-B slices per thread, (U, C) in {(4,8) production, (8,4),
+ * (2,8), (4,4), (8,2), (16,2), (2,16), (1,16)}; units of 1,024 x cols
+ * columns; round-split launches of <= blocks_per_cu x CUs workgroups
+ * (0 = one launch).  Same bits as the production call.
+ */
 int fedavg_reduce_segments_f32_variant(const int64_t* client_ptrs, const int64_t* key_numel, const int64_t* key_offset,
                                        const int64_t* key_kind, int64_t n_keys, int64_t K, const float* weights,
                                        float* out, void* host_ws, void* dev_ws, int64_t ws_bytes, int unroll, int cols,
@@ -167,11 +161,6 @@ int fedavg_client_sqdist_segments_f32_variant(const int64_t* client_ptrs, const 
 int fedavg_reduce_f32_buf(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,
                           int unroll, int cols, int block, int max_blocks, void* stream);
 
-/* The distance pass (fedavg_client_sqdist_f32) through buffer descriptors:
- * per block, one descriptor per client row and one for glob whose record
- * count ends at the last float4 (lanes past it read 0); (unroll, cols) in
- * {(4,8), (8,4), (2,16), (2,8), (8,8)}; round-split launches of <= max_blocks
- * blocks (0 = one launch).  Same workspace as fedavg_client_sqdist_f32. */
 /* fedavg_reduce_sqdist_f32 with an explicit kernel (cols = the code) and,
  * for the tile kernels, workgroups per CU (0 = as many as are resident);
  * workspace >= K x the launch's workgroups (one-wave windows: waves)
@@ -195,6 +184,12 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
                                      const float* weights, float* out, double* workspace,
                                      int64_t workspace_elems, double* sumsq, int cols,
                                      int blocks_per_cu, void* stream);
+
+/* The distance pass (fedavg_client_sqdist_f32) through buffer descriptors:
+ * per block, one descriptor per client row and one for glob whose record
+ * count ends at the last float4 (lanes past it read 0); (unroll, cols) in
+ * {(4,8), (8,4), (2,16), (2,8), (8,8)}; round-split launches of <= max_blocks
+ * blocks (0 = one launch).  Same workspace as fedavg_client_sqdist_f32. */
 int fedavg_client_sqdist_buf(const float* clients, int64_t K, int64_t P, int64_t ld, const float* glob,
                              double* workspace, int64_t workspace_elems, double* sumsq, int unroll, int cols,
                              int max_blocks, void* stream);
@@ -207,6 +202,13 @@ int fedavg_client_sqdist_buf(const float* clients, int64_t K, int64_t P, int64_t
 int fedavg_reduce_vec_buf(int dtype, const void* clients, int64_t K, int64_t P, int64_t ld, const void* weights,
                           void* out, int unroll, int cols, int max_blocks, void* stream);
 
+/*
+ * HBM read-ceiling probe (measurement only): stream `nvec` 16-B vectors of a
+ * device buffer with no reduction structure, in `launches` equal launches of
+ * `blocks` workgroups each.  mode 0: grid-stride, nontemporal; 1: one
+ * contiguous range per block, nontemporal; 2: as 1 with default-policy loads.
+ * `sink` needs `blocks` floats (written only on an impossible value match).
+ */
 int fedavg_probe_read_f32x4(const float* buf, int64_t nvec, int mode, int blocks, int launches, float* sink,
                             void* stream);
 

@@ -61,6 +61,7 @@ CSRC_WINDOW = CSRC_DIR / "window.hpp"  # what the rows and zero-copy window kern
 CSRC_STAGING = CSRC_DIR / "staging.hpp"  # host-side staged layouts (also g++-built by tests/native)
 CSRC_PLAN_TABLE = CSRC_DIR / "plan_table.hpp"  # PlanEntry / for_entry of every plan family
 CSRC_REDUCE_PLAN = CSRC_DIR / "reduce_plan.hpp"  # the row reduce's plan, forms and round-split cut (also g++-built)
+CSRC_SEGMENTS_PLAN = CSRC_DIR / "segments_plan.hpp"  # the zero-copy passes' plans, forms and bounds (also g++-built)
 CSRC_VEC_RULES = CSRC_DIR / "fused_vec_rules.hpp"  # dtype rules and bands of the fused-vec and seg-vec kernels
 CSRC_COLLECT = CSRC_DIR / "fedavg_collect_ext.cpp"
 COLLECT_NAME = "fedavg_collect_ext"
@@ -84,6 +85,10 @@ HIPCC_FLAGS = [
     "-fno-fast-math",
     "-Wall",
     "-pthread",
+    # host code only: loops start on a 64-byte line.  stage_device_round's 61-byte pointer-fill loop (staging.hpp)
+    # ran 22 % slower in a build that happened to place it across one (resnet56 x 100 device round: 48 vs 42 us)
+    "-Xarch_host",
+    "-falign-loops=64",
 ]
 
 
@@ -96,8 +101,8 @@ def hipcc_path() -> str:
 
 def sources():
     return [*HIP_SOURCES, *PROBE_SOURCES, *FUSEDVEC_SOURCES, *SEGVEC_SOURCES, *CLIENTVEC_SOURCES, CSRC_HOST,
-            CSRC_COMMON, CSRC_WINDOW, CSRC_STAGING, CSRC_PLAN_TABLE, CSRC_REDUCE_PLAN, CSRC_VEC_RULES,
-            INCLUDE / "fedavg_amd.h",
+            CSRC_COMMON, CSRC_WINDOW, CSRC_STAGING, CSRC_PLAN_TABLE, CSRC_REDUCE_PLAN, CSRC_SEGMENTS_PLAN,
+            CSRC_VEC_RULES, INCLUDE / "fedavg_amd.h",
             INCLUDE / "fedavg_amd_tuning.h", INCLUDE / "fedavg_amd_fusedvec.h", INCLUDE / "fedavg_amd_segvec.h",
             INCLUDE / "fedavg_amd_clientvec.h", Path(__file__)]
 

@@ -1250,8 +1250,8 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
 template <int NSMAX, int PF, int MODE = 0>
 int64_t fused_winf_grid(int64_t K, int64_t P) {
   const int ns = static_cast<int>((K + 63) / 64);
-  return persistent_grid(split_per_cu(resident_blocks(reduce_sqdist_winf_kernel<NSMAX, PF, MODE>, 64 * ns)), cu_count(),
-                         (P + 63) / 64);
+  return persistent_grid(split_per_cu(resident_blocks(reduce_sqdist_winf_kernel<NSMAX, PF, MODE>, 64 * ns), cu_count()),
+                         cu_count(), (P + 63) / 64);
 }
 
 template <int NSMAX, int PF, int MODE = 0>
@@ -1748,10 +1748,7 @@ int fedavg_reduce_sqdist_f32(const float* clients, int64_t K, int64_t P, int64_t
     return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned rows and ld %% 4 == 0 (reduce alone: fedavg_reduce_f32)",
                      what);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (P == 0) {
-    const hipError_t e = hipMemsetAsync(sumsq, 0, static_cast<size_t>(K) * sizeof(double), s);
-    return e == hipSuccess ? FEDAVG_OK : set_error(-static_cast<int>(e), "%s: hipMemsetAsync failed", what);
-  }
+  if (P == 0) return zero_sums(kRowsLaunch, what, sumsq, K, s);
   const FusedPlan pl = fused_plan(K, P);
   if (pl.kind != kFusedNone && aligned4(out) && aligned4(weights)) {
     const FusedCall call{clients, K, P, ld, weights, out, workspace, workspace_elems, sumsq, s, what};

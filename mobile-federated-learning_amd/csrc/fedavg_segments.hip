@@ -21,75 +21,30 @@
 #include "common.hpp"
 #include "window.hpp"
 #include "staging.hpp"
+#include "reduce_plan.hpp"
+#include "segments_plan.hpp"
 
 #include <chrono>
 #include <vector>
 
 namespace {
 using namespace fedavg_impl;
-// the host-side staged layouts (key table, pointer table, descriptor table,
-// workspace sizes): staging.hpp, which g++ also builds for the sanitizer fuzz
+// HIP-free, g++-built for the sanitizer checks: the plans, forms and unit widths (segments_plan.hpp),
+// the round-split cut (reduce_plan.hpp), the staged layouts and workspace sizes (staging.hpp)
 using fedavg_staging::kBool;
 using fedavg_staging::kI16;
 using fedavg_staging::kI32;
 using fedavg_staging::kI64;
 using fedavg_staging::kI8;
 using fedavg_staging::kRaw;
-using fedavg_staging::kSegDescMaxBytes;
-using fedavg_staging::kSegUnitMapMax;
-using fedavg_staging::kSegWinTablePad;
 using fedavg_staging::kU8;
-using fedavg_staging::kWinRsrcFlags;
 using fedavg_staging::IntKey;
-using fedavg_staging::round16;
 using fedavg_staging::round_ws;
 using fedavg_staging::RoundWs;
-using fedavg_staging::seg_desc_bytes;
 using fedavg_staging::SegKey;
 
 typedef f32x4 f32x4_a4 __attribute__((aligned(4)));  // dword-aligned 16-B vector (client tensors, outputs)
-
-// U4 x C4: units of 4,096 columns.  The multi-key sweep (scripts/
-// segments_probe.py --model, profiles/r01_segments_models.jsonl) measured
-// resnet56 x 100 at 113 us against 161 us for U4 x C8 (more units for the
-// mid-size keys, cheaper masked tails), FEMNIST 19.1 vs 20.2 us, and the flat
-// 25M-element key level (6,256 vs 6,226 GB/s); U2 x C16 loses 2.7x on resnet56.
-constexpr int kSegU = 4;
-constexpr int kSegC = 4;
-constexpr int64_t kSegSpan = static_cast<int64_t>(kBlock) * kSegC * 4;  // columns per unit
-// Round 3: full units run reduce_raw_unit's STYLE 2 -- loads and products
-// interleaved in (row, slice) order with two loads of the wave in flight
-// (a sched_barrier keeps the compiler from bunching a batch's loads) -- in
-// launches of 2 workgroups per CU.  Interleaved against the round-2 schedule
-// (U4 x C4, batch loads, 3 per CU) on separately allocated client tensors
-// (scripts/segments_probe.py --model, profiles/r03/seg/models.jsonl): flat
-// 100 x 25M 1.580 -> 1.444 ms (6,393 -> 6,996 GB/s), resnet18_gn x 500
-// (62 keys) 3.683 -> 3.285 ms, resnet56 x 100 (small units, 8 per CU)
-// 101.8 -> 94.6 us, FEMNIST x 10 17.4 -> 17.2 us; 3 per CU 1.479 ms, 4 loads
-// in flight 1.498 ms, 64 KiB units (U2 x C16, 1 per CU) 1.473 ms.
-constexpr int kSegStyle = 2;
-constexpr int kSegBlocksPerCU = 2;
-// Small models (fewer than 4 units of 4,096 columns per CU): units of 1,024
-// columns (U4 x C1), up to 8 blocks per CU per launch -- 4x the workgroups.
-// rocprofv3 kernel time per call (scripts/segments_probe.py --model,
-// profiles/r02/sweeps/segments_small_models.json): resnet56 x 100 (350 keys)
-// 90.0 -> 77.1 us, FEMNIST x 10 12.1 -> 10.9 us, MNIST-LR x 10 6.3 -> 4.3 us;
-// the flat 25M key stays on C4 (1,577 vs 1,717 us at C1).
-constexpr int kSegSmallC = 1;
-constexpr int kSegSmallBlocksPerCU = 8;
-constexpr int64_t kSegSmallUnitsPerCU = 4;
-constexpr int64_t kSegSmallSpan = static_cast<int64_t>(kBlock) * kSegSmallC * 4;
-// :291 on device-resident clients: U4 client rows per load batch; units of
-// 8,192 columns (C8), or the small-model units of 1,024 (C1).  rocprofv3
-// kernel time (scripts/segments_dist_probe.py, profiles/r02/sweeps/
-// segments_dist.json): flat 100 x 25M 1,638 us at U4 x C8 vs 1,656 for the
-// round-1 form (one client at a time, C4) and 1,681 at U4 x C4; resnet56 x 100
-// 84.5 us at U4 x C1 vs 100.8 (one client at a time, C4); FEMNIST 13.8 vs 14.5.
-constexpr int kSegDistU = 4;
-constexpr int kSegDistC = 8;
-constexpr int64_t kSegDistSpan = static_cast<int64_t>(kBlock) * kSegDistC * 4;
-constexpr int64_t kSegSpanMaxBytes = static_cast<int64_t>(kBlock) * 16 * 16;  // widest unit (C = 16), bytes
-
+static_assert(kSegBlock == kBlock && kReduceBlock == kBlock, "the HIP-free plans' workgroup size");
 
 // the key owning unit u (keys without units share their successor's start
 // and lose the tie)
@@ -632,8 +587,6 @@ __global__ __launch_bounds__(kBlock, LADDR && S != 32 ? 6 : 1) void reduce_sqdis
 // pointer table is padded by kSegWinTablePad entries so every group's 8
 // addresses load unconditionally (a padding row's is never dereferenced).
 // ---------------------------------------------------------------------------
-constexpr int64_t kSegWinMinPerWave = 16;  // windows per wave below which the LDS-DMA tiles keep the round
-
 // DESC (round 5): every fast window's K client descriptors come from a
 // descriptor table staged with the key table -- desc[j * KMAX + i] = {client
 // i's address of key j (lo, hi), the key's byte length (0 for padding rows
@@ -1134,43 +1087,17 @@ __global__ __launch_bounds__(64 * NSMAX, win_min_waves(64, 1)) void reduce_sqdis
   }
 }
 
-constexpr int64_t kSegSplitMaxK = 1024;  // the split-row windows' reach (16 waves of 64 clients)
-
-// Probe library only (tuning_knob, common.hpp): FEDAVG_SEGWINF_STAMPS=1
-// launches the hand-off kernel's timeline build (MODE 8; the partials grow by
-// winn_stamp_elems)
+// the planner's knobs (SegKnobs), read once: probe library only (tuning_knob; the product library keeps the constants)
+inline const SegKnobs& seg_knobs() {
+  static const SegKnobs k{tuning_knob("FEDAVG_SEGWIN", 1) != 0,
+                          tuning_knob("FEDAVG_SEGWIN_MIN_PER_WAVE", kSegWinMinPerWave),
+                          tuning_knob("FEDAVG_SEG_SPLIT_MIN_K", kSegSplitMinK)};
+  return k;
+}
+// FEDAVG_SEGWINF_STAMPS=1 launches the hand-off kernel's timeline build (MODE 8; + winn_stamp_elems partials)
 inline bool seg_split_stamps() {
   static const bool on = tuning_knob("FEDAVG_SEGWINF_STAMPS", 0) == 1;
   return on;
-}
-
-// windows per wave below which the LDS-DMA tiles keep the round
-// (kSegWinMinPerWave; the probe library's FEDAVG_SEGWIN_MIN_PER_WAVE overrides it)
-inline int64_t segwin_min_per_wave() {
-  static const int64_t v = tuning_knob("FEDAVG_SEGWIN_MIN_PER_WAVE", kSegWinMinPerWave);
-  return v;
-}
-
-// the probe library's FEDAVG_SEGWIN=0 keeps the LDS-DMA tiles for every device round
-inline bool segwin_disabled() {
-  static const bool off = tuning_knob("FEDAVG_SEGWIN", 1) == 0;
-  return off;
-}
-
-// Round 3 ran 81-100 clients on the 128 x 1 window instance because its
-// 100 x 2 form spilled (device round 100 x 25M 3.66 ms, profiles/r03/segwin/);
-// the spill was the slow path's per-lane 64-bit element addresses, gone with
-// the buffer-load form (232 VGPRs, no scratch), so 81-100 clients take 100 x 2
-// as on rows (kWinBands, window.hpp)
-constexpr int kSegFusedMaxK = kBlock;
-
-// tile width by clients (32 above 128, 64 above 64, 128 up to 64, 256 up to
-// 16): every width keeps <= 8 load slots per thread
-inline int seg_fused_cols(int64_t K) { return K > 128 ? 32 : (K > 64 ? 64 : (K > 16 ? 128 : 256)); }
-
-inline int64_t seg_fused_lds_bytes(int64_t K, int S, bool laddr = false) {
-  const int64_t b = (K + 1) * S * 4 + (laddr ? K * 8 : 0);  // LADDR: + the key's K client addresses
-  return b > kBlock * 8 ? b : kBlock * 8;
 }
 
 // The tile kernel's two forms: MAP = false (the key of a unit by search, the
@@ -1181,22 +1108,14 @@ int seg_fused_per_cu(int64_t K) {  // 0: the tile does not fit LDS
   return lds_blocks_per_cu(reduce_sqdist_segments_f32_kernel<S, MAP, MAP>, kBlock, seg_fused_lds_bytes(K, S, MAP));
 }
 
-// the tile widths of seg_fused_cols; f(S)
-constexpr PlanEntry kSegTiles[] = {{32, 0}, {64, 0}, {128, 0}, {256, 0}};
-
-int64_t units_of(const int64_t* numel, int64_t n_keys, int64_t span = kSegSpan) {
-  int64_t units = 0;
-  for (int64_t j = 0; j < n_keys; ++j) units += (numel[j] + span - 1) / span;
-  return units;
-}
-
-// a model with fewer than kSegSmallUnitsPerCU units of kSegSpan per CU takes
-// the narrow units (reduce and :291 alike)
-bool segments_small(const int64_t* numel, int64_t n_keys) {
-  if (!numel || n_keys <= 0) return false;
-  for (int64_t j = 0; j < n_keys; ++j)
-    if (numel[j] < 0) return false;  // stage_tables reports it
-  return units_of(numel, n_keys) < kSegSmallUnitsPerCU * static_cast<int64_t>(cu_count());
+// the staged tables in dev_ws (stage_tables' and round_ws's layout alike): the keys, then the key-major pointers
+struct SegTables {
+  const SegKey* keys;
+  const int64_t* ptrs;
+};
+inline SegTables seg_tables(const void* dev_ws, int64_t n_keys) {
+  const char* db = static_cast<const char*>(dev_ws);
+  return {reinterpret_cast<const SegKey*>(db), reinterpret_cast<const int64_t*>(db + n_keys * int64_t(sizeof(SegKey)))};
 }
 
 // Validate the tables, write the device tables into host_ws, copy them to
@@ -1233,50 +1152,23 @@ int64_t stage_tables(const char* what, const int64_t* client_ptrs, const int64_t
   return units;
 }
 
-// round-split: equal launches of at most `cap` workgroups (production: 3 x
-// CUs, the reduce's schedule); cap <= 0 = one launch
-template <int U, int C, int STYLE = 0>
-void launch_reduce_segments(const SegKey* keys, const int64_t* ptrs, int64_t n_keys, int64_t units, int64_t K,
-                            const float* weights, float* out, int64_t cap, hipStream_t s) {
-  if (cap <= 0) cap = units;
-  const int64_t nl = (units + cap - 1) / cap;
-  const int64_t per = (units + nl - 1) / nl;
-  for (int64_t u0 = 0; u0 < units; u0 += per) {
-    const int64_t nb = units - u0 < per ? units - u0 : per;
-    hipLaunchKernelGGL((reduce_segments_f32_kernel<U, C, STYLE>), dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, s, keys,
-                       ptrs, n_keys, u0, static_cast<int>(K), weights, out);
-  }
-}
-
-// The fused pass a round takes: the wave-owned windows for 17-128 clients
-// when every key is fp32 and each wave gets at least segwin_min_per_wave()
-// windows, else the LDS-DMA tiles.  `span` is the unit width the key table is
-// staged with.
-struct SegFusedPlan {
-  bool win;
-  int kmax;
-  int64_t span, waves;
-};
-
-// 257-1024 clients fuse only on the split-row windows: 32-bit buffer offsets
-// per key, window indices in 32 bits
-inline bool seg_split_ok(const int64_t* numel, int64_t n_keys) {
-  if (!numel || n_keys <= 0 || n_keys >= (int64_t(1) << 31)) return false;
-  for (int64_t j = 0; j < n_keys; ++j)
-    if (numel[j] < 0 || numel[j] >= (int64_t(1) << 30)) return false;
-  return units_of(numel, n_keys, 64) < (int64_t(1) << 31);
-}
-
-// 129-256 clients take the zero-copy split windows too when every workgroup
-// gets >= kSegSplitMinPerBlock windows (round 6; profiles/r06/seg160/, seg129/,
-// resnet18_gn-shaped device rounds, ms, tiles vs split windows: 129 2.07 vs
-// 1.46; 150 2.29 vs 1.49; 160 2.44 vs 1.43; 200 2.90 vs 1.71; 256 4.12 vs
-// 2.10; the one-wave windows keep <= 128: 100 0.79 vs 1.06, 120 0.97 vs 1.11)
-constexpr int64_t kSegSplitMinK = 129, kSegSplitMinPerBlock = 8;
-// the probe library's FEDAVG_SEG_SPLIT_MIN_K overrides kSegSplitMinK
-inline int64_t seg_split_min_k() {
-  static const int64_t v = tuning_knob("FEDAVG_SEG_SPLIT_MIN_K", kSegSplitMinK);
-  return v;
+// The unfused reduce on staged tables: the plan's entry of `Forms` in round-split launches of at most
+// blocks_per_cu x CUs workgroups, one unit each (round_split with span 1, reduce_plan.hpp; 0 = one launch).
+// A template: its kernels are first instantiated where an entry point names it, after the pointer
+// reduce's, the order the kernels' recorded code hashes come from.
+template <auto& Forms, int STYLE>
+int launch_segments_reduce(const char* what, const SegPassPlan& pl, const SegTables& t, int64_t n_keys, int64_t units,
+                           int64_t K, const float* weights, float* out, hipStream_t s) {
+  const int64_t cap = pl.blocks_per_cu > 0 ? static_cast<int64_t>(pl.blocks_per_cu) * cu_count() : units;
+  if (!for_entry<Forms>(pl.unroll, pl.cols, [&](auto u, auto c) {
+        for_each_launch(round_split(units, 1, cap), units, 0, [&](int64_t u0, int64_t nb, int, bool, bool) {
+          hipLaunchKernelGGL((reduce_segments_f32_kernel<decltype(u)::value, decltype(c)::value, STYLE>),
+                             dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, s, t.keys, t.ptrs, n_keys, u0,
+                             static_cast<int>(K), weights, out);
+        });
+      }))
+    return set_error(FEDAVG_EMODE, "%s: plan U%d x C%d names no kernel instance", what, pl.unroll, pl.cols);
+  return launch_status(what);
 }
 
 const LaunchCtx kSegLaunch{set_error, launch_status, "%s: partials need %lld doubles",
@@ -1318,9 +1210,9 @@ struct SegSplitInstance {  // split-row windows: workgroups of ceil(K / 64) wave
     // library's FEDAVG_SEGWINN_PER_CU caps it instead
     static const int64_t per_cu_knob = tuning_knob("FEDAVG_SEGWINN_PER_CU", 0);
     const int64_t cus = cu_count();
-    return persistent_grid(per_cu_knob > 0 ? std::min(per_cu_knob, res / cus) : split_per_cu(res), cus, units);
+    return persistent_grid(per_cu_knob > 0 ? std::min(per_cu_knob, res / cus) : split_per_cu(res, cus), cus, units);
   }
-  static int launch(const SegFusedPlan& p, const SegCall& c) {
+  static int launch(const RoundPlan& p, const SegCall& c) {
     if (p.waves <= 0) return set_error(FEDAVG_EMODE, "%s: the split window kernel is not resident", c.what);
     if (c.K < 2) return set_error(FEDAVG_EMODE, "%s: the split windows take K >= 2", c.what);
     const dim3 grid(static_cast<unsigned>(p.waves)), block(static_cast<unsigned>(64 * ((c.K + 63) / 64)));
@@ -1345,7 +1237,7 @@ struct SegWinInstance {  // one-wave windows, 4 waves per workgroup: waves
     return window_waves(resident_blocks(reduce_sqdist_segwin_kernel<KMAX, VEC, 4, true>, 256) / cu_count(), cu_count(),
                         units, 4);
   }
-  static int launch(const SegFusedPlan& p, const SegCall& c) {
+  static int launch(const RoundPlan& p, const SegCall& c) {
     const dim3 grid(static_cast<unsigned>(p.waves / 4)), block(256);
     const int k32 = static_cast<int>(c.K);
     return seg_launch(c, p.waves, 0, [&] {
@@ -1365,7 +1257,7 @@ struct SegTileInstance {  // LDS-DMA tiles; the form (MAP) by whether the round 
     const int per_cu = std::max(seg_fused_per_cu<S, false>(K), seg_fused_per_cu<S, true>(K));
     return persistent_grid(per_cu > 0 ? per_cu : 1, cu_count(), units);
   }
-  static int launch(const SegFusedPlan&, const SegCall& c) {
+  static int launch(const RoundPlan&, const SegCall& c) {
     const auto go = [&](auto map) {
       constexpr bool MAP = decltype(map)::value;
       const int per_cu = seg_fused_per_cu<S, MAP>(c.K);
@@ -1386,7 +1278,7 @@ struct SegTileInstance {  // LDS-DMA tiles; the form (MAP) by whether the round 
 // columns); false: it names none.  The only walk over the zero-copy forms:
 // the plan's waves, the partials' bound and the launch come through here.
 template <class F>
-bool with_seg_instance(const SegFusedPlan& p, int64_t K, F&& f) {
+bool with_seg_instance(const RoundPlan& p, int64_t K, F&& f) {
   if (p.win && p.kmax < 0)
     return for_split(static_cast<int>((K + 63) / 64), [&](auto nsmax, auto pf) {
       f(SegSplitInstance<decltype(nsmax)::value, decltype(pf)::value>{});
@@ -1399,53 +1291,20 @@ bool with_seg_instance(const SegFusedPlan& p, int64_t K, F&& f) {
                               [&](auto s, auto) { f(SegTileInstance<decltype(s)::value>{}); });
 }
 
-inline int64_t seg_parts(const SegFusedPlan& p, int64_t K, int64_t units) {  // 0: no instance, or not resident
+inline int64_t seg_parts(const RoundPlan& p, int64_t K, int64_t units) {  // 0: no instance, or not resident
   int64_t n = 0;
   with_seg_instance(p, K, [&](auto inst) { n = decltype(inst)::parts(K, units); });
   return n;
 }
 
-SegFusedPlan seg_fused_plan(const int64_t* numel, int64_t n_keys, int64_t K, bool all_raw) {
-  const PlanEntry* band = win_band_of(K);  // {KMAX, VEC}, nullptr outside 17..128
-  SegFusedPlan p{false, band ? band->a : 0, seg_fused_cols(K), 0};
-  const SegFusedPlan split{true, -1, 64, 0};  // kmax -1: the split-row windows
-  if (K >= seg_split_min_k() && K >= 2 && K <= kSegFusedMaxK && all_raw && seg_split_ok(numel, n_keys)) {
-    const int64_t units = units_of(numel, n_keys, 64);
-    const int64_t blocks = seg_parts(split, K, units);
-    if (blocks > 0 && units >= kSegSplitMinPerBlock * blocks) {
-      p = split;
-      p.waves = blocks;
-      return p;
-    }
-  }
-  if (K > kSegFusedMaxK) {
-    if (K <= kSegSplitMaxK && all_raw && seg_split_ok(numel, n_keys)) {
-      p = split;
-      p.waves = seg_parts(split, K, units_of(numel, n_keys, 64));
-    }
-    return p;
-  }
-  // the windows address a key's bytes with 32-bit buffer offsets
-  bool small_keys = numel != nullptr;
-  for (int64_t j = 0; small_keys && j < n_keys; ++j) small_keys = numel[j] < (int64_t(1) << 30);
-  if (band && all_raw && small_keys && n_keys > 0 && n_keys < (int64_t(1) << 31) && !segwin_disabled()) {
-    const SegFusedPlan win{true, band->a, 64 * band->b, 0};
-    const int64_t wunits = units_of(numel, n_keys, win.span);
-    const int64_t waves = seg_parts(win, K, wunits);
-    if (waves > 0 && wunits >= segwin_min_per_wave() * waves && wunits < (int64_t(1) << 31)) {
-      p = win;
-      p.waves = waves;
-    }
-  }
-  return p;
+// the planner (segments_plan.hpp) on this device: the library's knobs, the instance tags' occupancy answers
+inline RoundPlan seg_fused_plan(const int64_t* numel, int64_t n_keys, int64_t K, bool all_raw) {
+  return seg_fused_plan(numel, n_keys, K, all_raw, seg_knobs(), seg_parts);
 }
 
 // The fused launch (+ the sums' finalize) on tables staged with plan.span
-int launch_seg_fused(const SegFusedPlan& p, const SegCall& c) {
-  if (c.units == 0) {
-    const hipError_t e = hipMemsetAsync(c.sumsq, 0, static_cast<size_t>(c.K) * sizeof(double), c.s);
-    return e == hipSuccess ? FEDAVG_OK : set_error(-static_cast<int>(e), "%s: hipMemsetAsync failed", c.what);
-  }
+int launch_seg_fused(const RoundPlan& p, const SegCall& c) {
+  if (c.units == 0) return zero_sums(kSegLaunch, c.what, c.sumsq, c.K, c.s);
   // beyond kSegFusedMaxK clients only the split-row windows fuse: the tile
   // kernel loads at most kBlock client addresses per workgroup
   if (c.K > kSegFusedMaxK && !(p.win && p.kmax < 0))
@@ -1473,7 +1332,6 @@ int launch_seg_fused(const SegFusedPlan& p, const SegCall& c) {
 // limits: staging.hpp; a tile round of more than kSegUnitMapMax units at
 // 17-128 clients takes the windows)
 
-
 // a fused round's integer / bool keys as fp32 columns of the [K, S] scratch:
 // one wave per (key, client) item, the packers' static_cast (fedavg_pack.hip)
 __global__ __launch_bounds__(64) void int_keys_to_f32_kernel(const IntKey* __restrict__ ik,
@@ -1496,9 +1354,7 @@ int64_t fedavg_segments_workspace(int64_t K, int64_t n_keys) {
 }
 
 int64_t fedavg_segments_partials(const int64_t* key_numel, int64_t n_keys, int64_t K) {
-  if (!key_numel || n_keys <= 0 || K <= 0) return 0;
-  return K * units_of(key_numel, n_keys, segments_small(key_numel, n_keys) ? kSegSmallSpan : kSegDistSpan) *
-         (kBlock / 64);
+  return segments_dist_partials(key_numel, n_keys, K, cu_count());
 }
 
 int fedavg_reduce_ptrs_f32(const float* const* client_ptrs, int64_t K, int64_t P, const float* weights,
@@ -1509,22 +1365,17 @@ int fedavg_reduce_ptrs_f32(const float* const* client_ptrs, int64_t K, int64_t P
   if (P == 0) return FEDAVG_OK;
   if (!aligned4(out) || !aligned4(weights)) return set_error(FEDAVG_EALIGN, "%s: out/weights misaligned", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool small = (P + kSegSpan - 1) / kSegSpan < kSegSmallUnitsPerCU * static_cast<int64_t>(cu_count());
-  const int64_t span = small ? static_cast<int64_t>(kBlock) * kSegSmallC * 4 : kSegSpan;
-  const int64_t units = (P + span - 1) / span;
-  const int64_t cap = static_cast<int64_t>(small ? kSegSmallBlocksPerCU : kSegBlocksPerCU) * cu_count();
-  const int64_t nl = (units + cap - 1) / cap;
-  const int64_t per = (units + nl - 1) / nl;
+  const SegPassPlan pl = segments_reduce_plan(segments_small(&P, 1, cu_count()));  // the one key's units
+  const int64_t units = (P + pl.span - 1) / pl.span;
   const auto* ptrs = reinterpret_cast<const int64_t*>(client_ptrs);
-  for (int64_t u0 = 0; u0 < units; u0 += per) {
-    const int64_t nb = units - u0 < per ? units - u0 : per;
-    if (small)
-      hipLaunchKernelGGL((reduce_ptrs_f32_kernel<kSegU, kSegSmallC>), dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0,
-                         s, ptrs, P, u0, static_cast<int>(K), weights, out);
-    else
-      hipLaunchKernelGGL((reduce_ptrs_f32_kernel<kSegU, kSegC>), dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, s,
-                         ptrs, P, u0, static_cast<int>(K), weights, out);
-  }
+  if (!for_entry<kSegReduceForms>(pl.unroll, pl.cols, [&](auto u, auto c) {
+        const RoundSplit cut = round_split(units, 1, static_cast<int64_t>(pl.blocks_per_cu) * cu_count());
+        for_each_launch(cut, units, 0, [&](int64_t u0, int64_t nb, int, bool, bool) {
+          hipLaunchKernelGGL((reduce_ptrs_f32_kernel<decltype(u)::value, decltype(c)::value>),
+                             dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, s, ptrs, P, u0, int(K), weights, out);
+        });
+      }))
+    return set_error(FEDAVG_EMODE, "%s: plan U%d x C%d names no kernel instance", what, pl.unroll, pl.cols);
   return launch_status(what);
 }
 
@@ -1535,21 +1386,12 @@ int fedavg_reduce_segments_f32(const int64_t* client_ptrs, const int64_t* key_nu
   if (!weights || !out) return set_error(FEDAVG_EINVAL, "%s: null weights/out", what);
   if (!is_device_memory(out)) return set_error(FEDAVG_EINVAL, "%s: out must be device memory", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool small = segments_small(key_numel, n_keys);
-  const int64_t span = small ? kSegSmallSpan : kSegSpan;
+  const SegPassPlan pl = segments_reduce_plan(segments_small(key_numel, n_keys, cu_count()));
   const int64_t units = stage_tables(what, client_ptrs, key_numel, key_offset, key_kind, n_keys, K, host_ws, dev_ws,
-                                     ws_bytes, s, span);
+                                     ws_bytes, s, pl.span);
   if (units <= 0) return static_cast<int>(units);
-  const auto* keys = static_cast<const SegKey*>(dev_ws);
-  const auto* ptrs = reinterpret_cast<const int64_t*>(static_cast<const char*>(dev_ws) +
-                                                      n_keys * static_cast<int64_t>(sizeof(SegKey)));
-  if (small)
-    launch_reduce_segments<kSegU, kSegSmallC, kSegStyle>(keys, ptrs, n_keys, units, K, weights, out,
-                                                         static_cast<int64_t>(kSegSmallBlocksPerCU) * cu_count(), s);
-  else
-    launch_reduce_segments<kSegU, kSegC, kSegStyle>(keys, ptrs, n_keys, units, K, weights, out,
-                                                    static_cast<int64_t>(kSegBlocksPerCU) * cu_count(), s);
-  return launch_status(what);
+  const SegTables t = seg_tables(dev_ws, n_keys);
+  return launch_segments_reduce<kSegReduceForms, kSegStyle>(what, pl, t, n_keys, units, K, weights, out, s);
 }
 
 int fedavg_client_sqdist_segments_f32(const int64_t* client_ptrs, const int64_t* key_numel, const int64_t* key_offset,
@@ -1563,25 +1405,20 @@ int fedavg_client_sqdist_segments_f32(const int64_t* client_ptrs, const int64_t*
   const int64_t need = fedavg_segments_partials(key_numel, n_keys, K);
   if (partial_elems < need) return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)need);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool small = segments_small(key_numel, n_keys);
+  const SegPassPlan pl = segments_dist_plan(segments_small(key_numel, n_keys, cu_count()));
   const int64_t units = stage_tables(what, client_ptrs, key_numel, key_offset, key_kind, n_keys, K, host_ws, dev_ws,
-                                     ws_bytes, s, small ? kSegSmallSpan : kSegDistSpan);
+                                     ws_bytes, s, pl.span);
   if (units < 0) return static_cast<int>(units);
-  if (units == 0) {
-    const hipError_t e = hipMemsetAsync(sumsq, 0, static_cast<size_t>(K) * sizeof(double), s);
-    return e == hipSuccess ? FEDAVG_OK : set_error(-static_cast<int>(e), "%s: hipMemsetAsync failed", what);
-  }
-  const auto* keys = static_cast<const SegKey*>(dev_ws);
-  const auto* ptrs = reinterpret_cast<const int64_t*>(static_cast<const char*>(dev_ws) +
-                                                      n_keys * static_cast<int64_t>(sizeof(SegKey)));
+  if (units == 0) return zero_sums(kSegLaunch, what, sumsq, K, s);
+  const SegTables t = seg_tables(dev_ws, n_keys);
   const int64_t nparts = units * (kBlock / 64);
   return launch_and_finalize(kSegLaunch, what, K, nparts, 0, partials, partial_elems, sumsq, s, [&] {
-    if (small)
-      hipLaunchKernelGGL((sqdist_segments_f32_kernel<kSegDistU, kSegSmallC>), dim3(static_cast<unsigned>(units)),
-                         dim3(kBlock), 0, s, keys, ptrs, n_keys, int64_t(0), static_cast<int>(K), glob, partials, nparts);
-    else
-      hipLaunchKernelGGL((sqdist_segments_f32_kernel<kSegDistU, kSegDistC>), dim3(static_cast<unsigned>(units)),
-                         dim3(kBlock), 0, s, keys, ptrs, n_keys, int64_t(0), static_cast<int>(K), glob, partials, nparts);
+    const bool found = for_entry<kSegDistForms>(pl.unroll, pl.cols, [&](auto u, auto c) {
+      hipLaunchKernelGGL((sqdist_segments_f32_kernel<decltype(u)::value, decltype(c)::value>),
+                         dim3(static_cast<unsigned>(units)), dim3(kBlock), 0, s, t.keys, t.ptrs, n_keys, int64_t(0),
+                         static_cast<int>(K), glob, partials, nparts);
+    });
+    return found ? FEDAVG_OK : set_error(FEDAVG_EMODE, "%s: plan U%d x C%d names no kernel", what, pl.unroll, pl.cols);
   });
 }
 
@@ -1590,16 +1427,7 @@ int fedavg_client_sqdist_segments_f32(const int64_t* client_ptrs, const int64_t*
 // fedavg_reduce_segments_f32, sumsq as fedavg_client_sqdist_segments_f32 on
 // that out.  partials : fedavg_reduce_sqdist_segments_partials(K) doubles.
 int64_t fedavg_reduce_sqdist_segments_partials(int64_t K) {
-  if (K <= 0 || K > kSegSplitMaxK) return 0;
-  const int64_t full = INT64_MAX / 2;  // units of a launch that fills the chip
-  const int64_t stamps = seg_split_stamps() ? winn_stamp_elems(16) : 0;
-  const int64_t split = seg_parts({true, -1, 64, 0}, K, full);
-  if (K > kSegFusedMaxK) return K * split + stamps;  // the split-row windows (device round)
-  const PlanEntry* band = win_band_of(K);
-  const int64_t tiles = seg_parts({false, 0, seg_fused_cols(K), 0}, K, full);
-  const int64_t windows = band ? seg_parts({true, band->a, 64 * band->b, 0}, K, full) : 0;
-  const int64_t need = std::max(std::max(tiles, windows), K >= seg_split_min_k() ? split : 0);  // 129-256: split windows
-  return K * need + stamps;
+  return seg_fused_partials(K, seg_knobs(), seg_split_stamps() ? winn_stamp_elems(16) : 0, seg_parts);
 }
 
 int fedavg_reduce_sqdist_segments_f32(const int64_t* client_ptrs, const int64_t* key_numel, const int64_t* key_offset,
@@ -1622,17 +1450,16 @@ int fedavg_reduce_sqdist_segments_f32(const int64_t* client_ptrs, const int64_t*
   // long models, 17-128 clients, fp32 keys only: the zero-copy wave-owned windows
   bool all_raw = key_kind != nullptr && key_numel != nullptr;
   for (int64_t jk = 0; all_raw && jk < n_keys; ++jk) all_raw = key_numel[jk] >= 0 && key_kind[jk] == kRaw;
-  const SegFusedPlan plan = seg_fused_plan(key_numel, n_keys, K, all_raw);
+  const RoundPlan plan = seg_fused_plan(key_numel, n_keys, K, all_raw);
   if (plan.win && partial_elems < K * plan.waves)
     return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)(K * plan.waves));
   const int64_t units = stage_tables(what, client_ptrs, key_numel, key_offset, key_kind, n_keys, K, host_ws, dev_ws,
                                      ws_bytes, s, plan.span);
   if (units < 0) return static_cast<int>(units);
-  const auto* keys = static_cast<const SegKey*>(dev_ws);
-  const auto* tptrs = reinterpret_cast<const int64_t*>(static_cast<const char*>(dev_ws) +
-                                                       n_keys * static_cast<int64_t>(sizeof(SegKey)));
-  return launch_seg_fused(plan, SegCall{keys, tptrs, n_keys, units, K, weights, out, partials, partial_elems, sumsq, s,
-                                        what, nullptr, nullptr});
+  const SegTables t = seg_tables(dev_ws, n_keys);
+  const SegCall c{t.keys, t.ptrs, n_keys, units, K, weights, out, partials,
+                  partial_elems, sumsq, s, what, nullptr, nullptr};
+  return launch_seg_fused(plan, c);
 }
 
 int64_t fedavg_device_round_workspace(int64_t K, int64_t n_keys) {
@@ -1716,14 +1543,8 @@ int fedavg_device_round_f32(const int64_t* client_ptrs, int64_t ptr_ld, const in
   // profiles/r04/device_round/), the integer keys' scratch columns, the plan,
   // the key table, the tiles' unit map or the windows' descriptor table, the
   // weights.
-  SegFusedPlan plan{false, 0, 0, 0};
-  const auto plan_fn = [&](bool fuse, bool all_raw) -> fedavg_staging::RoundPlan {
-    if (fuse) {
-      plan = seg_fused_plan(key_numel, n_keys, K, all_raw);
-      return fedavg_staging::RoundPlan{plan.win, plan.kmax, plan.span, false};
-    }
-    const bool small = segments_small(key_numel, n_keys);
-    return fedavg_staging::RoundPlan{false, 0, small ? kSegSmallSpan : kSegSpan, small};
+  const auto plan_fn = [&](bool fuse, bool all_raw) {
+    return fuse ? seg_fused_plan(key_numel, n_keys, K, all_raw) : segments_round_plan(key_numel, n_keys, cu_count());
   };
   const fedavg_staging::RoundIn rin{client_ptrs, ptr_ld, key_index, key_numel, key_offset, key_kind, n_keys, K,
                                     weights, reinterpret_cast<int64_t>(int_scratch), int_scratch ? scratch_elems : 0,
@@ -1733,16 +1554,8 @@ int fedavg_device_round_f32(const int64_t* client_ptrs, int64_t ptr_ld, const in
   int rc = fedavg_staging::stage_device_round(rin, host_ws, ws_bytes, plan_fn, &st, &msg);
   if (rc) return set_error(rc, "%s: %s", what, msg.text);
   FEDAVG_ROUND_MARK(3);  // the pointer-table fill
-  const bool fuse = st.fuse, converted = st.converted, small = st.plan.small;
-  const int64_t units = st.units, S = st.S, n_int = st.n_int, moff = st.moff;
-  const bool with_map = st.with_map, with_desc = st.with_desc;
-  if (!st.first_src) {  // every key empty
-    if (sumsq) {
-      const hipError_t e = hipMemsetAsync(sumsq, 0, static_cast<size_t>(K) * sizeof(double), static_cast<hipStream_t>(stream));
-      if (e != hipSuccess) return set_error(-static_cast<int>(e), "%s: hipMemsetAsync failed", what);
-    }
-    return sumsq ? FEDAVG_OK : 1;
-  }
+  if (!st.first_src)  // every key empty
+    return sumsq ? zero_sums(kSegLaunch, what, sumsq, K, static_cast<hipStream_t>(stream)) : 1;
   // a host address would fault the kernels: spot check of the first and last
   // source (the Python layer checks every tensor's device)
   if (!is_device_memory(st.first_src) || !is_device_memory(st.last_src))
@@ -1757,40 +1570,34 @@ int fedavg_device_round_f32(const int64_t* client_ptrs, int64_t ptr_ld, const in
   }
   FEDAVG_ROUND_MARK(6);  // the tables' H2D issued
   const char* db = static_cast<const char*>(dev_ws);
-  const auto* keys = reinterpret_cast<const SegKey*>(db);
-  const auto* tptrs = reinterpret_cast<const int64_t*>(db + L.ptrs);
+  const SegTables t = seg_tables(dev_ws, n_keys);
   const auto* dw = reinterpret_cast<const float*>(db + L.w);
-  if (converted) {
-    if (n_int * K > INT32_MAX) return set_error(FEDAVG_EINVAL, "%s: too many integer keys", what);
-    hipLaunchKernelGGL(int_keys_to_f32_kernel, dim3(static_cast<unsigned>(n_int * K)), dim3(64), 0, s,
+  if (st.converted) {
+    if (st.n_int * K > INT32_MAX) return set_error(FEDAVG_EINVAL, "%s: too many integer keys", what);
+    hipLaunchKernelGGL(int_keys_to_f32_kernel, dim3(static_cast<unsigned>(st.n_int * K)), dim3(64), 0, s,
                        reinterpret_cast<const IntKey*>(db + L.ik), reinterpret_cast<const int64_t*>(db + L.isrc),
-                       static_cast<int>(K), S, int_scratch);
+                       static_cast<int>(K), st.S, int_scratch);
     rc = launch_status(what);
     if (rc) return rc;
   }
   FEDAVG_ROUND_MARK(7);  // the integer keys' launch
-  if (fuse) {
-    rc = launch_seg_fused(plan, SegCall{keys, tptrs, n_keys, units, K, dw, out, partials, partial_elems, sumsq, s, what,
-                                        with_map ? reinterpret_cast<const int*>(db + moff) : nullptr,
-                                        with_desc ? reinterpret_cast<const u32x4*>(db + moff) : nullptr});
+  if (st.fuse) {
+    const SegCall c{t.keys, t.ptrs, n_keys, st.units, K, dw, out, partials, partial_elems, sumsq, s, what,
+                    st.with_map ? reinterpret_cast<const int*>(db + st.moff) : nullptr,
+                    st.with_desc ? reinterpret_cast<const u32x4*>(db + st.moff) : nullptr};
+    rc = launch_seg_fused(st.plan, c);
     FEDAVG_ROUND_MARK(8);  // the fused launch and the sums' finalize
     return rc ? rc : FEDAVG_OK;
   }
-  if (small)
-    launch_reduce_segments<kSegU, kSegSmallC, kSegStyle>(keys, tptrs, n_keys, units, K, dw, out,
-                                                         static_cast<int64_t>(kSegSmallBlocksPerCU) * cu_count(), s);
-  else
-    launch_reduce_segments<kSegU, kSegC, kSegStyle>(keys, tptrs, n_keys, units, K, dw, out,
-                                                    static_cast<int64_t>(kSegBlocksPerCU) * cu_count(), s);
-  rc = launch_status(what);
+  const SegPassPlan pl = segments_reduce_plan(st.plan.small);
+  rc = launch_segments_reduce<kSegReduceForms, kSegStyle>(what, pl, t, n_keys, st.units, K, dw, out, s);
   FEDAVG_ROUND_MARK(8);  // the reduce's launches
   return rc ? rc : 1;
 }
 
-// tuning hook (fedavg_amd_tuning.h): the zero-copy reduce with an explicit
 #ifdef FEDAVG_TUNING  // probe library only (libfedavg_amd_probe.so)
-// fedavg_client_sqdist_segments_f32 with an explicit (U, C): units of
-// 1,024 x C columns; partials need K x units x 4 doubles for that span
+// fedavg_client_sqdist_segments_f32 with an explicit (U, C) of kSegDistVariants: units of 1,024 x C
+// columns; partials need K x units x 4 doubles for that span
 int fedavg_client_sqdist_segments_f32_variant(const int64_t* client_ptrs, const int64_t* key_numel,
                                               const int64_t* key_offset, const int64_t* key_kind, int64_t n_keys,
                                               int64_t K, const float* glob, double* partials, int64_t partial_elems,
@@ -1799,45 +1606,28 @@ int fedavg_client_sqdist_segments_f32_variant(const int64_t* client_ptrs, const 
   const char* what = "fedavg_client_sqdist_segments_f32_variant";
   if (!glob || !partials || !sumsq || !key_numel || n_keys <= 0 || K <= 0)
     return set_error(FEDAVG_EINVAL, "%s: bad arguments", what);
-  const int uc = unroll * 100 + cols;
-  if (uc != 104 && uc != 404 && uc != 804 && uc != 401 && uc != 801 && uc != 402 && uc != 802 && uc != 408)
+  if (!for_entry<kSegDistVariants>(unroll, cols, [](auto, auto) {}))
     return set_error(FEDAVG_EMODE, "%s: unsupported (unroll, cols) = (%d, %d)", what, unroll, cols);
-  const int64_t span = static_cast<int64_t>(kBlock) * cols * 4;
+  const int64_t span = seg_span_of(cols);
   const int64_t need = K * units_of(key_numel, n_keys, span) * (kBlock / 64);
   if (partial_elems < need) return set_error(FEDAVG_EINVAL, "%s: partials need %lld doubles", what, (long long)need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t units = stage_tables(what, client_ptrs, key_numel, key_offset, key_kind, n_keys, K, host_ws, dev_ws,
                                      ws_bytes, s, span);
   if (units <= 0) return static_cast<int>(units);
-  const auto* keys = static_cast<const SegKey*>(dev_ws);
-  const auto* ptrs = reinterpret_cast<const int64_t*>(static_cast<const char*>(dev_ws) +
-                                                      n_keys * static_cast<int64_t>(sizeof(SegKey)));
+  const SegTables t = seg_tables(dev_ws, n_keys);
   const int64_t nparts = units * (kBlock / 64);
-  const dim3 grid(static_cast<unsigned>(units));
-  const int k = static_cast<int>(K);
   return launch_and_finalize(kSegLaunch, what, K, nparts, 0, partials, partial_elems, sumsq, s, [&] {
-    switch (uc) {
-#define FEDAVG_SQSEG_CASE(U, C)                                                                                      \
-    case U * 100 + C:                                                                                                  \
-      hipLaunchKernelGGL((sqdist_segments_f32_kernel<U, C>), grid, dim3(kBlock), 0, s, keys, ptrs, n_keys, int64_t(0), \
-                         k, glob, partials, nparts);                                                                   \
-      break;
-      FEDAVG_SQSEG_CASE(1, 4)
-      FEDAVG_SQSEG_CASE(4, 4)
-      FEDAVG_SQSEG_CASE(8, 4)
-      FEDAVG_SQSEG_CASE(4, 1)
-      FEDAVG_SQSEG_CASE(8, 1)
-      FEDAVG_SQSEG_CASE(4, 2)
-      FEDAVG_SQSEG_CASE(8, 2)
-      FEDAVG_SQSEG_CASE(4, 8)
-#undef FEDAVG_SQSEG_CASE
-    }
+    for_entry<kSegDistVariants>(unroll, cols, [&](auto u, auto c) {
+      hipLaunchKernelGGL((sqdist_segments_f32_kernel<decltype(u)::value, decltype(c)::value>),
+                         dim3(static_cast<unsigned>(units)), dim3(kBlock), 0, s, t.keys, t.ptrs, n_keys, int64_t(0),
+                         static_cast<int>(K), glob, partials, nparts);
+    });
   });
 }
-#endif  // FEDAVG_TUNING
 
-// (U, C) schedule -- units of 1,024 x C columns -- and launch size; same bits
-#ifdef FEDAVG_TUNING  // probe library only (libfedavg_amd_probe.so)
+// tuning hook (fedavg_amd_tuning.h): the zero-copy reduce with an explicit (U, C) schedule of
+// kSegReduceVariants -- units of 1,024 x C columns -- and launch size; same bits
 int fedavg_reduce_segments_f32_variant(const int64_t* client_ptrs, const int64_t* key_numel, const int64_t* key_offset,
                                        const int64_t* key_kind, int64_t n_keys, int64_t K, const float* weights,
                                        float* out, void* host_ws, void* dev_ws, int64_t ws_bytes, int unroll, int cols,
@@ -1845,30 +1635,16 @@ int fedavg_reduce_segments_f32_variant(const int64_t* client_ptrs, const int64_t
   const char* what = "fedavg_reduce_segments_f32_variant";
   if (!weights || !out) return set_error(FEDAVG_EINVAL, "%s: null weights/out", what);
   if (!is_device_memory(out)) return set_error(FEDAVG_EINVAL, "%s: out must be device memory", what);
-  const int uc = unroll * 100 + cols;
-  if (uc != 408 && uc != 804 && uc != 208 && uc != 404 && uc != 802 && uc != 1602 && uc != 216 && uc != 116)
+  if (!for_entry<kSegReduceVariants>(unroll, cols, [](auto, auto) {}))
     return set_error(FEDAVG_EMODE, "%s: unsupported (unroll, cols) = (%d, %d)", what, unroll, cols);
   if (blocks_per_cu < 0) return set_error(FEDAVG_EINVAL, "%s: blocks_per_cu < 0", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int64_t span = static_cast<int64_t>(kBlock) * cols * 4;
+  const SegPassPlan pl{unroll, cols, blocks_per_cu, seg_span_of(cols)};
   const int64_t units = stage_tables(what, client_ptrs, key_numel, key_offset, key_kind, n_keys, K, host_ws, dev_ws,
-                                     ws_bytes, s, span);
+                                     ws_bytes, s, pl.span);
   if (units <= 0) return static_cast<int>(units);
-  const auto* keys = static_cast<const SegKey*>(dev_ws);
-  const auto* ptrs = reinterpret_cast<const int64_t*>(static_cast<const char*>(dev_ws) +
-                                                      n_keys * static_cast<int64_t>(sizeof(SegKey)));
-  const int64_t cap = static_cast<int64_t>(blocks_per_cu) * cu_count();
-  switch (uc) {
-    case 408: launch_reduce_segments<4, 8>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 804: launch_reduce_segments<8, 4>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 208: launch_reduce_segments<2, 8>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 404: launch_reduce_segments<4, 4>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 802: launch_reduce_segments<8, 2>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 1602: launch_reduce_segments<16, 2>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    case 216: launch_reduce_segments<2, 16>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-    default: launch_reduce_segments<1, 16>(keys, ptrs, n_keys, units, K, weights, out, cap, s); break;
-  }
-  return launch_status(what);
+  const SegTables t = seg_tables(dev_ws, n_keys);
+  return launch_segments_reduce<kSegReduceVariants, 0>(what, pl, t, n_keys, units, K, weights, out, s);
 }
 #endif  // FEDAVG_TUNING
 

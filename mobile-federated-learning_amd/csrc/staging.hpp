@@ -185,14 +185,16 @@ inline int stage_pack_items(const fedavg_pack_item* items, int64_t n_items, int6
 // `plan_fn(fuse, all_raw)` decides the round's form once the sources are known
 // (a misaligned fp32 source clears `fuse`): win / kmax (window instance, -1 =
 // the split-row windows) / span (the unit width the key table is staged with)
-// / small (the narrow units of a non-fused round).  The fuzz harness passes
-// every form; production passes seg_fused_plan (fedavg_segments.hip).
+// / small (the narrow units of a non-fused round) / waves (a window plan's
+// launch, not read here).  The fuzz harness passes every form; production
+// passes seg_fused_plan or segments_round_plan (segments_plan.hpp).
 // ---------------------------------------------------------------------------
 struct RoundPlan {
   bool win;
   int kmax;
   int64_t span;
   bool small;
+  int64_t waves = 0;
 };
 
 struct RoundIn {

@@ -1,9 +1,10 @@
 // window.hpp -- what the window kernels of fedavg_dist.hip ([K, ld] rows) and
 // fedavg_segments.hip (zero-copy, device-resident clients) share: the
 // register-window helpers, the row-sum folds, the hand-off protocol's wait /
-// publish / weights, and the one-wave band table with the plan dispatch
-// helpers (host); and, for every fused launcher (fedavg_fused_vec.hip's too),
-// the grid rule and the launch-and-finalize step (host).
+// publish / weights; and, for every fused launcher (fedavg_fused_vec.hip's
+// too), the launch-and-finalize step (host).  The band tables, their plan
+// dispatch helpers and the grid rules are HIP-free and live in
+// plan_table.hpp, included here.
 // Everything about where a row comes from stays with the kernels.
 #pragma once
 
@@ -152,63 +153,9 @@ __device__ __forceinline__ void handoff_weights(float (&wv)[4], const float* W, 
 }
 
 // ---------------------------------------------------------------------------
-// Plan tables of the window kernels (host; PlanEntry and for_entry:
-// plan_table.hpp).
+// The launch step of every fused aggregate + :291 launcher (host; the plan
+// tables and grid rules: plan_table.hpp).
 // ---------------------------------------------------------------------------
-// One-wave windows, 17..128 rows: {KMAX, VEC} by band (measurements:
-// fedavg_dist.hip's fused_plan notes).  The only place the bands are written.
-constexpr PlanEntry kWinBands[] = {{48, 4}, {64, 2}, {80, 2}, {100, 2}, {128, 1}};
-constexpr int64_t kWinMinK = 17;
-
-// the band of K rows ({kmax, vec}), nullptr outside 17..128
-inline const PlanEntry* win_band_of(int64_t K) {
-  if (K < kWinMinK) return nullptr;
-  for (const PlanEntry& b : kWinBands)
-    if (K <= b.a) return &b;
-  return nullptr;
-}
-// f(KMAX, VEC) for the band whose KMAX is `kmax`; false: no such band
-template <class F>
-bool for_win_band(int kmax, F&& f) {
-  return for_entry<kWinBands>(kmax, kAnyB, f);
-}
-
-// Split-row windows (hand-off form): {NSMAX, PF} -- up to 8 waves per
-// workgroup with 8 prefetched rows, up to 16 with 16 (profiles/r06/winf/)
-constexpr PlanEntry kSplitForms[] = {{8, 8}, {16, 16}};
-// f(NSMAX, PF) for workgroups of (at most) `waves` waves
-template <class F>
-bool for_split(int waves, F&& f) {
-  return for_entry<kSplitForms>(waves <= 8 ? 8 : 16, kAnyB, f);
-}
-
-// Workgroups per CU of a split-row window launch: the resident ones rounded
-// down to a power of two (3 workgroups of 5 waves on a CU ran 12-15 % slower
-// than 2, profiles/r05/prefetch/; zero-copy: profiles/r06/zc_percu/); 0: none
-inline int64_t split_per_cu(int64_t resident) {
-  const int64_t r = resident / cu_count();
-  int64_t per_cu = 0;
-  if (r >= 1)
-    for (per_cu = 1; per_cu * 2 <= r;) per_cu *= 2;
-  return per_cu;
-}
-
-// ---------------------------------------------------------------------------
-// The grid rule and the launch step of every fused aggregate + :291 launcher
-// (host).  The CU count is an argument: fedavg_fused_vec.hip sizes its grids
-// for a constant chip and answers without a device.
-// ---------------------------------------------------------------------------
-// workgroups of a persistent launch: every resident one, or one per work item
-// when there are fewer
-inline int64_t persistent_grid(int64_t per_cu, int64_t cus, int64_t items) {
-  const int64_t g = per_cu * cus;
-  return items < g ? items : g;
-}
-// waves of a window launch of NW-wave workgroups: a workgroup per NW windows
-inline int64_t window_waves(int64_t per_cu, int64_t cus, int64_t windows, int nw) {
-  return persistent_grid(per_cu, cus, (windows + nw - 1) / nw) * nw;
-}
-
 // What a translation unit's launches share: its library's error state, the
 // wording of its "too small" refusal (what, doubles needed) and the kernel
 // that sums partials[K][parts] into sumsq[K]
@@ -240,6 +187,12 @@ int launch_and_finalize(const LaunchCtx& cx, const char* what, int64_t K, int64_
   void* args[] = {&sums_of, &parts, &sumsq};
   (void)hipLaunchKernel(cx.finalize, dim3(static_cast<unsigned>(K)), dim3(kBlock), args, 0, s);
   return cx.status(what);
+}
+
+// nothing to read (no columns, no units): every client's sum is 0
+inline int zero_sums(const LaunchCtx& cx, const char* what, double* sumsq, int64_t K, hipStream_t s) {
+  const hipError_t e = hipMemsetAsync(sumsq, 0, static_cast<size_t>(K) * sizeof(double), s);
+  return e == hipSuccess ? FEDAVG_OK : cx.error(-static_cast<int>(e), "%s: hipMemsetAsync failed", what);
 }
 
 }  // namespace fedavg_impl

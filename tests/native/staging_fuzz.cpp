@@ -10,9 +10,10 @@
 //   for every plan form the round can take -- the LDS-DMA tiles with and
 //   without the unit map, every window instance (KMAX 16/32/48/64/80/100/128)
 //   with its descriptor table, the split-row windows, the non-fused reduce's
-//   wide and narrow units -- with n_keys 1..5,000 and K 1..1,024, integer keys
-//   converted or not, misaligned sources clearing the fused pass: the host
-//   buffer is exactly round_ws(K, n_keys).end bytes (ASan flags any write past
+//   wide and narrow units; every entry of the real tables (kWinBands,
+//   kSplitForms, kSegTiles) must be among them -- with n_keys 1..5,000 and
+//   K 1..1,024, integer keys converted or not, misaligned sources clearing
+//   the fused pass: the host buffer is exactly round_ws(K, n_keys).end bytes (ASan flags any write past
 //   it), every written byte lies below the bytes the H2D ships, and the
 //   descriptor table / unit map / converted pointers hold what the kernels
 //   expect;
@@ -32,6 +33,7 @@
 #include <vector>
 
 #include "fedavg_amd.h"
+#include "segments_plan.hpp"  // the real form tables (with plan_table.hpp)
 #include "staging.hpp"
 
 using namespace fedavg_staging;
@@ -119,16 +121,40 @@ Table random_table(std::mt19937_64& rng, int64_t n_keys, int64_t K) {
   return t;
 }
 
+constexpr int64_t kFuzzMaxK = 1024;  // client counts 1..kFuzzMaxK (main)
+
 // the forms fedavg_device_round_f32's plan can take (seg_fused_plan / segments_small)
 std::vector<RoundPlan> plan_forms(int64_t K) {
   std::vector<RoundPlan> f;
-  for (int64_t span : {64, 128, 256, 512, 1024}) f.push_back(RoundPlan{false, 0, span, false});  // tiles
+  for (int64_t span : {32, 64, 128, 256, 512, 1024}) f.push_back(RoundPlan{false, 0, span, false});  // tiles
   const int kmaxes[] = {16, 32, 48, 64, 80, 100, 128};
   const int vecs[] = {4, 4, 4, 2, 2, 2, 1};
   for (int i = 0; i < 7; ++i)
     if (K <= kmaxes[i]) f.push_back(RoundPlan{true, kmaxes[i], 64 * vecs[i], false});
   f.push_back(RoundPlan{true, -1, 64, false});  // split-row windows
   return f;
+}
+
+// every form the real tables hold (plan_table.hpp's window bands and split
+// forms, segments_plan.hpp's tiles) is among the fuzzed ones: a band added
+// there without coverage here fails
+void check_forms_cover_tables() {
+  using namespace fedavg_impl;
+  const auto fuzzed = [](int64_t K, bool win, int kmax, int64_t span) {
+    for (const RoundPlan& p : plan_forms(K))
+      if (p.win == win && p.kmax == kmax && p.span == span) return true;
+    return false;
+  };
+  for (const PlanEntry& b : kWinBands)
+    CHECK(fuzzed(b.a, true, b.a, 64 * b.b), "window band %d x %d is not fuzzed", b.a, b.b);
+  for (const PlanEntry& t : kSegTiles) CHECK(fuzzed(1, false, 0, t.a), "tile of %d columns is not fuzzed", t.a);
+  // the split-row windows stage ONE RoundPlan whatever {NSMAX, PF} launches it (the staging never sees
+  // the entry), so per entry the check is its reach: the fuzzed client counts go up to its 64 x NSMAX rows
+  for (const PlanEntry& s : kSplitForms) {
+    const RoundPlan p = seg_split_plan();
+    CHECK(64 * s.a <= kFuzzMaxK && fuzzed(64 * s.a, p.win, p.kmax, p.span),
+          "split form %d (up to %d clients) is beyond the fuzzed client counts", s.a, 64 * s.a);
+  }
 }
 
 void fuzz_device_round(std::mt19937_64& rng, int64_t n_keys, int64_t K, bool every_form) {
@@ -298,17 +324,20 @@ int main(int argc, char** argv) {
   const int iters = argc > 1 ? std::atoi(argv[1]) : 200;
   const uint64_t seed = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 1234;
   std::mt19937_64 rng(seed);
+  check_forms_cover_tables();
   // the edges first: 1 key / 1 client, the descriptor table's room switch
   // (2,047 / 2,048 keys at KMAX 128), the unit map's limit, the largest sizes
-  const int64_t edges[][2] = {{1, 1}, {1, 1024}, {2047, 128}, {2048, 128}, {2049, 17}, {5000, 1}, {5000, 100},
+  const int64_t edges[][2] = {{1, 1}, {1, kFuzzMaxK}, {2047, 128}, {2048, 128}, {2049, 17}, {5000, 1}, {5000, 100},
                               {3, 1024}, {350, 100}, {62, 500}, {4095, 64}, {4096, 100}};
   for (const auto& e : edges) {
     fuzz_device_round(rng, e[0], e[1], true);
     fuzz_segment_tables(rng, e[0], e[1]);
   }
   for (int it = 0; it < iters; ++it) {
-    const int64_t n_keys = rng() % 4 == 0 ? 1 + static_cast<int64_t>(rng() % 5000) : 1 + static_cast<int64_t>(rng() % 400);
-    const int64_t K = rng() % 4 == 0 ? 1 + static_cast<int64_t>(rng() % 1024) : 1 + static_cast<int64_t>(rng() % 130);
+    const int64_t n_keys =
+        rng() % 4 == 0 ? 1 + static_cast<int64_t>(rng() % 5000) : 1 + static_cast<int64_t>(rng() % 400);
+    const int64_t K =
+        rng() % 4 == 0 ? 1 + static_cast<int64_t>(rng() % kFuzzMaxK) : 1 + static_cast<int64_t>(rng() % 130);
     if (n_keys * K > 1500000) continue;  // bound the run time (the edges above cover the corners)
     fuzz_device_round(rng, n_keys, K, false);
     fuzz_segment_tables(rng, n_keys, K);

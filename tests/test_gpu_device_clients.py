@@ -351,6 +351,75 @@ def test_segments_reduce_bit_identical_to_rows(K):
         assert_bits(out_rows[k], out_seg[k].cpu(), f"rows vs segments K={K} {k}")
 
 
+@pytest.mark.parametrize("path", ["narrow", "wide"])
+def test_segments_reduce_across_the_round_split_cut(path):
+    """The unfused zero-copy reduce where its round-split cut has more than one
+    launch, bit for bit against the row reduce on the same packed rows, K = 3:
+    narrow units (1,024 columns, 8 blocks per CU: just over 8 x CUs units of a
+    model that stays "small", 2 launches) and wide units (4,096 columns, 2 per
+    CU: just over 4 x CUs units, 3 launches).  5 keys of unequal odd sizes, no
+    key starting at a launch boundary; through fedavg_reduce_segments_f32,
+    fedavg_device_round_f32 without sums (rc 1) and, as one key,
+    fedavg_reduce_ptrs_f32."""
+    K, cus = 3, torch.cuda.get_device_properties(DEV).multi_processor_count
+    span, per_cu = (1024, 8) if path == "narrow" else (4096, 2)
+    P = (per_cu if path == "narrow" else 4) * cus * span + 2 * span + 513  # odd
+    sizes = [int(P * f) | 1 for f in (0.07, 0.31, 0.11, 0.29)]
+    sizes.append(P - sum(sizes))
+    numel = np.array(sizes, dtype=np.int64)
+    assert numel.min() > 0 and np.all(numel % 2 == 1) and len(set(sizes)) == 5
+    # the plan this shape takes, and its cut
+    units_wide = int(np.sum((numel + 4095) // 4096))
+    assert (units_wide < 4 * cus) == (path == "narrow")
+    starts = np.concatenate([[0], np.cumsum((numel + span - 1) // span)])
+    units, cap = int(starts[-1]), per_cu * cus
+    nl = -(-units // cap)
+    per = -(-units // nl)
+    assert nl == (2 if path == "narrow" else 3)
+    assert not set(range(per, units, per)) & set(int(u) for u in starts[1:-1])
+    one_units = -(-P // span)  # the pointer reduce's one key
+    assert -(-one_units // cap) == nl
+
+    ld = (P + 3) // 4 * 4
+    g = torch.Generator(device=DEV).manual_seed(7)
+    rows = torch.randn(K, ld, generator=g, device=DEV) * 0.05
+    w = mfl_amd.weights_tensor(mfl_amd.sample_weights([5, 11, 3]), torch.float32, DEV)
+    lib = mfl_amd._lib.load()
+    ref = torch.full((P,), float("nan"), device=DEV)
+    mfl_amd._lib.check(lib.fedavg_reduce_f32(rows.data_ptr(), K, P, ld, w.data_ptr(), ref.data_ptr(), None), "rows")
+
+    offset = np.concatenate([[0], np.cumsum(numel)[:-1]]).astype(np.int64)
+    kind = np.zeros(5, dtype=np.int64)
+    ptrs = np.array([[rows[k].data_ptr() + 4 * int(o) for o in offset] for k in range(K)], dtype=np.int64)
+    outs = {}
+
+    need = lib.fedavg_segments_workspace(K, 5)
+    ws_h, ws_d = torch.empty(need, dtype=torch.uint8, pin_memory=True), torch.empty(need, dtype=torch.uint8, device=DEV)
+    outs["segments"] = torch.full((P,), float("nan"), device=DEV)
+    mfl_amd._lib.check(lib.fedavg_reduce_segments_f32(ptrs.ctypes.data, numel.ctypes.data, offset.ctypes.data,
+                                                      kind.ctypes.data, 5, K, w.data_ptr(), outs["segments"].data_ptr(),
+                                                      ws_h.data_ptr(), ws_d.data_ptr(), need, None), "segments")
+
+    need_r = lib.fedavg_device_round_workspace(K, 5)
+    wr_h = torch.empty(need_r, dtype=torch.uint8, pin_memory=True)
+    wr_d = torch.empty(need_r, dtype=torch.uint8, device=DEV)
+    w64 = w.cpu().numpy().astype(np.float64)  # rounds back to the same fp32 weights
+    outs["round"] = torch.full((P,), float("nan"), device=DEV)
+    rc = lib.fedavg_device_round_f32(ptrs.ctypes.data, 5, None, numel.ctypes.data, offset.ctypes.data, kind.ctypes.data,
+                                     5, K, w64.ctypes.data, outs["round"].data_ptr(), None, 0, None, None, 0,
+                                     wr_h.data_ptr(), wr_d.data_ptr(), need_r, None)
+    assert rc == 1, lib.fedavg_last_error()
+
+    dptrs = torch.tensor([rows[k].data_ptr() for k in range(K)], dtype=torch.int64, device=DEV)
+    outs["ptrs"] = torch.full((P,), float("nan"), device=DEV)
+    mfl_amd._lib.check(lib.fedavg_reduce_ptrs_f32(dptrs.data_ptr(), K, P, w.data_ptr(), outs["ptrs"].data_ptr(), None),
+                       "ptrs")
+    torch.cuda.synchronize()
+    assert not torch.isnan(ref).any()
+    for name, out in outs.items():
+        assert torch.equal(out.view(torch.int32), ref.view(torch.int32)), f"{name} ({path}) differs from the row reduce"
+
+
 def test_segments_distances_match_rows_path():
     wl = _segment_case(9, [s for s in _SEG_SPECS if s[1] != torch.bool], seed=11)
     seg = mfl_amd.DeviceAggregator(DEV)

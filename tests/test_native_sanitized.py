@@ -13,6 +13,10 @@
 * ``tests/native/reduce_plan_check.cpp`` (always): the row reduce's HIP-free
   plan header (``csrc/reduce_plan.hpp``) against the plans recorded in
   ``tests/reduce_plan_cases.txt``, its form tables and the round-split cut.
+* ``tests/native/segments_plan_check.cpp`` (always): the zero-copy passes'
+  HIP-free plan header (``csrc/segments_plan.hpp``) against the plans recorded
+  in ``tests/segments_plan_cases.txt``, its form tables, the partials' bounds
+  and the unfused passes' round-split cut.
 * ``fedavg_collect_ext`` (the state_dict walk, ``verify_rows``) built with
   ``-fsanitize=address,undefined`` and the CPU suites that drive it run under
   ``LD_PRELOAD=libasan`` -- opt-in (``MFL_ASAN_TESTS=1``; it compiles a torch
@@ -63,6 +67,24 @@ def test_reduce_plan_under_asan_ubsan(tmp_path):
                            text=True, timeout=300, env=env)
         assert r.returncode == 0, r.stdout + r.stderr
         assert " 0 failures" in r.stdout and "ERROR" not in r.stderr, r.stdout + r.stderr
+
+
+@pytest.mark.skipif(_gxx() is None, reason="g++ not found")
+def test_segments_plan_under_asan_ubsan(tmp_path):
+    """csrc/segments_plan.hpp against tests/segments_plan_cases.txt (recorded
+    from the planner it replaced, a stub table for the kernels' residency):
+    the fused and unfused plans, the partials' bounds and the round-split cut
+    equal every recorded line, every plan names a table entry, the partials
+    cover the chosen plan's launch (tests/native/segments_plan_check.cpp)."""
+    exe = tmp_path / "segments_plan_check"
+    cmd = [_gxx(), "-std=c++17", "-O1", "-g", *SAN, f"-I{ROOT / 'include'}", f"-I{CSRC}",
+           str(ROOT / "tests" / "native" / "segments_plan_check.cpp"), "-o", str(exe)]
+    subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe), str(ROOT / "tests" / "segments_plan_cases.txt")], capture_output=True, text=True,
+                       timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert " 0 failures" in r.stdout and "ERROR" not in r.stderr, r.stdout + r.stderr
 
 
 def _gcc_lib(name):
