@@ -189,7 +189,10 @@ int fedavg_reduce_sqdist_f32_variant(const float* clients, int64_t K, int64_t P,
  * per block, one descriptor per client row and one for glob whose record
  * count ends at the last float4 (lanes past it read 0); (unroll, cols) in
  * {(4,8), (8,4), (2,16), (2,8), (8,8)}; round-split launches of <= max_blocks
- * blocks (0 = one launch).  Same workspace as fedavg_client_sqdist_f32. */
+ * blocks (0 = one launch).  Same workspace as fedavg_client_sqdist_f32.
+ * unroll = chains x 10000 + U names the forms with interleaved fp64 chains;
+ * production's four (kDistBufForms and the rule that picks one, dist_plan:
+ * csrc/dist_plan.hpp) are (40002, 16), (40004, 8), (40004, 4), (40008, 2). */
 int fedavg_client_sqdist_buf(const float* clients, int64_t K, int64_t P, int64_t ld, const float* glob,
                              double* workspace, int64_t workspace_elems, double* sumsq, int unroll, int cols,
                              int max_blocks, void* stream);

@@ -62,6 +62,7 @@ CSRC_STAGING = CSRC_DIR / "staging.hpp"  # host-side staged layouts (also g++-bu
 CSRC_PLAN_TABLE = CSRC_DIR / "plan_table.hpp"  # PlanEntry / for_entry of every plan family
 CSRC_REDUCE_PLAN = CSRC_DIR / "reduce_plan.hpp"  # the row reduce's plan, forms and round-split cut (also g++-built)
 CSRC_SEGMENTS_PLAN = CSRC_DIR / "segments_plan.hpp"  # the zero-copy passes' plans, forms and bounds (also g++-built)
+CSRC_DIST_PLAN = CSRC_DIR / "dist_plan.hpp"  # the rows fused and distance passes' plans, forms and bounds (also g++-built)
 CSRC_VEC_RULES = CSRC_DIR / "fused_vec_rules.hpp"  # dtype rules and bands of the fused-vec and seg-vec kernels
 CSRC_COLLECT = CSRC_DIR / "fedavg_collect_ext.cpp"
 COLLECT_NAME = "fedavg_collect_ext"
@@ -102,7 +103,7 @@ def hipcc_path() -> str:
 def sources():
     return [*HIP_SOURCES, *PROBE_SOURCES, *FUSEDVEC_SOURCES, *SEGVEC_SOURCES, *CLIENTVEC_SOURCES, CSRC_HOST,
             CSRC_COMMON, CSRC_WINDOW, CSRC_STAGING, CSRC_PLAN_TABLE, CSRC_REDUCE_PLAN, CSRC_SEGMENTS_PLAN,
-            CSRC_VEC_RULES, INCLUDE / "fedavg_amd.h",
+            CSRC_DIST_PLAN, CSRC_VEC_RULES, INCLUDE / "fedavg_amd.h",
             INCLUDE / "fedavg_amd_tuning.h", INCLUDE / "fedavg_amd_fusedvec.h", INCLUDE / "fedavg_amd_segvec.h",
             INCLUDE / "fedavg_amd_clientvec.h", Path(__file__)]
 

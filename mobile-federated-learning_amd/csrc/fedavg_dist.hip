@@ -1,6 +1,7 @@
 // fedavg_dist.hip -- the post-aggregate client distance pass
 // (fedavg_trainer.py:291) of libfedavg_amd.so.
 #include "common.hpp"
+#include "dist_plan.hpp"
 #include "window.hpp"
 
 namespace {
@@ -506,16 +507,10 @@ __global__ __launch_bounds__(kBlock) void reduce_sqdist_f32_kernel(const float* 
   fused_finish<RM>(lds, acc, K, partials);
 }
 
-// (The LDS-DMA kernel serves 17-128 rows in production, fused_plan below.
+// (The LDS-DMA kernel serves 17-128 rows in production, fused_plan in dist_plan.hpp.
 // Round 2 ran it up to 300 clients with two rows per thread above 256:
 // 200 x 10M 2.74 -> 1.84 ms, 300 x 5M 1.96 -> 1.58, but 500 x 11.2M 10.8 vs
 // 7.26 ms for the two passes; profiles/r02/fused/fused_many_clients*_probe.jsonl.)
-
-// the tile + its average, and at least the 256 doubles of the final per-row sums
-inline int64_t fused_lds_bytes(int64_t K, int S, bool db = false) {
-  const int64_t b = ((db ? 2 : 1) * K + 1) * S * 4;
-  return b > kBlock * 8 ? b : kBlock * 8;
-}
 
 // One call of the fused pass as its launchers take it: the entry point's
 // arguments (partials = the workspace)
@@ -740,10 +735,6 @@ __global__ __launch_bounds__(kBlock, DEPTH == 1 ? 1 : 4) void reduce_sqdist_rs_k
   }
 }
 
-// LDS of a register-staged tile: [K][S] + the average [S]; the final per-row
-// sums need K * V doubles (= K * S * 2 bytes, inside the tile)
-inline int64_t fused_rs_lds_bytes(int64_t K, int S) { return (K + 1) * S * 4; }
-
 template <int S, int SLOTS, int MODE, int FLAGS = 0, int DEPTH = 1>
 int fused_rs_per_cu(int64_t K) {
   return lds_blocks_per_cu(reduce_sqdist_rs_kernel<S, SLOTS, MODE, FLAGS, DEPTH>, kBlock, fused_rs_lds_bytes(K, S));
@@ -758,7 +749,7 @@ int64_t fused_rs_grid(int64_t K, int64_t P, int blocks_per_cu) {
 template <int S, int SLOTS, int MODE = 0, int FLAGS = 0, int DEPTH = 1>
 int launch_fused_rs(const FusedCall& c, int blocks_per_cu) {
   const int64_t K = c.K;
-  if ((K * S + 1023) / 1024 > SLOTS)
+  if (!fused_rs_slots_cover(K, S, SLOTS))
     return set_error(FEDAVG_EMODE, "%s: %d slots per thread cover K <= %d at %d columns", c.what, SLOTS,
                      SLOTS * 1024 / S, S);
   const int per_cu = fused_rs_per_cu<S, SLOTS, MODE, FLAGS, DEPTH>(K);
@@ -1270,100 +1261,8 @@ int launch_fused_winf(const FusedCall& c) {
   });
 }
 
-// Which one-read kernel serves K rows (production), from interleaved
-// measurements of every candidate against the others and the two passes on
-// ~4 GB of rows (scripts/fused_probe.py, profiles/r03/fused_rule/*.jsonl and
-// profiles/r03/win/*.jsonl; ms):
-//   long rows (>= 16 windows per wave), 17 <= K <= 128: the wave-owned
-//   windows (reduce_sqdist_win_kernel), KMAX x VEC by K:
-//     K <= 48   48 x 4 (1 KiB per wave per row; 24 x 41.7M 0.675 vs 0.697
-//               LDS-DMA 128 and 0.687 at 32 x 4; 32 x 31.3M 0.715 vs 0.736;
-//               48 x 20.8M 0.652 vs 0.687 LDS-DMA 256)
-//     K <= 64   64 x 2 (64 x 10M 0.449 vs 0.464; 56 x 20M 0.841 vs 0.867)
-//     K <= 80   80 x 2 (72 x 25M 1.311 vs 1.915 LDS-DMA 64; 80 x 25M 1.397
-//               vs 2.124 -- the LDS-DMA tiles at 65-90 rows run far below
-//               their K = 100 rate)
-//     K <= 100  100 x 2 (100 x 25M 1.531-1.665 vs 1.601-1.797 by box; 90 x
-//               25M 1.578 vs 2.440; 100 x 6.25M 0.431 vs 0.451)
-//     K <= 128  128 x 1 (128 x 8M 0.693 vs 0.879; 112 x 8M 0.610 vs 0.640)
-//   shorter rows (100 x 3.1M: window 0.230 vs 0.218; 65-96 rows from 400K
-//   columns up stay on the windows, see kWinHoleMinP), other K:
-//   K <= 16    register-staged, 256-column tiles (8 x 125M 0.896 vs 0.880
-//              LDS-DMA; FEMNIST 10 x 1.2M 16.6 vs 22.2 us)
-//   K <= 32    LDS-DMA, 128 columns (24 x 41.7M 0.733 vs 0.738 register-staged)
-//   K <= 48    LDS-DMA, 256 columns (48 x 20.8M 0.737 vs 0.758 at 128)
-//   K <= 64    LDS-DMA, 128 columns (64 x 10M 0.472 vs 0.486 register-staged)
-//   K <= 128   LDS-DMA, 64 columns (100 x 25M 1.654 vs 1.753 register-staged)
-//   K <= 192   register-staged, 64 columns, 16 slots (192 x 5.2M 0.778 vs
-//              0.857 at 32 columns; the LDS-DMA kernel 0.829)
-//   K <= 320   register-staged, 32 columns, 10 slots (224 x 4.5M 0.728 vs
-//              1.03 at 64; 300 x 5M 1.08 vs 1.41 LDS-DMA vs 1.98 two passes)
-//   K <= 368   register-staged, 32 columns, 16 slots (round 3: 500 x 11.2M
-//              5.41 vs 6.88 ms for the two passes; 512 x 5M 2.58 vs 3.22)
-//   K <= 1024  split-row windows (round 5, below: kFusedWinnMinK)
-// Beyond 1024 rows the two passes (a workgroup holds at most 16 x 64 rows).
-constexpr int kFusedNone = 0, kFusedLds = 1, kFusedRs = 2, kFusedWin = 3, kFusedWinn = 4;
-constexpr int64_t kFusedRowsMaxK = 1024;
-// split-row windows (64 rows per wave, 64 columns) from 369 rows (round 5's
-// barrier form, since retired; scripts/fused_probe.py, profiles/r05/winn/, ms:
-// 384 x 5M 1.455 vs 1.494 register-staged; 448 x 5M 1.60 vs 2.30; 500 x
-// 11.2M 3.71 vs 5.37; 500 x 1.4M 0.54 vs 0.72; 512 x 5M 1.69 vs 2.59; but
-// 352 x 5M 1.42 vs 1.36 and 300 x 5M 1.10 vs 1.05), up to 8 waves per
-// workgroup to 512 rows, 16 beyond (640 x 3M 1.77 vs 2.46 for the two
-// passes; 1000 x 12.5M 9.99 vs 15.05; 520 x 5M 2.71 vs 3.34)
-constexpr int64_t kFusedWinnMinK = 369;
-// Round 6: the split windows run reduce_sqdist_winf_kernel (point-to-point
-// hand-offs, broadcast weights) with 8 prefetched rows at <= 8 waves and 16
-// beyond (profiles/r06/winf/, ms, barrier form vs winf: 1000 x 12.5M 9.06 vs
-// 8.02; 999 x 10M+3 7.75 vs 6.44; 600 x 10M 5.13 vs 4.28; 513 x 3M 1.48 vs
-// 1.26; 500 x 11.2M 3.66 vs 3.57; 400 x 10M 2.73 vs 2.60; 370 x 5M 1.25 vs
-// 1.18; every output bit-identical).
-// (kSplitForms, window.hpp: for_split gives <8, PF 8> or <16, PF 16>)
-// With the prefetch the split windows also beat the register-staged tiles at
-// 161-256 and 289-368 rows on long rows (profiles/r05/prefetch/, ms, tiles vs
-// split: 170 x 5M 0.606 vs 0.593; 192 x 5M 0.725 vs 0.661; 240 x 5M 0.897 vs
-// 0.822; 256 x 12M 2.53 vs 2.19; 290 x 5M 1.026 vs 0.998; 310 x 5M 1.092 vs
-// 1.033; 352 x 5M 1.347 vs 1.178; 368 x 5M 1.427 vs 1.228), not at 140 x 5M
-// (0.493 vs 0.529) or 270 x 5M (0.933 vs 0.981), and tie at 200 x 1.2M (18
-// windows per workgroup): below 369 rows they took rounds of >= 24 windows
-// per workgroup
-// Round 6, the hand-off kernel (profiles/r06/winf_bands/, ms, plan then vs
-// winf): 160 x 5M 0.615 vs 0.547; 260 x 5M 0.913 vs 0.851; 270 x 5M 0.939 vs
-// 0.876; 288 x 5M 0.983 vs 0.923 (the old 257-288 gap); 200 x 1.2M (18
-// windows per workgroup) 0.190 vs 0.182; 200 x 800K (12) 0.144 vs 0.126;
-// 300-368 x 5M equal; below 160 the tiles keep it (150 x 5M 0.526 vs 0.536,
-// 130 x 5M 0.459 vs 0.495)
-constexpr int64_t kFusedWinnLowMinK = 160;
-constexpr int64_t kFusedWinnLowMinPerBlock = 8;
-constexpr int64_t kWinMinPerWave = 16;  // windows per wave below which the tile kernels keep the round
-// ... except in the LDS-DMA tiles' weak band, 65-96 rows, where the windows
-// win down to ~400K columns (profiles/r03/win/short_rows_*.jsonl, ms, tiles
-// vs windows: 70 x 600K 0.052 vs 0.043; 70 x 3M 0.217 vs 0.143; 80 x 1.5M
-// 0.129 vs 0.090; 90 x 600K 0.065 vs 0.051; 90 x 3M 0.285 vs 0.190; 92 x
-// 1.5M 0.108 vs 0.102; 98 x 1.5M 0.109 vs 0.109; 100 x 600K 0.059 vs 0.059;
-// 65 x 200K 0.022 vs 0.023)
-constexpr int64_t kWinHoleMinK = 65, kWinHoleMaxK = 96, kWinHoleMinP = 400000;
-struct FusedPlan {
-  int kind, S, slots;  // kFusedWin: S = KMAX, slots = VEC
-};
-
-// The 81-100 band stages rows 0..23 of the next window in LDS (MODE 64):
-// 100 x 25M 1.652 -> 1.646 ms, 100 x 25M+3 1.700 -> 1.690, 90 x 25M 1.607 ->
-// 1.547 (profiles/r03/win/ldsrows.jsonl); every band has K > 24 rows
-constexpr int kWin100Mode = 64;
-
-constexpr int win_rows_mode(int kmax) { return kmax == 100 ? kWin100Mode : 0; }
-
-// the window kernel instance for K rows ({kFusedNone} outside 17..128: kWinBands, window.hpp)
-inline FusedPlan win_plan(int64_t K) {
-  const PlanEntry* band = win_band_of(K);
-  return band ? FusedPlan{kFusedWin, band->a, band->b} : FusedPlan{kFusedNone, 0, 0};
-}
-
-// The tile plans' instances: LDS-DMA tiles by columns, register-staged tiles
-// by {columns, slots}.  fused_plan returns entries of these tables.
-constexpr PlanEntry kLdsTiles[] = {{64, 0}, {128, 0}, {256, 0}};
-constexpr PlanEntry kRsTiles[] = {{256, 8}, {64, 16}, {32, 10}, {32, 16}};
+// (Which one-read kernel serves K rows -- fused_plan, its thresholds, tile tables and LDS sizes, each
+// with its measurements: dist_plan.hpp.)
 
 // The production instance a plan names, as a tag: parts(K, P) = workgroups
 // (one-wave windows: waves) of its launch, the partials' second dimension;
@@ -1409,259 +1308,202 @@ bool with_fused_instance(const FusedPlan& pl, F&& f) {
   return false;
 }
 
-// the partials' second dimension of the production launch of plan `pl` (0: no instance)
+// the partials' second dimension of the production launch of plan `pl` on
+// this device (0: no instance): the `parts` of fused_plan / fused_workspace
 inline int64_t fused_plan_parts(const FusedPlan& pl, int64_t K, int64_t P) {
   int64_t n = 0;
   with_fused_instance(pl, [&](auto inst) { n = decltype(inst)::parts(K, P); });
   return n;
 }
 
-inline FusedPlan fused_plan(int64_t K, int64_t P) {
-  if (K < 1 || K > kFusedRowsMaxK) return {kFusedNone, 0, 0};
-  const FusedPlan win = win_plan(K);
-  if (win.kind == kFusedWin && ((P + 64 * win.slots - 1) / (64 * win.slots) >= kWinMinPerWave * fused_plan_parts(win, K, P) ||
-                                 (K >= kWinHoleMinK && K <= kWinHoleMaxK && P >= kWinHoleMinP)))
-    return win;
-  if (K <= 16) return {kFusedRs, 256, 8};
-  if (K <= 32) return {kFusedLds, 128, 0};
-  if (K <= 48) return {kFusedLds, 256, 0};
-  if (K <= 64) return {kFusedLds, 128, 0};
-  if (K <= 128) return {kFusedLds, 64, 0};
-  if (K >= kFusedWinnLowMinK && K < kFusedWinnMinK) {
-    const int64_t grid = fused_plan_parts({kFusedWinn, 64, 8}, K, P);
-    if (grid > 0 && (P + 63) / 64 >= kFusedWinnLowMinPerBlock * grid) return {kFusedWinn, 64, 8};
-  }
-  if (K <= 192) return {kFusedRs, 64, 16};
-  if (K <= 320) return {kFusedRs, 32, 10};
-  if (K < kFusedWinnMinK) return {kFusedRs, 32, 16};
-  return {kFusedWinn, 64, K <= 512 ? 8 : 16};  // S = rows per wave, slots = waves per workgroup (max)
+inline FusedPlan fused_plan(int64_t K, int64_t P) { return fedavg_impl::fused_plan(K, P, fused_plan_parts); }
+
+// ---------------------------------------------------------------------------
+// The distance pass's host side (its plans, forms and workspace sizes:
+// dist_plan.hpp).
+// ---------------------------------------------------------------------------
+// The production form of the fp32 pass on this device: fedavg_client_sqdist_f32
+// and fedavg_client_sqdist_workspace both come through here.
+template <int U, int C>
+int64_t dist_buf_slots() {
+  return resident_blocks(client_sqdist_buf_kernel<U, C, 1, dist_chains(C), 0>);
+}
+PlanEntry dist_plan_here(int64_t P) {
+  return dist_plan(P, cu_count(), dist_buf_slots<kDistBufRows, kDistBufCols>(), dist_buf_slots<kDistRows, kDistCols>());
 }
 
-// Global-pointer schedule (the fp64/fp16/bf16 passes and the probe
-// variants): 32 x 16-B loads in flight per thread (U4 x C8) in one launch;
-// scripts/dist_variants.py (profiles/sweeps/r01_dist_*.jsonl) measured
-// round-split launches within 1 % of it and U4 x C4 6 % behind.
-constexpr int kDistCols = 8;
-constexpr int kDistRows = 4;
-// fp32 production (fedavg_client_sqdist_f32): the buffer-descriptor kernel at
-// U2 x C16 in one launch -- full column groups read each row through one
-// SGPR descriptor with no masking, 64 KiB contiguous per row per block, the
-// reduce's winning shape: 6,818-6,840 GB/s vs 6,520-6,531 for the
-// global-pointer U4 x C8 (scripts/dist_variants.py, profiles/r02/dist_variants.jsonl).
-// U4 x C8 remains the fp64/fp16/bf16 passes' schedule.  Each row's fp64 sum
-// runs as 4 interleaved chains (slice j into chain j % 4, added pairwise):
-// 0.9-1.5 % faster than one chain of 64 dependent square-adds in three
-// interleaved runs, 8 chains no better, 16 slower; a one-row-ahead pipeline
-// (U = 0) loses 5 % -- two rows in flight per wave beat compute overlap
-// (profiles/r02/sweeps/dist_chains.jsonl).
-constexpr int kDistBufRows = 2;
-constexpr int kDistBufCols = 16;
-constexpr int kDistBufChains = 4;
-
-// fp32 production column groups per thread: 16 while that still gives two
-// workgroups per CU (the 25M-column target: 1,526), else 4 while it gives
-// ~one per CU, else 2.  A small model's rows are short, and at 16 slices the
-// launch had 37 workgroups for resnet56 (100 x 600K) and 74 for FEMNIST
-// (10 x 1.2M).  rocprofv3 kernel time (profiles/r02/sweeps/dist_small_models.json):
-// resnet56 275 -> 72 us (U8 x C2), FEMNIST 30.8 -> 12.7 us (U4 x C4),
-// cfg4 500 x 1M 1,383 -> 391 us (U4 x C4), 100 x 3.125M 309 -> 197 us (U4 x C4).
-//
-// Between them, U4 x C8 when the 16-slice launch would end in a partly
-// filled round of workgroups: a launch of g groups on r resident slots runs
-// ceil(g / r) rounds, so 685 groups (cfg4, 500 x 11.2M) on 512 slots of the
-// 16-slice kernel (2 per CU) fill 67 %, against 89 % for the 1,371 8-slice
-// groups on its 768 slots (3 per CU).  scripts/dist_variants.py
-// (profiles/r02/sweeps/dist_many_clients*.jsonl): 500 x 11.2M 4.10 -> 3.69 ms,
-// 1000 x 12.5M 8.49 -> 8.03, 200 x 10M 1.52 -> 1.26; 100 x 25M keeps 16
-// slices (1,526 groups, 99 %; 1.467 vs 1.600 ms at 8).
-double round_fill(int64_t groups, int64_t slots) {
-  if (slots <= 0) return 0.0;
-  const int64_t rounds = (groups + slots - 1) / slots;
-  return static_cast<double>(groups) / static_cast<double>(rounds * slots);
-}
-
-int dist_cols(int64_t P) {
-  const int64_t nvec = (P + 3) / 4;
-  const int64_t cus = cu_count();
-  const int64_t g16 = (nvec + kBlock * 16 - 1) / (kBlock * 16);
-  const int64_t g8 = (nvec + kBlock * 8 - 1) / (kBlock * 8);
-  const int64_t slots16 = resident_blocks(client_sqdist_buf_kernel<2, 16, 1, 4>);
-  const int64_t slots8 = resident_blocks(client_sqdist_buf_kernel<4, 8, 1, 4>);
-  if (g16 >= 2 * cus) return round_fill(g8, slots8) > round_fill(g16, slots16) + 0.05 ? 8 : 16;
-  if (g8 >= slots8) return 8;
-  if ((nvec + kBlock * 4 - 1) / (kBlock * 4) >= cus * 9 / 10) return 4;
-  return 2;
-}
-
-int64_t sqdist_waves_for(int64_t P, int cols) {
-  const int64_t nvec = (P + 3) / 4;
-  const int64_t blocks = (nvec + kBlock * cols - 1) / (kBlock * cols);
-  return blocks * (kBlock / 64);
-}
-
-template <int U, int C, bool BUF = false, int MINW = 1, int ACC = 1, int STYLE = 0>
-void launch_sqdist(const float* clients, int K, int64_t ld, int64_t P, const float* glob, double* partials,
-                   int64_t nwaves, int max_blocks, hipStream_t s) {
-  const int64_t nvec = (P + 3) / 4;
-  const int64_t span = static_cast<int64_t>(kBlock) * C;
-  const int64_t blocks = (nvec + span - 1) / span;
-  const int64_t bpl = max_blocks > 0 ? max_blocks : blocks;
-  const int64_t nl = (blocks + bpl - 1) / bpl;
-  const int64_t per_blocks = (blocks + nl - 1) / nl;  // equal launches, whole blocks each
-  const f32x4* X = reinterpret_cast<const f32x4*>(clients);
-  const f32x4* Gv = reinterpret_cast<const f32x4*>(glob);
-  for (int64_t b0 = 0; b0 < blocks; b0 += per_blocks) {
-    const int64_t nb = (blocks - b0) < per_blocks ? (blocks - b0) : per_blocks;
-    const int64_t v0 = b0 * span;
-    const int64_t n = (nvec - v0) < nb * span ? (nvec - v0) : nb * span;
-    const int tail = (v0 + n == nvec) ? static_cast<int>(P & 3) : 0;
-    if constexpr (BUF)
-      hipLaunchKernelGGL((client_sqdist_buf_kernel<U, C, MINW, ACC, STYLE>), dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, s,
-                         X + v0, K, ld / 4, n, tail, Gv + v0, partials, nwaves, b0 * (kBlock / 64));
-    else
-      hipLaunchKernelGGL((client_sqdist_f32x4_kernel<U, C>), dim3(static_cast<unsigned>(nb)), dim3(kBlock), 0, s,
-                         X + v0, K, ld / 4, n, tail, Gv + v0, partials, nwaves, b0 * (kBlock / 64));
-  }
-}
-
-#ifdef FEDAVG_TUNING  // the global-pointer variants (probe library)
-int sqdist_impl(const float* clients, int64_t K, int64_t P, int64_t ld, const float* glob, double* workspace,
-                int64_t workspace_elems, double* sumsq, int unroll, int cols, int max_blocks, void* stream) {
-  const char* what = "fedavg_client_sqdist_f32";
+// The argument / alignment refusals of every distance entry point, `lanes`
+// elements per 16-B slice.
+int check_dist(const void* clients, int64_t K, int64_t P, int64_t ld, const void* glob, const double* sumsq, int lanes,
+               const char* what) {
   int rc = check_common(clients, K, P, ld, glob, sumsq, what);
   if (rc) return rc;
   if (P == 0) return set_error(FEDAVG_EINVAL, "%s: P must be >= 1", what);
-  if (!aligned16(clients) || !aligned16(glob) || (ld % 4) != 0)
-    return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned clients/glob and ld %% 4 == 0", what);
-  if (cols != 4 && cols != 8) return set_error(FEDAVG_EMODE, "%s: cols must be 4 or 8", what);
-  const int64_t nwaves = sqdist_waves_for(P, cols);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int k = static_cast<int>(K);
-  return launch_and_finalize(kRowsLaunch, what, K, nwaves, 0, workspace, workspace ? workspace_elems : 0, sumsq, s, [&] {
-    switch (unroll * 100 + cols) {
-      case 404: launch_sqdist<4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 804: launch_sqdist<8, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 408: launch_sqdist<4, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 208: launch_sqdist<2, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      default: return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", what, unroll, cols);
-    }
+  if (!aligned16(clients) || !aligned16(glob) || (ld % lanes) != 0)
+    return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned clients/glob and ld %% %d == 0", what, lanes);
+  return FEDAVG_OK;
+}
+
+// One call of the fp32 pass as its launches take it (max_blocks: workgroups
+// per launch, 0 = one launch)
+struct DistCall {
+  const float* clients;
+  int64_t K, P, ld;
+  const float* glob;
+  double* partials;
+  int64_t partial_elems;
+  double* sumsq;
+  int max_blocks;
+  hipStream_t s;
+  const char* what;
+  int64_t nwaves(int cols) const { return dist_waves((P + 3) / 4, cols); }
+};
+
+// Equal launches of whole workgroups (round_split); the waves of the launch
+// at slice v0 write their partials from wave v0 / span x 4 on.
+template <int U, int C, bool BUF = false, int MINW = 1, int ACC = 1, int STYLE = 0>
+void launch_sqdist(const DistCall& c) {
+  const int64_t nvec = (c.P + 3) / 4;
+  constexpr int64_t span = static_cast<int64_t>(kBlock) * C;
+  const int64_t blocks = (nvec + span - 1) / span;
+  const f32x4* X = reinterpret_cast<const f32x4*>(c.clients);
+  const f32x4* Gv = reinterpret_cast<const f32x4*>(c.glob);
+  const int K = static_cast<int>(c.K);
+  const int64_t nwaves = c.nwaves(C);
+  for_each_launch(round_split(nvec, span, c.max_blocks > 0 ? c.max_blocks : blocks), nvec, static_cast<int>(c.P & 3),
+                  [&](int64_t v0, int64_t n, int tail, bool, bool) {
+                    const dim3 grid(grid_for(n, static_cast<int>(span)));
+                    const int64_t wave0 = v0 / span * (kBlock / 64);
+                    if constexpr (BUF)
+                      hipLaunchKernelGGL((client_sqdist_buf_kernel<U, C, MINW, ACC, STYLE>), grid, dim3(kBlock), 0, c.s,
+                                         X + v0, K, c.ld / 4, n, tail, Gv + v0, c.partials, nwaves, wave0);
+                    else
+                      hipLaunchKernelGGL((client_sqdist_f32x4_kernel<U, C>), grid, dim3(kBlock), 0, c.s, X + v0, K,
+                                         c.ld / 4, n, tail, Gv + v0, c.partials, nwaves, wave0);
+                  });
+}
+
+// the workspace check, `launch` (an int status) and the finalize of a call at `cols` slices per thread
+template <class Launch>
+int dist_launch(const DistCall& c, int cols, Launch&& launch) {
+  return launch_and_finalize(kRowsLaunch, c.what, c.K, c.nwaves(cols), 0, c.partials, c.partials ? c.partial_elems : 0,
+                             c.sumsq, c.s, launch);
+}
+
+// fedavg_client_sqdist_f32: the plan's entry of kDistBufForms
+int sqdist_production(const DistCall& c) {
+  const PlanEntry plan = dist_plan_here(c.P);
+  return dist_launch(c, plan.b, [&] {
+    if (!for_entry<kDistBufForms>(plan.a, plan.b, [&](auto u, auto cols) {
+          constexpr int U = decltype(u)::value, C = decltype(cols)::value;
+          launch_sqdist<U, C, true, 1, dist_chains(C)>(c);
+        }))
+      return set_error(FEDAVG_EMODE, "%s: plan U%d x C%d names no kernel instance", c.what, plan.a, plan.b);
     return static_cast<int>(FEDAVG_OK);
   });
 }
-#endif  // FEDAVG_TUNING
-
-// fp64/fp16/bf16 passes: U4 x C8 while that gives ~one workgroup per CU,
-// else U8 x C2 (the fp32 pass's short-row measurements, dist_cols)
-constexpr int kDistSmallRows = 8;
-constexpr int kDistSmallCols = 2;
-int dist_vec_cols(int64_t nvec) {
-  return (nvec + kBlock * kDistCols - 1) / (kBlock * kDistCols) >= cu_count() * 9 / 10 ? kDistCols : kDistSmallCols;
-}
-
-int64_t sqdist_vec_waves(int64_t nvec, int cols) {
-  const int64_t blocks = (nvec + kBlock * cols - 1) / (kBlock * cols);
-  return blocks * (kBlock / 64);
-}
-
-// One launch of client_sqdist_vec_kernel<D, 4, kDistCols> + the finalize.
+// One launch of the plan's entry of kDistVecForms + the finalize.
 // Rows: [K, ld] with 16-B aligned rows (ld a multiple of the 16-B lane count).
 template <class D>
 int sqdist_vec_impl(const void* clients, int64_t K, int64_t P, int64_t ld, const void* glob, double* workspace,
                     int64_t workspace_elems, double* sumsq, void* stream, const char* what) {
-  int rc = check_common(clients, K, P, ld, glob, sumsq, what);
-  if (rc) return rc;
-  if (P == 0) return set_error(FEDAVG_EINVAL, "%s: P must be >= 1", what);
-  constexpr int64_t lanes = D::kLanes;
-  if (!aligned16(clients) || !aligned16(glob) || (ld % lanes) != 0)
-    return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned clients/glob and ld %% %d == 0", what, (int)lanes);
+  constexpr int lanes = D::kLanes;
+  if (const int rc = check_dist(clients, K, P, ld, glob, sumsq, lanes, what)) return rc;
   const int64_t nvec = (P + lanes - 1) / lanes;
-  const int cols = dist_vec_cols(nvec);
-  const int64_t nwaves = sqdist_vec_waves(nvec, cols);
+  const PlanEntry plan = dist_vec_plan(nvec, cu_count());
+  const int64_t nwaves = dist_waves(nvec, plan.b);
   hipStream_t s = static_cast<hipStream_t>(stream);
   using vec = typename D::vec;
-  const int64_t blocks = (nvec + kBlock * cols - 1) / (kBlock * cols);
   return launch_and_finalize(kRowsLaunch, what, K, nwaves, 0, workspace, workspace ? workspace_elems : 0, sumsq, s, [&] {
-    if (cols == kDistCols)
-      hipLaunchKernelGGL((client_sqdist_vec_kernel<D, kDistRows, kDistCols>), dim3(static_cast<unsigned>(blocks)),
-                         dim3(kBlock), 0, s, reinterpret_cast<const vec*>(clients), static_cast<int>(K), ld / lanes,
-                         nvec, static_cast<int>(P % lanes), reinterpret_cast<const vec*>(glob), workspace, nwaves);
-    else
-      hipLaunchKernelGGL((client_sqdist_vec_kernel<D, kDistSmallRows, kDistSmallCols>),
-                         dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, reinterpret_cast<const vec*>(clients),
-                         static_cast<int>(K), ld / lanes, nvec, static_cast<int>(P % lanes),
-                         reinterpret_cast<const vec*>(glob), workspace, nwaves);
-  });
-}
-
-int sqdist_buf_impl(const float* clients, int64_t K, int64_t P, int64_t ld, const float* glob, double* workspace,
-                    int64_t workspace_elems, double* sumsq, int unroll, int cols, int max_blocks, void* stream,
-                    const char* what) {
-  int rc = check_common(clients, K, P, ld, glob, sumsq, what);
-  if (rc) return rc;
-  if (P == 0) return set_error(FEDAVG_EINVAL, "%s: P must be >= 1", what);
-  if (!aligned16(clients) || !aligned16(glob) || (ld % 4) != 0)
-    return set_error(FEDAVG_EALIGN, "%s: needs 16-B aligned clients/glob and ld %% 4 == 0", what);
-  if (cols != 1 && cols != 2 && cols != 4 && cols != 8 && cols != 12 && cols != 16)
-    return set_error(FEDAVG_EMODE, "%s: cols must be 1, 2, 4, 8, 12 or 16", what);
-  const int64_t nwaves = sqdist_waves_for(P, cols);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int k = static_cast<int>(K);
-  return launch_and_finalize(kRowsLaunch, what, K, nwaves, 0, workspace, workspace ? workspace_elems : 0, sumsq, s, [&] {
-    switch (unroll * 100 + cols) {
-      // production (fedavg_client_sqdist_f32, dist_cols): 4 chains at U2 x C16, U4 x C8, U4 x C4; 2 at U8 x C2
-      case 4000216: launch_sqdist<2, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4000408: launch_sqdist<4, 8, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4000404: launch_sqdist<4, 4, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4000802: launch_sqdist<8, 2, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-#ifdef FEDAVG_TUNING  // every other shape: fedavg_client_sqdist_buf, probe library only
-      case 408: launch_sqdist<4, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 804: launch_sqdist<8, 4, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 216: launch_sqdist<2, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      // register-capped forms (launch_bounds min waves per SIMD 3 / 4): more
-      // waves resident, fewer loads in flight per wave
-      case 30216: launch_sqdist<2, 16, true, 3>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 40216: launch_sqdist<2, 16, true, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 30408: launch_sqdist<4, 8, true, 3>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 116: launch_sqdist<1, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 112: launch_sqdist<1, 12, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 212: launch_sqdist<2, 12, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 208: launch_sqdist<2, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 808: launch_sqdist<8, 8, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      // 2 / 4 interleaved fp64 chains per row (codes + 1,000,000 x ACC)
-      case 2000216: launch_sqdist<2, 16, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 2000408: launch_sqdist<4, 8, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 8000216: launch_sqdist<2, 16, true, 1, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 16000216: launch_sqdist<2, 16, true, 1, 16>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      // U = 0: row k + 1 loads while row k is summed (one row of registers each)
-      case 16: launch_sqdist<0, 16, true>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4000016: launch_sqdist<0, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4000012: launch_sqdist<0, 12, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4000008: launch_sqdist<0, 8, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      // 4 chains under a register cap (min waves per SIMD 3 / 4)
-      case 4030212: launch_sqdist<2, 12, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4030216: launch_sqdist<2, 16, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4040208: launch_sqdist<2, 8, true, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4030308: launch_sqdist<3, 8, true, 3, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      // narrow column groups for small models (more workgroups per launch)
-      case 4000804: launch_sqdist<8, 4, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4000402: launch_sqdist<4, 2, true, 1, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4000801: launch_sqdist<8, 1, true, 1, 1>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4001601: launch_sqdist<16, 1, true, 1, 1>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 4000116: launch_sqdist<1, 16, true, 1, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      // interleaved loads and squares, L loads in flight: + 100000000 x L
-      case 204000216: launch_sqdist<2, 16, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 404000216: launch_sqdist<2, 16, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 804000216: launch_sqdist<2, 16, true, 1, 4, 8>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 204000404: launch_sqdist<4, 4, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 404000404: launch_sqdist<4, 4, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 204000408: launch_sqdist<4, 8, true, 1, 4, 2>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-      case 404000408: launch_sqdist<4, 8, true, 1, 4, 4>(clients, k, ld, P, glob, workspace, nwaves, max_blocks, s); break;
-#endif  // FEDAVG_TUNING
-      default: return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", what, unroll, cols);
-    }
+    if (!for_entry<kDistVecForms>(plan.a, plan.b, [&](auto u, auto cols) {
+          constexpr int U = decltype(u)::value, C = decltype(cols)::value;
+          hipLaunchKernelGGL((client_sqdist_vec_kernel<D, U, C>), dim3(grid_for(nvec, kBlock * C)), dim3(kBlock), 0, s,
+                             reinterpret_cast<const vec*>(clients), static_cast<int>(K), ld / lanes, nvec,
+                             static_cast<int>(P % lanes), reinterpret_cast<const vec*>(glob), workspace, nwaves);
+        }))
+      return set_error(FEDAVG_EMODE, "%s: plan U%d x C%d names no kernel instance", what, plan.a, plan.b);
     return static_cast<int>(FEDAVG_OK);
   });
 }
+
+#ifdef FEDAVG_TUNING  // probe library only: the variant codes of include/fedavg_amd_tuning.h
+// fedavg_client_sqdist_variant: the global-pointer kernel by unroll x 100 + cols; false: no such code
+bool launch_sqdist_variant(int code, const DistCall& c) {
+  switch (code) {
+    case 404: launch_sqdist<4, 4>(c); return true;
+    case 804: launch_sqdist<8, 4>(c); return true;
+    case 408: launch_sqdist<4, 8>(c); return true;
+    case 208: launch_sqdist<2, 8>(c); return true;
+  }
+  return false;
+}
+
+// fedavg_client_sqdist_buf: the buffer-descriptor kernel by unroll x 100 + cols; false: no such code
+bool launch_sqdist_buf_variant(int code, const DistCall& c) {
+  switch (code) {
+    // production's forms (kDistBufForms): unroll = chains x 10000 + rows per batch
+    case 4000216: launch_sqdist<2, 16, true, 1, 4>(c); return true;
+    case 4000408: launch_sqdist<4, 8, true, 1, 4>(c); return true;
+    case 4000404: launch_sqdist<4, 4, true, 1, 4>(c); return true;
+    case 4000802: launch_sqdist<8, 2, true, 1, 2>(c); return true;
+    case 408: launch_sqdist<4, 8, true>(c); return true;
+    case 804: launch_sqdist<8, 4, true>(c); return true;
+    case 216: launch_sqdist<2, 16, true>(c); return true;
+    // register-capped forms (launch_bounds min waves per SIMD 3 / 4): more
+    // waves resident, fewer loads in flight per wave
+    case 30216: launch_sqdist<2, 16, true, 3>(c); return true;
+    case 40216: launch_sqdist<2, 16, true, 4>(c); return true;
+    case 30408: launch_sqdist<4, 8, true, 3>(c); return true;
+    case 116: launch_sqdist<1, 16, true>(c); return true;
+    case 112: launch_sqdist<1, 12, true>(c); return true;
+    case 212: launch_sqdist<2, 12, true>(c); return true;
+    case 208: launch_sqdist<2, 8, true>(c); return true;
+    case 808: launch_sqdist<8, 8, true>(c); return true;
+    // 2 / 4 interleaved fp64 chains per row (codes + 1,000,000 x ACC)
+    case 2000216: launch_sqdist<2, 16, true, 1, 2>(c); return true;
+    case 2000408: launch_sqdist<4, 8, true, 1, 2>(c); return true;
+    case 8000216: launch_sqdist<2, 16, true, 1, 8>(c); return true;
+    case 16000216: launch_sqdist<2, 16, true, 1, 16>(c); return true;
+    // U = 0: row k + 1 loads while row k is summed (one row of registers each)
+    case 16: launch_sqdist<0, 16, true>(c); return true;
+    case 4000016: launch_sqdist<0, 16, true, 1, 4>(c); return true;
+    case 4000012: launch_sqdist<0, 12, true, 1, 4>(c); return true;
+    case 4000008: launch_sqdist<0, 8, true, 1, 4>(c); return true;
+    // 4 chains under a register cap (min waves per SIMD 3 / 4)
+    case 4030212: launch_sqdist<2, 12, true, 3, 4>(c); return true;
+    case 4030216: launch_sqdist<2, 16, true, 3, 4>(c); return true;
+    case 4040208: launch_sqdist<2, 8, true, 4, 4>(c); return true;
+    case 4030308: launch_sqdist<3, 8, true, 3, 4>(c); return true;
+    // narrow column groups for small models (more workgroups per launch)
+    case 4000804: launch_sqdist<8, 4, true, 1, 4>(c); return true;
+    case 4000402: launch_sqdist<4, 2, true, 1, 2>(c); return true;
+    case 4000801: launch_sqdist<8, 1, true, 1, 1>(c); return true;
+    case 4001601: launch_sqdist<16, 1, true, 1, 1>(c); return true;
+    case 4000116: launch_sqdist<1, 16, true, 1, 4>(c); return true;
+    // interleaved loads and squares, L loads in flight: + 100000000 x L
+    case 204000216: launch_sqdist<2, 16, true, 1, 4, 2>(c); return true;
+    case 404000216: launch_sqdist<2, 16, true, 1, 4, 4>(c); return true;
+    case 804000216: launch_sqdist<2, 16, true, 1, 4, 8>(c); return true;
+    case 204000404: launch_sqdist<4, 4, true, 1, 4, 2>(c); return true;
+    case 404000404: launch_sqdist<4, 4, true, 1, 4, 4>(c); return true;
+    case 204000408: launch_sqdist<4, 8, true, 1, 4, 2>(c); return true;
+    case 404000408: launch_sqdist<4, 8, true, 1, 4, 4>(c); return true;
+  }
+  return false;
+}
+
+// a probe entry point's call: `cols_ok` and its refusal, then the code's launch
+int sqdist_probe(const DistCall& c, int unroll, int cols, bool cols_ok, const char* cols_list,
+                 bool (*launch)(int code, const DistCall&)) {
+  if (const int rc = check_dist(c.clients, c.K, c.P, c.ld, c.glob, c.sumsq, 4, c.what)) return rc;
+  if (!cols_ok) return set_error(FEDAVG_EMODE, "%s: cols must be %s", c.what, cols_list);
+  return dist_launch(c, cols, [&] {
+    if (!launch(unroll * 100 + cols, c))
+      return set_error(FEDAVG_EMODE, "%s: unsupported unroll=%d cols=%d", c.what, unroll, cols);
+    return static_cast<int>(FEDAVG_OK);
+  });
+}
+#endif  // FEDAVG_TUNING
 
 }  // namespace
 
@@ -1669,23 +1511,20 @@ extern "C" {
 
 int64_t fedavg_client_sqdist_workspace(int64_t K, int64_t P) {
   if (K <= 0 || P <= 0) return 0;
-  return K * sqdist_waves_for(P, dist_cols(P) < 4 ? dist_cols(P) : 4);  // production; any variant of >= 4 slices
+  return dist_workspace(K, P, dist_plan_here(P));
 }
 
 int fedavg_client_sqdist_f32(const float* clients, int64_t K, int64_t P, int64_t ld, const float* glob,
                              double* workspace, int64_t workspace_elems, double* sumsq, void* stream) {
-  // unroll codes: chains x 10000 + rows per batch (4 chains, at most one per slice)
-  const int cols = P > 0 ? dist_cols(P) : kDistBufCols;
-  const int rows = cols == 16 ? kDistBufRows : (cols == 8 || cols == 4 ? 4 : 8);
-  return sqdist_buf_impl(clients, K, P, ld, glob, workspace, workspace_elems, sumsq, kDistBufChains * 10000 + rows,
-                         cols, 0, stream, "fedavg_client_sqdist_f32");
+  const char* what = "fedavg_client_sqdist_f32";
+  if (const int rc = check_dist(clients, K, P, ld, glob, sumsq, 4, what)) return rc;
+  return sqdist_production(
+      DistCall{clients, K, P, ld, glob, workspace, workspace_elems, sumsq, 0, static_cast<hipStream_t>(stream), what});
 }
 
 int64_t fedavg_client_sqdist_workspace_elems(int64_t K, int64_t P, int64_t elem_size) {
-  if (K <= 0 || P <= 0 || (elem_size != 2 && elem_size != 4 && elem_size != 8)) return 0;
-  const int64_t lanes = 16 / elem_size;
-  const int64_t nvec = (P + lanes - 1) / lanes;
-  return K * sqdist_vec_waves(nvec, dist_vec_cols(nvec));
+  if (K <= 0 || dist_vec_slices(P, elem_size) <= 0) return 0;
+  return dist_vec_workspace(K, P, elem_size, cu_count());
 }
 
 int fedavg_client_sqdist_f64(const double* clients, int64_t K, int64_t P, int64_t ld, const double* glob,
@@ -1710,16 +1549,18 @@ int fedavg_client_sqdist_bf16(const uint16_t* clients, int64_t K, int64_t P, int
 int fedavg_client_sqdist_variant(const float* clients, int64_t K, int64_t P, int64_t ld, const float* glob,
                                  double* workspace, int64_t workspace_elems, double* sumsq, int unroll, int cols,
                                  int max_blocks, void* stream) {
-  return sqdist_impl(clients, K, P, ld, glob, workspace, workspace_elems, sumsq, unroll, cols, max_blocks, stream);
+  const DistCall call{clients, K, P, ld, glob, workspace, workspace_elems, sumsq, max_blocks,
+                      static_cast<hipStream_t>(stream), "fedavg_client_sqdist_f32"};
+  return sqdist_probe(call, unroll, cols, cols == 4 || cols == 8, "4 or 8", launch_sqdist_variant);
 }
-#endif  // FEDAVG_TUNING
 
-#ifdef FEDAVG_TUNING  // probe library only (libfedavg_amd_probe.so)
 int fedavg_client_sqdist_buf(const float* clients, int64_t K, int64_t P, int64_t ld, const float* glob,
                              double* workspace, int64_t workspace_elems, double* sumsq, int unroll, int cols,
                              int max_blocks, void* stream) {
-  return sqdist_buf_impl(clients, K, P, ld, glob, workspace, workspace_elems, sumsq, unroll, cols, max_blocks, stream,
-                         "fedavg_client_sqdist_buf");
+  const DistCall call{clients, K, P, ld, glob, workspace, workspace_elems, sumsq, max_blocks,
+                      static_cast<hipStream_t>(stream), "fedavg_client_sqdist_buf"};
+  return sqdist_probe(call, unroll, cols, cols == 1 || cols == 2 || cols == 4 || cols == 8 || cols == 12 || cols == 16,
+                      "1, 2, 4, 8, 12 or 16", launch_sqdist_buf_variant);
 }
 #endif  // FEDAVG_TUNING
 
@@ -1730,10 +1571,7 @@ int fedavg_client_sqdist_buf(const float* clients, int64_t K, int64_t P, int64_t
 // fedavg_reduce_f32's bits and sumsq the :291 sums.
 int64_t fedavg_reduce_sqdist_workspace(int64_t K, int64_t P) {
   if (K <= 0 || P <= 0) return 0;
-  const FusedPlan pl = fused_plan(K, P);
-  const int64_t two_pass = fedavg_client_sqdist_workspace(K, P);
-  const int64_t fused = K * fused_plan_parts(pl, K, P);
-  return fused > two_pass ? fused : two_pass;
+  return fused_workspace(K, P, fedavg_client_sqdist_workspace(K, P), fused_plan_parts);
 }
 
 int fedavg_reduce_sqdist_f32(const float* clients, int64_t K, int64_t P, int64_t ld, const float* weights, float* out,

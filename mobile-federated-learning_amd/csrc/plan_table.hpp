@@ -7,7 +7,7 @@
 // its instances through the same table.  Tables: here (the window kernels'
 // bands and grid rules, for window.hpp and segments_plan.hpp alike),
 // reduce_plan.hpp (the row reduce's forms), segments_plan.hpp (the zero-copy
-// passes') and the translation units' own.
+// passes'), dist_plan.hpp (the rows passes') and the translation units' own.
 #pragma once
 
 #include <cstddef>
@@ -36,7 +36,7 @@ bool for_entry(int a, int b, F&& f) {
 // Plan tables of the window kernels (fedavg_dist.hip's [K, ld] rows and
 // fedavg_segments.hip's zero-copy forms).
 // One-wave windows, 17..128 rows: {KMAX, VEC} by band (measurements:
-// fedavg_dist.hip's fused_plan notes).  The only place the bands are written.
+// dist_plan.hpp's fused_plan notes).  The only place the bands are written.
 constexpr PlanEntry kWinBands[] = {{48, 4}, {64, 2}, {80, 2}, {100, 2}, {128, 1}};
 constexpr int64_t kWinMinK = 17;
 

@@ -4,8 +4,9 @@
 
 Loads DIR/libfedavg_amd.so (default: the package's lib/) and times, per call
 and on the host alone (the stream is synchronized outside the timed region),
-fedavg_reduce_sqdist_f32 at 10 x 7850 and 100 x 600372 and
-fedavg_device_round_f32 at resnet56 x 100.  These rounds are launch-bound:
+fedavg_reduce_sqdist_f32 at 10 x 7850 and 100 x 600372,
+fedavg_client_sqdist_f32 and fedavg_client_sqdist_workspace at 100 x 600372
+and fedavg_device_round_f32 at resnet56 x 100.  These rounds are launch-bound:
 the figures are the cost of the plan, the occupancy lookups, the workspace
 check and the launches.  One JSON line with the medians in microseconds.
 Compare builds by alternating processes on one machine (A, B, A): the spread
@@ -33,7 +34,8 @@ from model_shapes import resnet56_shapes
 
 def typed(path):
     lib = ctypes.CDLL(str(path))
-    for name in ("fedavg_reduce_sqdist_workspace", "fedavg_reduce_sqdist_f32", "fedavg_reduce_sqdist_segments_partials",
+    for name in ("fedavg_reduce_sqdist_workspace", "fedavg_reduce_sqdist_f32", "fedavg_client_sqdist_workspace",
+                 "fedavg_client_sqdist_f32", "fedavg_reduce_sqdist_segments_partials",
                  "fedavg_device_round_scratch", "fedavg_device_round_workspace", "fedavg_device_round_f32"):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _lib.SIGNATURES[name]
@@ -62,6 +64,16 @@ def rows_call(lib, dev, K, P):
     ws = torch.empty(lib.fedavg_reduce_sqdist_workspace(K, P), dtype=torch.float64, device=dev)
     return lambda: lib.fedavg_reduce_sqdist_f32(x.data_ptr(), K, P, ld, w.data_ptr(), out.data_ptr(), ws.data_ptr(),
                                                 ws.numel(), sumsq.data_ptr(), None)
+
+
+def dist_call(lib, dev, K, P):
+    ld = (P + 63) // 64 * 64
+    x = torch.zeros((K, ld), device=dev)
+    glob = torch.zeros(ld, device=dev)
+    sumsq = torch.empty(K, dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.fedavg_client_sqdist_workspace(K, P), dtype=torch.float64, device=dev)
+    return lambda: lib.fedavg_client_sqdist_f32(x.data_ptr(), K, P, ld, glob.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                sumsq.data_ptr(), None)
 
 
 def round_call(lib, dev, K):
@@ -101,6 +113,9 @@ def main():
     res = {"label": args.label, "lib_dir": str(args.lib_dir), "reps": args.reps}
     for name, call in (("reduce_sqdist_f32_10x7850_us", rows_call(lib, dev, 10, 7850)),
                        ("reduce_sqdist_f32_100x600372_us", rows_call(lib, dev, 100, 600372)),
+                       ("client_sqdist_f32_100x600372_us", dist_call(lib, dev, 100, 600372)),
+                       ("client_sqdist_workspace_100x600372_us",
+                        lambda: 0 * lib.fedavg_client_sqdist_workspace(100, 600372)),
                        ("device_round_f32_resnet56x100_us", round_call(lib, dev, 100))):
         res[name] = median_us(call, args.reps, args.warmup)
     print(json.dumps(res))

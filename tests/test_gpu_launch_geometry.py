@@ -63,6 +63,9 @@ def collect_rows(lib):
         "fused_plan_of": [[lib.fedavg_fused_plan_of(K, P) for P in ROW_P] for K in ROW_K],
         "reduce_sqdist_workspace": [[lib.fedavg_reduce_sqdist_workspace(K, P) for P in ROW_P] for K in ROW_K],
         "client_sqdist_workspace": [[lib.fedavg_client_sqdist_workspace(K, P) for P in ROW_P] for K in ROW_K],
+        # the fp16 / bf16 (2), fp32-sized (4) and fp64 (8) distance pass
+        "client_sqdist_workspace_elems": {str(es): [[lib.fedavg_client_sqdist_workspace_elems(K, P, es) for P in ROW_P]
+                                                    for K in ROW_K] for es in (2, 4, 8)},
     }
 
 

@@ -872,6 +872,40 @@ def test_client_sqdist_buffer_descriptor_variants(K, P):
         assert torch.equal(outs[0], outs[1]), (u, c, mb)
 
 
+# (unroll code, cols, P): production's U8 x C2 on 6 workgroups with a ragged
+# last slice, and U2 x C16 on 3 (unroll = chains x 10000 + rows per batch)
+@pytest.mark.parametrize("unroll,cols,P", [(40008, 2, 5 * 2048 + 3), (40002, 16, 2 * 16384 + 1)])
+def test_client_sqdist_cut_launches_bit_identical(unroll, cols, P):
+    """The distance pass cut into launches of max_blocks workgroups against
+    the uncut launch: the cut launches write the same partials at the same
+    offsets and the finalize order is fixed, so the sums are equal bit for bit
+    (1, 2, 4 and 5 workgroups per launch: 6 / 3 launches down to 2 / 1)."""
+    lib = mfl_amd._lib.load_probe()
+    K = 3
+    ld = (P + 63) // 64 * 64
+    g = torch.Generator(device=DEV).manual_seed(K + P)
+    x = torch.full((K, ld), float("nan"), device=DEV)
+    x[:, :P] = torch.randn((K, P), generator=g, device=DEV) * 0.05
+    glob = torch.full((ld,), float("nan"), device=DEV)
+    glob[:P] = torch.randn(P, generator=g, device=DEV) * 0.05
+    ref = torch.stack([((x[k, :P] - glob[:P]).double() ** 2).sum() for k in range(K)])
+    blocks = -(-((P + 3) // 4) // (256 * cols))
+    assert blocks == (6 if cols == 2 else 3)
+    n_ws = K * blocks * 4
+    outs = {}
+    for mb in (0, 1, 2, 4, 5):
+        work = torch.full((n_ws,), float("nan"), dtype=torch.float64, device=DEV)
+        o = torch.empty(K, dtype=torch.float64, device=DEV)
+        mfl_amd._lib.check(lib.fedavg_client_sqdist_buf(x.data_ptr(), K, P, ld, glob.data_ptr(), work.data_ptr(), n_ws,
+                                                        o.data_ptr(), unroll, cols, mb, None), f"U{unroll}C{cols}mb{mb}")
+        outs[mb] = o
+    torch.cuda.synchronize()
+    rel = ((outs[0] - ref).abs() / ref).max().item()
+    assert rel < 1e-12, rel
+    for mb, o in outs.items():
+        assert torch.equal(o, outs[0]), (mb, o, outs[0])
+
+
 def test_client_sqdist_padding_nan_ignored():
     K, P = 3, 1001  # P % 4 == 1: the last float4 holds 3 padding lanes
     x = torch.full((K, 1024), float("nan"), device=DEV)

@@ -17,6 +17,10 @@
   HIP-free plan header (``csrc/segments_plan.hpp``) against the plans recorded
   in ``tests/segments_plan_cases.txt``, its form tables, the partials' bounds
   and the unfused passes' round-split cut.
+* ``tests/native/dist_plan_check.cpp`` (always): the [K, ld] rows passes'
+  HIP-free plan header (``csrc/dist_plan.hpp``) against the plans recorded in
+  ``tests/dist_plan_cases.txt``, its form tables, the workspace bounds and the
+  distance pass's round-split cut.
 * ``fedavg_collect_ext`` (the state_dict walk, ``verify_rows``) built with
   ``-fsanitize=address,undefined`` and the CPU suites that drive it run under
   ``LD_PRELOAD=libasan`` -- opt-in (``MFL_ASAN_TESTS=1``; it compiles a torch
@@ -82,6 +86,25 @@ def test_segments_plan_under_asan_ubsan(tmp_path):
     subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([str(exe), str(ROOT / "tests" / "segments_plan_cases.txt")], capture_output=True, text=True,
+                       timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert " 0 failures" in r.stdout and "ERROR" not in r.stderr, r.stdout + r.stderr
+
+
+@pytest.mark.skipif(_gxx() is None, reason="g++ not found")
+def test_dist_plan_under_asan_ubsan(tmp_path):
+    """csrc/dist_plan.hpp against tests/dist_plan_cases.txt (recorded from the
+    planner text of fedavg_dist.hip it replaced, two stub tables for the
+    kernels' residency): the fused plan and workspace, the distance pass's
+    forms and workspaces equal every recorded line, every plan names a table
+    entry, the workspace covers the chosen launch, and round_split cuts as
+    launch_sqdist's loop did (tests/native/dist_plan_check.cpp)."""
+    exe = tmp_path / "dist_plan_check"
+    cmd = [_gxx(), "-std=c++17", "-O1", "-g", *SAN, f"-I{ROOT / 'include'}", f"-I{CSRC}",
+           str(ROOT / "tests" / "native" / "dist_plan_check.cpp"), "-o", str(exe)]
+    subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe), str(ROOT / "tests" / "dist_plan_cases.txt")], capture_output=True, text=True,
                        timeout=300, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     assert " 0 failures" in r.stdout and "ERROR" not in r.stderr, r.stdout + r.stderr
