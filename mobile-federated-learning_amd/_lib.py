@@ -1,15 +1,17 @@
-"""ctypes binding of libfedavg_amd.so (the C ABI in include/fedavg_amd.h).
+"""ctypes binding of the native libraries ``build.LIBS`` describes (the C ABI
+in include/*.h): a signature table each, one loader and one status check.
 
-There is no fallback: if the HIP library is missing or does not export the
+There is no fallback: if a HIP library is missing or does not export the
 declared entry points, every product call raises ``FedAvgLibraryError``.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 import threading
 from pathlib import Path
 
-from .build import CLIENTVEC_LIB_PATH, FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH
+from .build import BY_KEY, CLIENTVEC_LIB_PATH, FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH, NativeLib
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -151,10 +153,10 @@ CLIENTVEC_SIGNATURES = {
     "fedavg_client_track_f64": _CLIENTVEC_TRACK,
 }
 
-ABI_VERSION = 1
-FUSEDVEC_ABI_VERSION = 1
-SEGVEC_ABI_VERSION = 1
-CLIENTVEC_ABI_VERSION = 1
+ABI_VERSION = BY_KEY["product"].abi[1]
+FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
+SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
+CLIENTVEC_ABI_VERSION = BY_KEY["clientvec"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -169,8 +171,18 @@ class FpfGroups(ctypes.Structure):
 
 
 class FedAvgLibraryError(RuntimeError):
-    """libfedavg_amd.so is missing, stale, or a call into it failed."""
+    """A native library is missing, stale, or a call into it failed."""
 
+
+# description key -> (its signature tables, the module-level name of its path, the module-level name of its cache
+# slot).  _load reads both names when it runs, so a test that patches them is served.
+_BINDING = {
+    "product": ((SIGNATURES,), "LIB_PATH", "_lib"),
+    "probe": ((SIGNATURES, TUNING_SIGNATURES), "PROBE_LIB_PATH", "_probe"),
+    "fusedvec": ((FUSEDVEC_SIGNATURES,), "FUSEDVEC_LIB_PATH", "_fusedvec"),
+    "segvec": ((SEGVEC_SIGNATURES,), "SEGVEC_LIB_PATH", "_segvec"),
+    "clientvec": ((CLIENTVEC_SIGNATURES,), "CLIENTVEC_LIB_PATH", "_clientvec"),
+}
 
 _lock = threading.Lock()
 _lib = None
@@ -184,174 +196,91 @@ def library_path() -> Path:
     return LIB_PATH
 
 
-def load() -> ctypes.CDLL:
-    """Load (once) and type the HIP library; raise loudly if unavailable."""
-    global _lib
-    if _lib is not None:
-        return _lib
+def _load(d: NativeLib) -> ctypes.CDLL:
+    """Load (once), type and version-check the library ``d`` describes.  No
+    fallback: a missing, unloadable or stale library raises ``FedAvgLibraryError``."""
+    tables, path_name, slot = _BINDING[d.key]
+    g = globals()
+    if g[slot] is not None:
+        return g[slot]
+    if d.needs:
+        _load(BY_KEY[d.needs])
     with _lock:
-        if _lib is not None:
-            return _lib
-        if not LIB_PATH.exists():
-            raise FedAvgLibraryError(
-                f"{LIB_PATH} not built: run __graft_entry__.build() (hipcc --offload-arch=gfx950); "
-                "there is no CPU fallback for the FedAvg reduction"
-            )
-        lib = ctypes.CDLL(str(LIB_PATH))
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise FedAvgLibraryError(f"{LIB_PATH} does not export {name}") from e
-            fn.restype = res
-            fn.argtypes = args
-        ver = lib.fedavg_abi_version()
-        if ver != ABI_VERSION:
-            raise FedAvgLibraryError(f"ABI version {ver} != expected {ABI_VERSION}; rebuild the library")
-        _lib = lib
-    return _lib
+        if g[slot] is not None:
+            return g[slot]
+        path = g[path_name]
+        if not path.exists():
+            raise FedAvgLibraryError(f"{path} not built: run __graft_entry__.build(){d.no_fallback}")
+        try:
+            lib = ctypes.CDLL(str(path))
+        except OSError as e:
+            raise FedAvgLibraryError(f"{path} does not load: {e}") from e
+        for table in tables:
+            for name, (res, args) in table.items():
+                try:
+                    fn = getattr(lib, name)
+                except AttributeError as e:
+                    raise FedAvgLibraryError(f"{path} does not export {name}") from e
+                fn.restype = res
+                fn.argtypes = args
+        symbol, expected = d.abi
+        ver = getattr(lib, symbol)()
+        if ver != expected:
+            raise FedAvgLibraryError(f"ABI version {ver} != expected {expected}; rebuild the library")
+        g[slot] = lib
+    return lib
+
+
+def _check(d: NativeLib, rc: int, what: str) -> None:
+    """Raise on a non-zero status of a call into ``d``'s library, with that library's own message."""
+    if rc != 0:
+        msg = getattr(_load(d), d.last_error)().decode(errors="replace")
+        raise FedAvgLibraryError(f"{what} failed (rc={rc}): {msg}")
+
+
+# The loaders.  Warm, each reads its own module-level slot and returns it: load() runs once per product call.
+def load() -> ctypes.CDLL:
+    """The product library (include/fedavg_amd.h)."""
+    return _lib if _lib is not None else _load(BY_KEY["product"])
 
 
 def load_probe() -> ctypes.CDLL:
     """The probe library (product entry points + the tuning hooks of
     include/fedavg_amd_tuning.h).  Scripts and variant tests only; the
     product path never loads it."""
-    global _probe
-    if _probe is not None:
-        return _probe
-    with _lock:
-        if _probe is not None:
-            return _probe
-        if not PROBE_LIB_PATH.exists():
-            raise FedAvgLibraryError(f"{PROBE_LIB_PATH} not built: run __graft_entry__.build()")
-        lib = ctypes.CDLL(str(PROBE_LIB_PATH))
-        for name, (res, args) in {**SIGNATURES, **TUNING_SIGNATURES}.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise FedAvgLibraryError(f"{PROBE_LIB_PATH} does not export {name}") from e
-            fn.restype = res
-            fn.argtypes = args
-        _probe = lib
-    return _probe
+    return _probe if _probe is not None else _load(BY_KEY["probe"])
 
 
 def load_fusedvec() -> ctypes.CDLL:
     """The fused aggregate + :291 library for fp64 / fp16 / bf16 rows
-    (include/fedavg_amd_fusedvec.h).  It calls the product library for its
-    two-pass route, so that one is loaded first.  No fallback: a missing or
-    stale library raises ``FedAvgLibraryError``."""
-    global _fusedvec
-    if _fusedvec is not None:
-        return _fusedvec
-    load()
-    with _lock:
-        if _fusedvec is not None:
-            return _fusedvec
-        if not FUSEDVEC_LIB_PATH.exists():
-            raise FedAvgLibraryError(
-                f"{FUSEDVEC_LIB_PATH} not built: run __graft_entry__.build(); there is no fallback for the "
-                "one-read aggregate + distances pass of fp64 / fp16 / bf16 rows")
-        try:
-            lib = ctypes.CDLL(str(FUSEDVEC_LIB_PATH))
-        except OSError as e:
-            raise FedAvgLibraryError(f"{FUSEDVEC_LIB_PATH} does not load: {e}") from e
-        for name, (res, args) in FUSEDVEC_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise FedAvgLibraryError(f"{FUSEDVEC_LIB_PATH} does not export {name}") from e
-            fn.restype = res
-            fn.argtypes = args
-        ver = lib.fedavg_fusedvec_abi_version()
-        if ver != FUSEDVEC_ABI_VERSION:
-            raise FedAvgLibraryError(f"ABI version {ver} != expected {FUSEDVEC_ABI_VERSION}; rebuild the library")
-        _fusedvec = lib
-    return _fusedvec
+    (include/fedavg_amd_fusedvec.h); loads the product library first."""
+    return _fusedvec if _fusedvec is not None else _load(BY_KEY["fusedvec"])
 
 
 def load_segvec() -> ctypes.CDLL:
-    """The zero-copy device-round library for fp64 / fp16 / bf16 groups
-    (include/fedavg_amd_segvec.h).  It calls no other library.  No fallback:
-    a missing or stale library raises ``FedAvgLibraryError``."""
-    global _segvec
-    if _segvec is not None:
-        return _segvec
-    with _lock:
-        if _segvec is not None:
-            return _segvec
-        if not SEGVEC_LIB_PATH.exists():
-            raise FedAvgLibraryError(
-                f"{SEGVEC_LIB_PATH} not built: run __graft_entry__.build(); there is no fallback for the "
-                "zero-copy device round of fp64 / fp16 / bf16 groups")
-        try:
-            lib = ctypes.CDLL(str(SEGVEC_LIB_PATH))
-        except OSError as e:
-            raise FedAvgLibraryError(f"{SEGVEC_LIB_PATH} does not load: {e}") from e
-        for name, (res, args) in SEGVEC_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise FedAvgLibraryError(f"{SEGVEC_LIB_PATH} does not export {name}") from e
-            fn.restype = res
-            fn.argtypes = args
-        ver = lib.fedavg_segvec_abi_version()
-        if ver != SEGVEC_ABI_VERSION:
-            raise FedAvgLibraryError(f"ABI version {ver} != expected {SEGVEC_ABI_VERSION}; rebuild the library")
-        _segvec = lib
-    return _segvec
+    """The zero-copy device-round library for fp64 / fp16 / bf16 groups (include/fedavg_amd_segvec.h)."""
+    return _segvec if _segvec is not None else _load(BY_KEY["segvec"])
 
 
 def load_clientvec() -> ctypes.CDLL:
-    """The client-statistics library for bf16 / fp16 / fp64 models
-    (include/fedavg_amd_clientvec.h).  It calls no other library.  No
-    fallback: a missing or stale library raises ``FedAvgLibraryError``."""
-    global _clientvec
-    if _clientvec is not None:
-        return _clientvec
-    with _lock:
-        if _clientvec is not None:
-            return _clientvec
-        if not CLIENTVEC_LIB_PATH.exists():
-            raise FedAvgLibraryError(
-                f"{CLIENTVEC_LIB_PATH} not built: run __graft_entry__.build(); there is no fallback for the "
-                "fused client statistics of bf16 / fp16 / fp64 models")
-        try:
-            lib = ctypes.CDLL(str(CLIENTVEC_LIB_PATH))
-        except OSError as e:
-            raise FedAvgLibraryError(f"{CLIENTVEC_LIB_PATH} does not load: {e}") from e
-        for name, (res, args) in CLIENTVEC_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise FedAvgLibraryError(f"{CLIENTVEC_LIB_PATH} does not export {name}") from e
-            fn.restype = res
-            fn.argtypes = args
-        ver = lib.fedavg_clientvec_abi_version()
-        if ver != CLIENTVEC_ABI_VERSION:
-            raise FedAvgLibraryError(f"ABI version {ver} != expected {CLIENTVEC_ABI_VERSION}; rebuild the library")
-        _clientvec = lib
-    return _clientvec
+    """The client-statistics library for bf16 / fp16 / fp64 models (include/fedavg_amd_clientvec.h)."""
+    return _clientvec if _clientvec is not None else _load(BY_KEY["clientvec"])
 
 
-def check_clientvec(rc: int, what: str) -> None:
-    """``check`` for a call into libfedavg_amd_clientvec.so (its own message)."""
+check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
+check_segvec = functools.partial(_check, BY_KEY["segvec"])
+check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
+
+
+def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:
+    """Raise on a non-zero status; the message comes from the library that
+    made the call (``lib``; default: the product library, or the probe
+    library when only that one is loaded)."""
     if rc != 0:
-        msg = load_clientvec().fedavg_clientvec_last_error().decode(errors="replace")
-        raise FedAvgLibraryError(f"{what} failed (rc={rc}): {msg}")
-
-
-def check_segvec(rc: int, what: str) -> None:
-    """``check`` for a call into libfedavg_amd_segvec.so (its own message)."""
-    if rc != 0:
-        msg = load_segvec().fedavg_segvec_last_error().decode(errors="replace")
-        raise FedAvgLibraryError(f"{what} failed (rc={rc}): {msg}")
-
-
-def check_fusedvec(rc: int, what: str) -> None:
-    """``check`` for a call into libfedavg_amd_fusedvec.so (its own message)."""
-    if rc != 0:
-        msg = load_fusedvec().fedavg_fusedvec_last_error().decode(errors="replace")
+        src = lib if lib is not None else (_lib if _lib is not None or _probe is None else _probe)
+        if src is None:
+            src = load()
+        msg = src.fedavg_last_error().decode(errors="replace")
         raise FedAvgLibraryError(f"{what} failed (rc={rc}): {msg}")
 
 
@@ -371,15 +300,3 @@ def f32_schedule(K: int, P: int, ld: int = 0) -> dict:
     sc["kernel"] = "reduce_f32x4_buf_kernel" if sc["nontemporal"] == 2 else "reduce_f32x4_var_kernel"
     sc["block"] = 256
     return sc
-
-
-def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:
-    """Raise on a non-zero status; the message comes from the library that
-    made the call (``lib``; default: the product library, or the probe
-    library when only that one is loaded)."""
-    if rc != 0:
-        src = lib if lib is not None else (_lib if _lib is not None or _probe is None else _probe)
-        if src is None:
-            src = load()
-        msg = src.fedavg_last_error().decode(errors="replace")
-        raise FedAvgLibraryError(f"{what} failed (rc={rc}): {msg}")

@@ -1,40 +1,17 @@
-"""Build recipe for libfedavg_amd.so, libfedavg_amd_probe.so,
-libfedavg_amd_fusedvec.so, libfedavg_amd_segvec.so and
-libfedavg_amd_clientvec.so (gfx950 only).
+"""Build recipe for the native libraries (gfx950 only); ``LIBS`` describes them.
 
     python -m mfl_amd.build           # or __graft_entry__.build()
 
-Compiles the HIP translation units in ``csrc/`` (``fedavg_reduce.hip``:
-production kernels + C ABI; ``fedavg_dist.hip``: the distance pass; FPF,
-transfer, device packing, zero-copy segment kernels and the client's
-per-iteration statistics) and
-``csrc/fedavg_host.cpp`` (native host packer) in parallel with hipcc for
-``--offload-arch=gfx950`` and links them into ``lib/libfedavg_amd.so`` inside
-the package (in-tree, so the built library travels with the repo snapshot to
-the GPU box).  ``-ffp-contract=off`` keeps every multiply and add separately
+Every translation unit of ``LIBS`` is compiled in parallel with hipcc for
+``--offload-arch=gfx950`` and each library is linked into ``lib/`` inside the
+package (in-tree, so the built libraries travel with the repo snapshot to the
+GPU box).  ``-ffp-contract=off`` keeps every multiply and add separately
 rounded (bit parity with the reference's ATen CPU ops,
 fedavg_trainer.py:455-457).
 
 The tuning hooks (``include/fedavg_amd_tuning.h``: kernel variants, probes)
-are NOT in the product library.  The same sources plus
-``fedavg_variants.hip``, compiled with ``-DFEDAVG_TUNING``, link into
-``lib/libfedavg_amd_probe.so``, which scripts/ and the variant tests load.
-
-``csrc/fedavg_fused_vec.hip`` (the one-read aggregate + :291 pass for fp64 /
-fp16 / bf16 rows, ``include/fedavg_amd_fusedvec.h``) is a product library of
-its own, ``lib/libfedavg_amd_fusedvec.so``: same flags, no ``FEDAVG_TUNING``,
-linked against ``libfedavg_amd.so`` (found next to it, ``$ORIGIN``) for the
-two-pass route.
-
-``csrc/fedavg_segments_vec.hip`` (a device-resident round's fp64 / fp16 / bf16
-group from the clients' own tensors, ``include/fedavg_amd_segvec.h``) is the
-third product library, ``lib/libfedavg_amd_segvec.so``: same flags, no
-``FEDAVG_TUNING``; it calls no other library, so it links none.
-
-``csrc/fedavg_client_vec.hip`` (the client's per-iteration statistics for
-bf16 / fp16 / fp64 models, ``include/fedavg_amd_clientvec.h``) is the fourth,
-``lib/libfedavg_amd_clientvec.so``: same flags, no ``FEDAVG_TUNING``, no
-other library linked.
+are NOT in the product library: only the probe library, which scripts/ and the
+variant tests load, is compiled with ``-DFEDAVG_TUNING``.
 """
 from __future__ import annotations
 
@@ -42,40 +19,80 @@ import os
 import shutil
 import subprocess
 import sys
+from dataclasses import dataclass
 from pathlib import Path
 
 PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
 CSRC_DIR = PKG_DIR / "csrc"
-# translation units of libfedavg_amd.so, compiled in parallel then linked
-HIP_SOURCES = [CSRC_DIR / "fedavg_reduce.hip", CSRC_DIR / "fedavg_dist.hip",
-               CSRC_DIR / "fedavg_fpf.hip", CSRC_DIR / "fedavg_xfer.hip", CSRC_DIR / "fedavg_pack.hip",
-               CSRC_DIR / "fedavg_segments.hip", CSRC_DIR / "fedavg_client.hip"]
-PROBE_SOURCES = [CSRC_DIR / "fedavg_variants.hip"]  # probe library only
-FUSEDVEC_SOURCES = [CSRC_DIR / "fedavg_fused_vec.hip"]  # libfedavg_amd_fusedvec.so only
-SEGVEC_SOURCES = [CSRC_DIR / "fedavg_segments_vec.hip"]  # libfedavg_amd_segvec.so only
-CLIENTVEC_SOURCES = [CSRC_DIR / "fedavg_client_vec.hip"]  # libfedavg_amd_clientvec.so only
-CSRC_HOST = CSRC_DIR / "fedavg_host.cpp"
-CSRC_COMMON = CSRC_DIR / "common.hpp"
-CSRC_WINDOW = CSRC_DIR / "window.hpp"  # what the rows and zero-copy window kernels share
-CSRC_STAGING = CSRC_DIR / "staging.hpp"  # host-side staged layouts (also g++-built by tests/native)
-CSRC_PLAN_TABLE = CSRC_DIR / "plan_table.hpp"  # PlanEntry / for_entry of every plan family
-CSRC_REDUCE_PLAN = CSRC_DIR / "reduce_plan.hpp"  # the row reduce's plan, forms and round-split cut (also g++-built)
-CSRC_SEGMENTS_PLAN = CSRC_DIR / "segments_plan.hpp"  # the zero-copy passes' plans, forms and bounds (also g++-built)
-CSRC_DIST_PLAN = CSRC_DIR / "dist_plan.hpp"  # the rows fused and distance passes' plans, forms and bounds (also g++-built)
-CSRC_VEC_RULES = CSRC_DIR / "fused_vec_rules.hpp"  # dtype rules and bands of the fused-vec and seg-vec kernels
 CSRC_COLLECT = CSRC_DIR / "fedavg_collect_ext.cpp"
 COLLECT_NAME = "fedavg_collect_ext"
 INCLUDE = REPO_DIR / "include"
 LIB_DIR = PKG_DIR / "lib"
-OBJ_DIR = LIB_DIR / "obj"
-PROBE_OBJ_DIR = LIB_DIR / "obj_probe"
-LIB_PATH = LIB_DIR / "libfedavg_amd.so"
-PROBE_LIB_PATH = LIB_DIR / "libfedavg_amd_probe.so"
-FUSEDVEC_LIB_PATH = LIB_DIR / "libfedavg_amd_fusedvec.so"
-SEGVEC_LIB_PATH = LIB_DIR / "libfedavg_amd_segvec.so"
-CLIENTVEC_LIB_PATH = LIB_DIR / "libfedavg_amd_clientvec.so"
 ARCH = "gfx950"
+
+
+@dataclass(frozen=True)
+class NativeLib:
+    """One native library: what build() compiles and links, and what
+    ``_lib._load`` / ``_lib._check`` need to load it and report its errors
+    (its signature table is ``_lib``'s, reached by ``key``)."""
+
+    key: str
+    file: str  # under lib/
+    header: str  # the public header under include/
+    units: tuple  # translation units under csrc/, one object each in lib/<obj_dir>/
+    abi: tuple  # (the ABI-version symbol, the value the binding expects)
+    last_error: str  # the symbol that returns the calling thread's message
+    no_fallback: str  # what follows "<path> not built: run __graft_entry__.build()" when the file is missing
+    defines: tuple = ()  # extra compile flags
+    link: tuple = ()  # extra link arguments
+    needs: str = ""  # key of the library that must be loaded first
+    obj_dir: str = "obj"
+    reuse: tuple = ()  # (key, unit): objects another library's compile already made, linked after this one's own
+
+    @property
+    def path(self) -> Path:
+        return LIB_DIR / self.file
+
+    @property
+    def sources(self):
+        return [CSRC_DIR / u for u in self.units]
+
+    def obj(self, unit: str) -> Path:
+        return LIB_DIR / self.obj_dir / (unit + ".o")
+
+
+_PRODUCT_UNITS = ("fedavg_reduce.hip", "fedavg_dist.hip", "fedavg_fpf.hip", "fedavg_xfer.hip", "fedavg_pack.hip",
+                  "fedavg_segments.hip", "fedavg_client.hip")
+
+LIBS = (
+    # production kernels + C ABI, the distance pass, FPF, transfer, device packing, zero-copy segment kernels, the
+    # client's per-iteration statistics and the native host packer
+    NativeLib("product", "libfedavg_amd.so", "fedavg_amd.h", (*_PRODUCT_UNITS, "fedavg_host.cpp"),
+              abi=("fedavg_abi_version", 1), last_error="fedavg_last_error",
+              no_fallback=" (hipcc --offload-arch=gfx950); there is no CPU fallback for the FedAvg reduction"),
+    # the same sources with the tuning hooks, plus the variants (the host packer has no hooks: the product's object)
+    NativeLib("probe", "libfedavg_amd_probe.so", "fedavg_amd_tuning.h", (*_PRODUCT_UNITS, "fedavg_variants.hip"),
+              abi=("fedavg_abi_version", 1), last_error="fedavg_last_error", no_fallback="",
+              defines=("-DFEDAVG_TUNING=1",), obj_dir="obj_probe", reuse=(("product", "fedavg_host.cpp"),)),
+    # the one-read aggregate + :291 pass of fp64 / fp16 / bf16 rows; its two-pass route calls the product library,
+    # found next to it at load time
+    NativeLib("fusedvec", "libfedavg_amd_fusedvec.so", "fedavg_amd_fusedvec.h", ("fedavg_fused_vec.hip",),
+              abi=("fedavg_fusedvec_abi_version", 1), last_error="fedavg_fusedvec_last_error",
+              no_fallback="; there is no fallback for the one-read aggregate + distances pass of fp64 / fp16 / bf16 rows",
+              link=(f"-L{LIB_DIR}", "-l:libfedavg_amd.so", "-Wl,-rpath,$ORIGIN"), needs="product"),
+    # a device-resident round's fp64 / fp16 / bf16 group from the clients' own tensors; calls no other library
+    NativeLib("segvec", "libfedavg_amd_segvec.so", "fedavg_amd_segvec.h", ("fedavg_segments_vec.hip",),
+              abi=("fedavg_segvec_abi_version", 1), last_error="fedavg_segvec_last_error",
+              no_fallback="; there is no fallback for the zero-copy device round of fp64 / fp16 / bf16 groups"),
+    # the client's per-iteration statistics for bf16 / fp16 / fp64 models; calls no other library
+    NativeLib("clientvec", "libfedavg_amd_clientvec.so", "fedavg_amd_clientvec.h", ("fedavg_client_vec.hip",),
+              abi=("fedavg_clientvec_abi_version", 1), last_error="fedavg_clientvec_last_error",
+              no_fallback="; there is no fallback for the fused client statistics of bf16 / fp16 / fp64 models"),
+)
+BY_KEY = {lib.key: lib for lib in LIBS}
+LIB_PATH, PROBE_LIB_PATH, FUSEDVEC_LIB_PATH, SEGVEC_LIB_PATH, CLIENTVEC_LIB_PATH = (lib.path for lib in LIBS)
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",
@@ -101,21 +118,15 @@ def hipcc_path() -> str:
 
 
 def sources():
-    return [*HIP_SOURCES, *PROBE_SOURCES, *FUSEDVEC_SOURCES, *SEGVEC_SOURCES, *CLIENTVEC_SOURCES, CSRC_HOST,
-            CSRC_COMMON, CSRC_WINDOW, CSRC_STAGING, CSRC_PLAN_TABLE, CSRC_REDUCE_PLAN, CSRC_SEGMENTS_PLAN,
-            CSRC_DIST_PLAN, CSRC_VEC_RULES, INCLUDE / "fedavg_amd.h",
-            INCLUDE / "fedavg_amd_tuning.h", INCLUDE / "fedavg_amd_fusedvec.h", INCLUDE / "fedavg_amd_segvec.h",
-            INCLUDE / "fedavg_amd_clientvec.h", Path(__file__)]
+    """Everything a library can depend on: every translation unit, every
+    header in csrc/ and include/ (found, not listed) and this recipe."""
+    units = dict.fromkeys(src for lib in LIBS for src in lib.sources)
+    return [*units, *sorted(CSRC_DIR.glob("*.hpp")), *sorted(INCLUDE.glob("*.h")), Path(__file__)]
 
 
 def up_to_date() -> bool:
-    for lib in (LIB_PATH, PROBE_LIB_PATH, FUSEDVEC_LIB_PATH, SEGVEC_LIB_PATH, CLIENTVEC_LIB_PATH):
-        if not lib.exists():
-            return False
-        t = lib.stat().st_mtime
-        if any(p.stat().st_mtime > t for p in sources()):
-            return False
-    return True
+    newest = max(p.stat().st_mtime for p in sources())
+    return all(lib.path.exists() and lib.path.stat().st_mtime >= newest for lib in LIBS)
 
 
 def collect_ext_path() -> Path:
@@ -170,45 +181,15 @@ def _link(objs, lib_path, verbose, extra=()):
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Build the product library, the probe library, the fused-vec library,
-    the seg-vec library and the client-vec library; returns the product path."""
+    """Build every library of ``LIBS``; returns the product library's path."""
     if not force and up_to_date():
         return LIB_PATH
-    OBJ_DIR.mkdir(parents=True, exist_ok=True)
-    PROBE_OBJ_DIR.mkdir(parents=True, exist_ok=True)
-    jobs, objs, probe_objs = [], [], []
-    for src in [*HIP_SOURCES, CSRC_HOST]:
-        obj = OBJ_DIR / (src.name + ".o")
-        jobs.append((src, obj, []))
-        objs.append(obj)
-    for src in [*HIP_SOURCES, *PROBE_SOURCES]:
-        obj = PROBE_OBJ_DIR / (src.name + ".o")
-        jobs.append((src, obj, ["-DFEDAVG_TUNING=1"]))
-        probe_objs.append(obj)
-    probe_objs.append(OBJ_DIR / (CSRC_HOST.name + ".o"))  # host packer: no tuning hooks
-    fusedvec_objs = []
-    for src in FUSEDVEC_SOURCES:
-        obj = OBJ_DIR / (src.name + ".o")
-        jobs.append((src, obj, []))
-        fusedvec_objs.append(obj)
-    segvec_objs = []
-    for src in SEGVEC_SOURCES:
-        obj = OBJ_DIR / (src.name + ".o")
-        jobs.append((src, obj, []))
-        segvec_objs.append(obj)
-    clientvec_objs = []
-    for src in CLIENTVEC_SOURCES:
-        obj = OBJ_DIR / (src.name + ".o")
-        jobs.append((src, obj, []))
-        clientvec_objs.append(obj)
-    _compile_all(jobs, verbose)
-    _link(objs, LIB_PATH, verbose)
-    _link(probe_objs, PROBE_LIB_PATH, verbose)
-    # the two-pass route calls the product library, found next to this one at load time
-    _link(fusedvec_objs, FUSEDVEC_LIB_PATH, verbose,
-          extra=[f"-L{LIB_DIR}", f"-l:{LIB_PATH.name}", "-Wl,-rpath,$ORIGIN"])
-    _link(segvec_objs, SEGVEC_LIB_PATH, verbose)  # calls no other library
-    _link(clientvec_objs, CLIENTVEC_LIB_PATH, verbose)  # calls no other library
+    for lib in LIBS:
+        (LIB_DIR / lib.obj_dir).mkdir(parents=True, exist_ok=True)
+    _compile_all([(CSRC_DIR / u, lib.obj(u), list(lib.defines)) for lib in LIBS for u in lib.units], verbose)
+    for lib in LIBS:  # in order: a library links after the one its link arguments name
+        objs = [lib.obj(u) for u in lib.units] + [BY_KEY[key].obj(u) for key, u in lib.reuse]
+        _link(objs, lib.path, verbose, extra=lib.link)
     return LIB_PATH
 
 

@@ -33,6 +33,7 @@
 #include <mutex>
 #include <utility>
 
+#include "error_state.hpp"
 #include "fedavg_amd.h"
 #include "fedavg_amd_tuning.h"
 #include "reduce_plan.hpp"
@@ -92,7 +93,17 @@ struct F16Pk {
   __device__ static unsigned short canon(unsigned short h) { return h; }  // NaN payloads are not specified
 };
 
-// Error state (thread-local message), defined in fedavg_reduce.hip.
+// The status of the launch just made, into the calling library's error state
+// (error_state.hpp): the HIP error as a negative code with its text, or
+// FEDAVG_OK and an empty message.
+__attribute__((visibility("hidden"))) inline int launch_status(ErrorState& err, const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return err.set(-static_cast<int>(e), "%s: launch failed: %s", what, hipGetErrorString(e));
+  err.clear();
+  return FEDAVG_OK;
+}
+
+// libfedavg_amd.so's error state (thread-local message), defined in fedavg_reduce.hip.
 int set_error(int code, const char* fmt, ...);
 int launch_status(const char* what);
 const char* last_error_message();

@@ -28,22 +28,17 @@
 namespace {
 using namespace fedavg_impl;
 
-thread_local char g_cv_err[512] = "";
+thread_local ErrorState g_cv_err;
 
 int cv_error(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(g_cv_err, sizeof(g_cv_err), fmt, ap);
+  g_cv_err.vset(code, fmt, ap);
   va_end(ap);
   return code;
 }
 
-int cv_launch_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return cv_error(-static_cast<int>(e), "%s: launch failed: %s", what, hipGetErrorString(e));
-  g_cv_err[0] = '\0';
-  return FEDAVG_OK;
-}
+int cv_launch_status(const char* what) { return launch_status(g_cv_err, what); }
 
 // the staged key table entry: tensor address, elements, snapshot offset, first unit
 struct ClientKey {
@@ -384,7 +379,7 @@ extern "C" {
 
 int fedavg_clientvec_abi_version(void) { return 1; }
 
-const char* fedavg_clientvec_last_error(void) { return g_cv_err; }
+const char* fedavg_clientvec_last_error(void) { return g_cv_err.c_str(); }
 
 int64_t fedavg_client_stats_vec_span(int64_t elem_size) { return span_of(elem_size); }
 

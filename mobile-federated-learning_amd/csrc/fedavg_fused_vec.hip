@@ -34,22 +34,17 @@
 namespace {
 using namespace fedavg_impl;
 
-thread_local char g_fv_err[512] = "";
+thread_local ErrorState g_fv_err;
 
 int fv_error(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(g_fv_err, sizeof(g_fv_err), fmt, ap);
+  g_fv_err.vset(code, fmt, ap);
   va_end(ap);
   return code;
 }
 
-int fv_launch_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fv_error(-static_cast<int>(e), "%s: launch failed: %s", what, hipGetErrorString(e));
-  g_fv_err[0] = '\0';
-  return FEDAVG_OK;
-}
+int fv_launch_status(const char* what) { return launch_status(g_fv_err, what); }
 
 // ---------------------------------------------------------------------------
 // The kernel.  X: the rows as bytes; row_bytes = ld * sizeof(elem), a multiple
@@ -273,7 +268,7 @@ int reduce_sqdist_vec(const void* clients, int64_t K, int64_t P, int64_t ld, con
   if (rc) return fv_product_error(rc, what);
   rc = sqdist(clients, K, P, ld, out, workspace, workspace_elems, sumsq, stream);
   if (rc) return fv_product_error(rc, what);
-  g_fv_err[0] = '\0';
+  g_fv_err.clear();
   return FEDAVG_OK;
 }
 
@@ -283,7 +278,7 @@ extern "C" {
 
 int fedavg_fusedvec_abi_version(void) { return 1; }
 
-const char* fedavg_fusedvec_last_error(void) { return g_fv_err; }
+const char* fedavg_fusedvec_last_error(void) { return g_fv_err.c_str(); }
 
 // K x the most partials per row either route writes.  Fused: the finest
 // slice's windows (4 B per lane), at most kVecMaxWaves.  Two passes: the

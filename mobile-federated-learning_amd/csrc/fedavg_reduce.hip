@@ -7,27 +7,20 @@
 namespace fedavg_impl {
 
 namespace {
-thread_local char g_err[512] = "";
+thread_local ErrorState g_err;
 }  // namespace
 
 int set_error(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  g_err.vset(code, fmt, ap);
   va_end(ap);
   return code;
 }
 
-int launch_status(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    return set_error(-static_cast<int>(e), "%s: launch failed: %s", what, hipGetErrorString(e));
-  }
-  g_err[0] = '\0';
-  return FEDAVG_OK;
-}
+int launch_status(const char* what) { return launch_status(g_err, what); }
 
-const char* last_error_message() { return g_err; }
+const char* last_error_message() { return g_err.c_str(); }
 
 int check_common(const void* clients, int64_t K, int64_t P, int64_t ld, const void* weights,
                  const void* out, const char* what) {
@@ -876,7 +869,7 @@ int fedavg_weights_f32(const int64_t* sample_nums, int64_t K, float* weights) {
     volatile double w = static_cast<double>(sample_nums[i]) / n;  // Python int / int (exact operands)
     weights[i] = static_cast<float>(w);                             // ATen double -> float scalar cast
   }
-  g_err[0] = '\0';
+  g_err.clear();
   return FEDAVG_OK;
 }
 

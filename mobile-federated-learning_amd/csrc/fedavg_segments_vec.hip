@@ -18,22 +18,17 @@
 namespace {
 using fedavg_staging::SegKey;
 
-thread_local char g_sv_err[512] = "";
+thread_local fedavg_impl::ErrorState g_sv_err;
 
 int sv_error(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(g_sv_err, sizeof(g_sv_err), fmt, ap);
+  g_sv_err.vset(code, fmt, ap);
   va_end(ap);
   return code;
 }
 
-int sv_launch_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return sv_error(-static_cast<int>(e), "%s: launch failed: %s", what, hipGetErrorString(e));
-  g_sv_err[0] = '\0';
-  return FEDAVG_OK;
-}
+int sv_launch_status(const char* what) { return fedavg_impl::launch_status(g_sv_err, what); }
 
 // client addresses arrive as integers: an explicit global pointer, or the
 // table loads would be flat loads (fedavg_segments.hip's gptr)
@@ -343,7 +338,7 @@ int device_round_vec(const int64_t* client_ptrs, int64_t ptr_ld, const int64_t* 
   if (!st.first_src) {  // every key empty: nothing to read, nothing to average
     const hipError_t e = hipMemsetAsync(sumsq, 0, static_cast<size_t>(K) * sizeof(double), s);
     if (e != hipSuccess) return sv_error(-static_cast<int>(e), "%s: hipMemsetAsync failed", what);
-    g_sv_err[0] = '\0';
+    g_sv_err.clear();
     return FEDAVG_OK;
   }
   // a host address would fault the kernel: spot check of the first and last
@@ -378,7 +373,7 @@ extern "C" {
 
 int fedavg_segvec_abi_version(void) { return 1; }
 
-const char* fedavg_segvec_last_error(void) { return g_sv_err; }
+const char* fedavg_segvec_last_error(void) { return g_sv_err.c_str(); }
 
 int64_t fedavg_device_round_vec_workspace(int64_t K, int64_t n_keys) {
   return fedavg_staging::round_vec_workspace_bytes(K, n_keys);

@@ -1,22 +1,15 @@
-"""libfedavg_amd_clientvec.so (include/fedavg_amd_clientvec.h): exports, kernel
-set, no scratch, argument validation and the span / workspace / partials
-arithmetic.
+"""libfedavg_amd_clientvec.so (include/fedavg_amd_clientvec.h): argument
+validation and the span / workspace / partials arithmetic (exports, kernel
+set and no scratch: test_native_libs.py).
 
 CPU only: sizes, tables and alignments are validated before any HIP call, and
 the span, workspace and partials functions are host arithmetic.
 """
-import importlib.util
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from mfl_amd import _lib, build
-from test_abi import _exported, declared_functions
 
-ROOT = Path(__file__).resolve().parents[1]
-HERE = Path(__file__).parent
-HEADER = ("fedavg_amd_clientvec.h",)
 STATS = ("fedavg_client_stats_bf16", "fedavg_client_stats_f16", "fedavg_client_stats_f64")
 TRACK = ("fedavg_client_track_bf16", "fedavg_client_track_f16", "fedavg_client_track_f64")
 ES = {"bf16": 2, "f16": 2, "f64": 8}
@@ -31,63 +24,6 @@ def es_of(entry):
 def lib():
     build.build()
     return _lib.load_clientvec()
-
-
-@pytest.fixture(scope="module")
-def inventory(lib):
-    spec = importlib.util.spec_from_file_location("kernel_inventory", ROOT / "scripts" / "kernel_inventory.py")
-    inv = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(inv)
-    if not inv.have_tools():
-        pytest.skip("llvm-objcopy / llvm-readelf not found")
-    return inv.inventory(build.CLIENTVEC_LIB_PATH)
-
-
-def test_exports_are_exactly_the_header(lib):
-    declared = declared_functions(HEADER)
-    assert declared == sorted(["fedavg_clientvec_abi_version", "fedavg_clientvec_last_error",
-                               "fedavg_client_stats_vec_span", "fedavg_client_stats_vec_workspace",
-                               "fedavg_client_stats_vec_partials", *STATS, *TRACK])
-    assert _exported(build.CLIENTVEC_LIB_PATH) == declared
-    assert sorted(_lib.CLIENTVEC_SIGNATURES) == declared
-    assert lib.fedavg_clientvec_abi_version() == _lib.CLIENTVEC_ABI_VERSION
-
-
-def test_no_overlap_with_the_other_headers(lib):
-    declared = set(declared_functions(HEADER))
-    for other in ("fedavg_amd.h", "fedavg_amd_tuning.h", "fedavg_amd_fusedvec.h", "fedavg_amd_segvec.h"):
-        assert not declared & set(declared_functions((other,))), other
-    assert not declared & (set(_lib.SIGNATURES) | set(_lib.TUNING_SIGNATURES) | set(_lib.FUSEDVEC_SIGNATURES) |
-                           set(_lib.SEGVEC_SIGNATURES))
-
-
-def test_gfx950_code_object_and_no_environment_variable(lib):
-    data = build.CLIENTVEC_LIB_PATH.read_bytes()
-    assert b"gfx950" in data
-    assert b"getenv" not in data
-
-
-def test_links_no_other_library_of_the_project(lib):
-    import subprocess
-
-    out = subprocess.run(["readelf", "-d", str(build.CLIENTVEC_LIB_PATH)], capture_output=True, text=True,
-                         check=True).stdout
-    assert "libfedavg_amd" not in "".join(ln for ln in out.splitlines() if "NEEDED" in ln)
-
-
-def test_kernel_set_is_the_listed_one_and_disjoint(inventory):
-    listed = (HERE / "clientvec_kernels.txt").read_text().splitlines()
-    built = sorted(inventory)
-    assert sorted(set(built) - set(listed)) == [], "kernels built but not listed"
-    assert sorted(set(listed) - set(built)) == [], "kernels listed but not built"
-    assert built == listed and len(built) == 10  # 3 dtypes x {first, later} passes, the finalize, 3 trackers
-    for other in ("product_kernels.txt", "fusedvec_kernels.txt", "segvec_kernels.txt"):
-        assert not set(listed) & set((HERE / other).read_text().splitlines()), other
-
-
-def test_no_instance_uses_scratch(inventory):
-    for name, row in inventory.items():
-        assert row["scratch"] == 0 and row["vgpr_spill"] == 0 and row["sgpr_spill"] == 0, (name, row)
 
 
 # ------------------------------------------------------------------ arithmetic

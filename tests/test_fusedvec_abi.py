@@ -1,19 +1,14 @@
-"""libfedavg_amd_fusedvec.so (include/fedavg_amd_fusedvec.h): exports, kernel
-set, no scratch, argument validation and the plan / workspace arithmetic.
+"""libfedavg_amd_fusedvec.so (include/fedavg_amd_fusedvec.h): argument validation
+and the plan / workspace arithmetic (exports, kernel set and no scratch:
+test_native_libs.py).
 
 CPU only: argument validation runs before any HIP call, and the plan and
 workspace functions are host arithmetic.
 """
-import importlib.util
-from pathlib import Path
-
 import pytest
 
 from mfl_amd import _lib, build
-from test_abi import ENV_PROBE_ONLY, ENV_REMOVED, _exported, declared_functions
 
-ROOT = Path(__file__).resolve().parents[1]
-HEADER = ("fedavg_amd_fusedvec.h",)
 # the fused ranges the header states
 FUSED_MAX_K = {8: 64, 2: 128}
 
@@ -22,53 +17,6 @@ FUSED_MAX_K = {8: 64, 2: 128}
 def lib():
     build.build()
     return _lib.load_fusedvec()
-
-
-@pytest.fixture(scope="module")
-def inventory(lib):
-    spec = importlib.util.spec_from_file_location("kernel_inventory", ROOT / "scripts" / "kernel_inventory.py")
-    inv = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(inv)
-    if not inv.have_tools():
-        pytest.skip("llvm-objcopy / llvm-readelf not found")
-    return inv.inventory(build.FUSEDVEC_LIB_PATH)
-
-
-def test_exports_are_exactly_the_header(lib):
-    declared = declared_functions(HEADER)
-    assert len(declared) == 7
-    assert _exported(build.FUSEDVEC_LIB_PATH) == declared
-    assert sorted(_lib.FUSEDVEC_SIGNATURES) == declared
-    assert not set(declared) & set(_lib.SIGNATURES)
-    assert lib.fedavg_fusedvec_abi_version() == _lib.FUSEDVEC_ABI_VERSION
-
-
-def test_gfx950_code_object_and_no_environment_variable(lib):
-    data = build.FUSEDVEC_LIB_PATH.read_bytes()
-    assert b"gfx950" in data
-    for name in ENV_REMOVED + ENV_PROBE_ONLY + (b"FEDAVG_FUSE_DISTANCES", b"FEDAVG_TUNING", b"getenv"):
-        assert name not in data, name
-
-
-def test_kernel_set_is_the_listed_one(inventory):
-    listed = (Path(__file__).with_name("fusedvec_kernels.txt")).read_text().splitlines()
-    built = sorted(inventory)
-    assert sorted(set(built) - set(listed)) == [], "kernels built but not listed"
-    assert sorted(set(listed) - set(built)) == [], "kernels listed but not built"
-    assert built == listed and len(built) == 14
-
-
-def test_no_instance_uses_scratch(inventory):
-    for name, row in inventory.items():
-        assert row["scratch"] == 0 and row["vgpr_spill"] == 0 and row["sgpr_spill"] == 0, (name, row)
-
-
-def test_product_library_kernel_set_is_untouched(lib):
-    """None of the new kernels went into libfedavg_amd.so (its pinned list:
-    tests/product_kernels.txt, checked by test_abi)."""
-    listed = set((Path(__file__).with_name("product_kernels.txt")).read_text().splitlines())
-    mine = set((Path(__file__).with_name("fusedvec_kernels.txt")).read_text().splitlines())
-    assert not listed & mine
 
 
 @pytest.mark.parametrize("entry", ["fedavg_reduce_sqdist_f64", "fedavg_reduce_sqdist_f16", "fedavg_reduce_sqdist_bf16"])

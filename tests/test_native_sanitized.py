@@ -21,6 +21,9 @@
   HIP-free plan header (``csrc/dist_plan.hpp``) against the plans recorded in
   ``tests/dist_plan_cases.txt``, its form tables, the workspace bounds and the
   distance pass's round-split cut.
+* ``tests/native/error_state_check.cpp`` (always): the HIP-free last-error
+  state every library keeps (``csrc/error_state.hpp``): truncation, the
+  setter's return value, ``clear()`` and one message per thread.
 * ``fedavg_collect_ext`` (the state_dict walk, ``verify_rows``) built with
   ``-fsanitize=address,undefined`` and the CPU suites that drive it run under
   ``LD_PRELOAD=libasan`` -- opt-in (``MFL_ASAN_TESTS=1``; it compiles a torch
@@ -106,6 +109,22 @@ def test_dist_plan_under_asan_ubsan(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([str(exe), str(ROOT / "tests" / "dist_plan_cases.txt")], capture_output=True, text=True,
                        timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert " 0 failures" in r.stdout and "ERROR" not in r.stderr, r.stdout + r.stderr
+
+
+@pytest.mark.skipif(_gxx() is None, reason="g++ not found")
+def test_error_state_under_asan_ubsan(tmp_path):
+    """csrc/error_state.hpp, the last-error state every library keeps: the
+    setter returns its code, a message longer than the buffer is cut and
+    NUL-terminated, clear() empties it, two threads hold independent messages
+    (tests/native/error_state_check.cpp)."""
+    exe = tmp_path / "error_state_check"
+    cmd = [_gxx(), "-std=c++17", "-O1", "-g", *SAN, f"-I{CSRC}",
+           str(ROOT / "tests" / "native" / "error_state_check.cpp"), "-pthread", "-o", str(exe)]
+    subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     assert " 0 failures" in r.stdout and "ERROR" not in r.stderr, r.stdout + r.stderr
 

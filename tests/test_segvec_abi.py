@@ -1,21 +1,15 @@
-"""libfedavg_amd_segvec.so (include/fedavg_amd_segvec.h): exports, kernel set,
-no scratch, argument validation and the plan / workspace arithmetic.
+"""libfedavg_amd_segvec.so (include/fedavg_amd_segvec.h): argument validation
+and the plan / workspace arithmetic (exports, kernel set and no scratch:
+test_native_libs.py).
 
 CPU only: sizes, tables and sources are validated before any HIP call, and
 the plan, workspace and partials functions are host arithmetic.
 """
-import ctypes
-import importlib.util
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 from mfl_amd import _lib, build
-from test_abi import _exported, declared_functions
 
-ROOT = Path(__file__).resolve().parents[1]
-HEADER = ("fedavg_amd_segvec.h",)
 ENTRIES = ("fedavg_device_round_f64", "fedavg_device_round_f16", "fedavg_device_round_bf16")
 ES = {"fedavg_device_round_f64": 8, "fedavg_device_round_f16": 2, "fedavg_device_round_bf16": 2}
 MAX_K = {8: 64, 2: 128}  # the one-wave bands the header states
@@ -25,56 +19,6 @@ MAX_K = {8: 64, 2: 128}  # the one-wave bands the header states
 def lib():
     build.build()
     return _lib.load_segvec()
-
-
-@pytest.fixture(scope="module")
-def inventory(lib):
-    spec = importlib.util.spec_from_file_location("kernel_inventory", ROOT / "scripts" / "kernel_inventory.py")
-    inv = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(inv)
-    if not inv.have_tools():
-        pytest.skip("llvm-objcopy / llvm-readelf not found")
-    return inv.inventory(build.SEGVEC_LIB_PATH)
-
-
-def test_exports_are_exactly_the_header(lib):
-    declared = declared_functions(HEADER)
-    assert declared == sorted(["fedavg_segvec_abi_version", "fedavg_segvec_last_error",
-                               "fedavg_device_round_vec_workspace", "fedavg_device_round_vec_partials",
-                               "fedavg_device_round_vec_plan_of", *ENTRIES])
-    assert _exported(build.SEGVEC_LIB_PATH) == declared
-    assert sorted(_lib.SEGVEC_SIGNATURES) == declared
-    assert not set(declared) & (set(_lib.SIGNATURES) | set(_lib.FUSEDVEC_SIGNATURES))
-    assert lib.fedavg_segvec_abi_version() == _lib.SEGVEC_ABI_VERSION
-
-
-def test_gfx950_code_object_and_no_environment_variable(lib):
-    data = build.SEGVEC_LIB_PATH.read_bytes()
-    assert b"gfx950" in data
-    assert b"getenv" not in data and b"FEDAVG_" not in data
-
-
-def test_links_no_other_library_of_the_project(lib):
-    import subprocess
-
-    out = subprocess.run(["readelf", "-d", str(build.SEGVEC_LIB_PATH)], capture_output=True, text=True, check=True).stdout
-    assert "libfedavg_amd" not in "".join(ln for ln in out.splitlines() if "NEEDED" in ln)
-
-
-def test_kernel_set_is_the_listed_one_and_disjoint(inventory):
-    here = Path(__file__).parent
-    listed = (here / "segvec_kernels.txt").read_text().splitlines()
-    built = sorted(inventory)
-    assert sorted(set(built) - set(listed)) == [], "kernels built but not listed"
-    assert sorted(set(listed) - set(built)) == [], "kernels listed but not built"
-    assert built == listed and len(built) == 14  # 5 + 5 + 3 window instances and the finalize
-    for other in ("product_kernels.txt", "fusedvec_kernels.txt"):
-        assert not set(listed) & set((here / other).read_text().splitlines()), other
-
-
-def test_no_instance_uses_scratch(inventory):
-    for name, row in inventory.items():
-        assert row["scratch"] == 0 and row["vgpr_spill"] == 0 and row["sgpr_spill"] == 0, (name, row)
 
 
 class _Round:
