@@ -1,4 +1,4 @@
-"""ctypes binding of the native libraries ``build.LIBS`` describes (the C ABI
+"""ctypes binding of the native libraries ``build.ALL_LIBS`` describes (the C ABI
 in include/*.h): a signature table each, one loader and one status check.
 
 There is no fallback: if a HIP library is missing or does not export the
@@ -11,7 +11,8 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import BY_KEY, CLIENTVEC_LIB_PATH, FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH, NativeLib
+from .build import (BY_KEY, CLIENTSTEP_LIB_PATH, CLIENTVEC_LIB_PATH, FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH,
+                    SEGVEC_LIB_PATH, NativeLib)
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -153,10 +154,25 @@ CLIENTVEC_SIGNATURES = {
     "fedavg_client_track_f64": _CLIENTVEC_TRACK,
 }
 
+# libfedavg_amd_clientstep.so (include/fedavg_amd_clientstep.h)
+_CLIENTSTEP_STEP = (_c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_double, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp])
+CLIENTSTEP_SIGNATURES = {
+    "fedavg_clientstep_abi_version": (_c_int, []),
+    "fedavg_clientstep_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_step_span": (_c_i64, [_c_i64]),
+    "fedavg_client_step_workspace": (_c_i64, [_c_i64]),
+    "fedavg_client_step_partials": (_c_i64, [_vp, _c_i64, _c_i64]),
+    "fedavg_client_sgd_step_f32": _CLIENTSTEP_STEP,
+    "fedavg_client_sgd_step_bf16": _CLIENTSTEP_STEP,
+    "fedavg_client_sgd_step_f16": _CLIENTSTEP_STEP,
+    "fedavg_client_sgd_step_f64": _CLIENTSTEP_STEP,
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
 CLIENTVEC_ABI_VERSION = BY_KEY["clientvec"].abi[1]
+CLIENTSTEP_ABI_VERSION = BY_KEY["clientstep"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -182,6 +198,7 @@ _BINDING = {
     "fusedvec": ((FUSEDVEC_SIGNATURES,), "FUSEDVEC_LIB_PATH", "_fusedvec"),
     "segvec": ((SEGVEC_SIGNATURES,), "SEGVEC_LIB_PATH", "_segvec"),
     "clientvec": ((CLIENTVEC_SIGNATURES,), "CLIENTVEC_LIB_PATH", "_clientvec"),
+    "clientstep": ((CLIENTSTEP_SIGNATURES,), "CLIENTSTEP_LIB_PATH", "_clientstep"),
 }
 
 _lock = threading.Lock()
@@ -190,6 +207,7 @@ _probe = None
 _fusedvec = None
 _segvec = None
 _clientvec = None
+_clientstep = None
 
 
 def library_path() -> Path:
@@ -267,9 +285,15 @@ def load_clientvec() -> ctypes.CDLL:
     return _clientvec if _clientvec is not None else _load(BY_KEY["clientvec"])
 
 
+def load_clientstep() -> ctypes.CDLL:
+    """The fused client SGD step library for fp32 / bf16 / fp16 / fp64 models (include/fedavg_amd_clientstep.h)."""
+    return _clientstep if _clientstep is not None else _load(BY_KEY["clientstep"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
+check_clientstep = functools.partial(_check, BY_KEY["clientstep"])
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

@@ -29,6 +29,16 @@ expressions on whatever device the parameters are on; it is what CPU
 parameters, models of mixed dtypes and any other dtype get under
 ``stats="auto"``.
 
+``step="fused"`` (opt in; the default ``"torch"`` is ``optimizer.step()`` and
+the weight pass above) replaces the plain SGD step of :74 and the weight pass
+by ONE kernel (``libfedavg_amd_clientstep.so``, ``fedavg_client_sgd_step_*``):
+it reads ``w`` and ``g``, writes ``w' = w - lr * g`` and sums ``w'^2`` and
+``rT(w' - w)^2`` on the way, since ``last_w`` of :78 is always the weight the
+step started from.  No weight snapshot is read or written: 12 B per fp32
+element instead of 24.  The bits it leaves must be torch's, and whether ATen's
+kernel fuses the multiply and the add is a property of the torch build:
+:func:`sgd_form` finds out on the GPU, once per (device, dtype).
+
 :func:`client_train` is ``Client.train`` written against this class and
 :func:`patch` binds it to a ``Client`` class (opt in; ``install()`` does not).
 """
@@ -95,6 +105,141 @@ def _guard_bound(n_w, lr_ratio, dtype):
         return _round_to(np.float64(n_w) * np.float64(np.float32(lr_ratio)), dtype)
 
 
+# ------------------------------------------------------------------ fused step
+# The dtypes the fused step is offered for: those sgd_form() found a form for on the MI355X (torch 2.10 / ROCm 7.0:
+# form 1 for fp32, bf16 and fp64).  Not fp16: there torch's kernel rounds fma(alpha, g, w) ONCE, to fp16 (a
+# mixed-precision fma), while both forms round to fp32 first; on sgd_form's probe form 1 differs from torch on 2 of
+# 571 elements, form 0 on 61.  fedavg_client_sgd_step_f16 stays in the C ABI; nothing here calls it.
+STEP_DTYPES = (torch.float32, torch.bfloat16, torch.float64)
+_STEP_SUFFIX = {torch.float32: "f32", **_VEC_DTYPES}
+_STEP_RULE = (f"the fused statistics ({_RULE}), fp32, bf16 or fp64 parameters, a plain SGD step (client_optimizer "
+              "'sgd': no momentum, no weight decay) and a form of the step kernel that leaves torch.optim.SGD's bits "
+              "on this GPU (sgd_form)")
+_BITS = {2: torch.int16, 4: torch.int32, 8: torch.int64}
+_PROBE_LR = 0.03
+_PROBE_N = 512
+_PROBE_POOL = 1 << 21
+_probes = {}  # (device index, dtype) -> the probe's findings
+
+
+class _StepPass:
+    """The buffers of ``fedavg_client_sgd_step_*`` calls over tensors of
+    ``numel`` elements, and the call.  The pinned key table is reused under
+    ``ClientStepStats._pass``'s rule: new bytes only after the stream has
+    passed the last call that shipped the old ones."""
+
+    def __init__(self, numel, dtype, device):
+        self.lib = _lib.load_clientstep()
+        self.name = f"fedavg_client_sgd_step_{_STEP_SUFFIX[dtype]}"
+        self.fn = getattr(self.lib, self.name)
+        self.device = device
+        self.numel = np.ascontiguousarray(numel, dtype=np.int64)
+        n = len(self.numel)
+        es = torch.empty(0, dtype=dtype).element_size()
+        nparts = int(self.lib.fedavg_client_step_partials(self.numel.ctypes.data, n, es))
+        ws = int(self.lib.fedavg_client_step_workspace(n))
+        with torch.cuda.device(device):
+            self.partials = torch.empty(max(nparts, 1), dtype=torch.float64, device=device)
+            self.host_ws = torch.empty(max(ws, 16), dtype=torch.uint8, pin_memory=True)
+            self.dev_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=device)
+        self._free = None    # event: the stream has passed the last use of host_ws
+        self._staged = None  # the pointer tables host_ws holds
+
+    def launch(self, w_ptrs, g_ptrs, lr, form, stats_ptr, st):
+        """w -= lr * g over the tensors at w_ptrs / g_ptrs on torch stream
+        ``st``; the record goes to the 4 device doubles at ``stats_ptr``."""
+        table = w_ptrs.tobytes() + g_ptrs.tobytes()
+        if self._free is not None and table != self._staged:
+            self._free.synchronize()  # host_ws gets new bytes below (already passed after an iteration's sync)
+        self._staged = table
+        with torch.cuda.device(self.device):
+            rc = self.fn(w_ptrs.ctypes.data, g_ptrs.ctypes.data, self.numel.ctypes.data, len(self.numel), float(lr),
+                         form, self.partials.data_ptr(), self.partials.numel(), stats_ptr, self.host_ws.data_ptr(),
+                         self.dev_ws.data_ptr(), self.host_ws.numel(), st.cuda_stream)
+            _lib.check_clientstep(rc, self.name)
+            if self._free is None:
+                self._free = torch.cuda.Event()
+            self._free.record(st)
+
+
+def _probe_values(dtype):
+    """Seeded model-like weights N(0, 0.05^2) and gradients N(0, 1) of type
+    ``dtype`` for the probe.  In fp32 and fp64 the two forms differ on about
+    every third random element.  In a 16-bit type they differ only where the
+    fp32 results lie on either side of a rounding boundary of the type (one
+    element in tens of thousands), so the first _PROBE_N values of a larger
+    seeded pool are joined by those of its elements at which a host
+    computation of the two forms differs; whether they differ on the device
+    is sgd_form's own check."""
+    wide = dtype in (torch.float32, torch.float64)
+    rng = np.random.default_rng(20250)
+    n = _PROBE_N if wide else _PROBE_POOL
+    w = torch.from_numpy(rng.normal(0.0, 0.05, n)).to(dtype)
+    g = torch.from_numpy(rng.normal(0.0, 1.0, n)).to(dtype)
+    if wide:
+        return w, g
+    wf, gf = w.float().numpy(), g.float().numpy()
+    alpha = np.float32(-_PROBE_LR)
+    with np.errstate(all="ignore"):
+        apart = torch.from_numpy(wf + alpha * gf).to(dtype)  # two fp32 roundings, then the type's
+        once = torch.from_numpy((wf.astype(np.float64) + np.float64(alpha) * gf.astype(np.float64))
+                                .astype(np.float32)).to(dtype)  # the product is exact in fp64
+    picked = torch.nonzero(apart.view(torch.int16) != once.view(torch.int16)).view(-1).numpy()[:_PROBE_N]
+    idx = torch.from_numpy(np.union1d(np.arange(_PROBE_N), picked))
+    return w[idx].clone(), g[idx].clone()
+
+
+def _probe_sgd_form(device, dtype):
+    w, g = _probe_values(dtype)
+    bits = _BITS[w.element_size()]
+    with torch.cuda.device(device):
+        w, g = w.to(device), g.to(device)
+        p = torch.nn.Parameter(w.clone())
+        p.grad = g.clone()
+        torch.optim.SGD([p], lr=_PROBE_LR).step()
+        want = p.detach().view(bits)
+        step = _StepPass([w.numel()], dtype, device)
+        rec = torch.empty(4, dtype=torch.float64, device=device)
+        st = torch.cuda.current_stream(device)
+        got = []
+        for form in (0, 1):
+            c = w.clone()
+            step.launch(np.array([c.data_ptr()], dtype=np.int64), np.array([g.data_ptr()], dtype=np.int64),
+                        _PROBE_LR, form, rec.data_ptr(), st)
+            got.append(c.view(bits))
+        differ = int((got[0] != got[1]).sum())
+        match = tuple(bool(torch.equal(c, want)) for c in got)
+    form = None
+    if differ:  # equal outputs would say nothing about which one torch computes
+        form = 0 if match[0] else 1 if match[1] else None
+    return {"form": form, "differ": differ, "match": match, "n": int(w.numel())}
+
+
+def sgd_form_probe(device, dtype):
+    """What :func:`sgd_form` found for (device, dtype), cached: ``form``, the
+    number of probe elements on which the kernel's two forms ``differ``,
+    ``match`` (form 0 / form 1 equal to torch on every element) and ``n``."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TypeError(f"sgd_form needs a GPU, not {device}")
+    index = torch.cuda.current_device() if device.index is None else device.index
+    key = (index, dtype)
+    if key not in _probes:
+        _probes[key] = _probe_sgd_form(torch.device("cuda", index), dtype)
+    return _probes[key]
+
+
+def sgd_form(device, dtype):
+    """Which form of ``fedavg_client_sgd_step_*`` leaves the bits of
+    ``torch.optim.SGD(params, lr=lr).step()`` on this GPU: 1 (``fma(-lr, g,
+    w)``), 0 (product and sum rounded separately) or ``None`` (neither, or no
+    kernel for the dtype).  Found by running torch's own step and both forms
+    on the same seeded values, once per (device, dtype)."""
+    if dtype not in STEP_DTYPES:
+        return None
+    return sgd_form_probe(device, dtype)["form"]
+
+
 class ClientStepStats:
     """Snapshots, key tables, workspaces and the running rho / beta of one
     ``Client.train`` call.
@@ -104,12 +249,20 @@ class ClientStepStats:
     trips) and ``after_step()`` (:76-86, no sync); ``result()`` at the end.
     ``trace(stage, w, g, loss)`` receives clones of the flattened weights and
     gradients at every call (``g`` is ``None`` where there is none yet).
+
+    ``step="fused"``: ``sgd_step()`` takes the place of the caller's
+    ``optimizer.step()`` and of ``after_step()`` (one kernel, no sync); it
+    needs the fused statistics and a form from :func:`sgd_form`, else
+    ``TypeError``.  ``step="auto"`` falls back to ``"torch"`` instead;
+    ``step_mode`` says which of the two the object was built for.
     """
 
-    def __init__(self, params, *, stream=None, stats="auto", trace=None):
+    def __init__(self, params, *, stream=None, stats="auto", trace=None, step="torch"):
         self.params = list(params)
         if stats not in ("auto", "hip", "torch"):
             raise ValueError(f"stats must be 'auto', 'hip' or 'torch', not {stats!r}")
+        if step not in ("torch", "fused", "auto"):
+            raise ValueError(f"step must be 'torch', 'fused' or 'auto', not {step!r}")
         fused = _fused_ok(self.params)
         if stats == "hip" and not fused:
             raise TypeError(f"stats='hip' needs {_RULE}")
@@ -124,6 +277,14 @@ class ClientStepStats:
         else:
             self._last_w = self._last_grads = self._grads = None
             self._rho = self._beta = None
+        self.step_mode = "torch"
+        if step != "torch":
+            self._form = sgd_form(self.device, self.dtype) if self.mode == "hip" else None
+            if self._form is not None:
+                self.step_mode = "fused"
+                self._step = _StepPass(self._numel, self.dtype, self.device)
+            elif step == "fused":
+                raise TypeError(f"step='fused' needs {_STEP_RULE}")
 
     # ------------------------------------------------------------------ fused
     def _init_hip(self):
@@ -273,6 +434,9 @@ class ClientStepStats:
         """client.py:76-86 after ``optimizer.step()``: the weight pass and the
         running rho / beta; ``loss`` and ``last_loss`` are the Python floats of
         :75 and :56 / :86."""
+        if self.step_mode == "fused":
+            raise RuntimeError("after_step() on an object built for fused stepping: sgd_step() takes the step and "
+                               "keeps no weight snapshot for this pass to compare with")
         if self.mode == "hip":
             self._pass("w", 1)
             base = self._rec.data_ptr()
@@ -292,6 +456,25 @@ class ClientStepStats:
                 self._last_w, self._last_grads = w, self._grads
         self._emit("after_step", loss)
 
+    def sgd_step(self, lr, loss, last_loss):
+        """client.py:74-86 in one kernel, in place of ``optimizer.step()`` and
+        ``after_step()``: ``w -= lr * g`` with torch.optim.SGD's bits, the
+        weight record (``sum w'^2`` for the next guard, ``sum rT(w' - w)^2``
+        for :78 / :82) and the running rho / beta.  No host sync."""
+        if self.step_mode != "fused":
+            raise RuntimeError("sgd_step() needs an object built with step='fused' (or 'auto' where it applies): "
+                               f"this one steps with torch ({self.step_mode=})")
+        if not self._begun:
+            raise RuntimeError("begin() first")
+        st = self._torch_stream()
+        base = self._rec.data_ptr()
+        self._step.launch(self._ptrs["w"], self._grad_ptrs(), lr, self._form, base + 8 * _W, st)
+        torch.autograd.graph.increment_version(self.params)  # the in-place update autograd did not see
+        with torch.cuda.device(self.device):
+            rc = self._track_fn(base + 8 * _STATE, base + 8 * _W, base + 8 * _G, abs(loss - last_loss), st.cuda_stream)
+        self._check(rc, self._track_name)
+        self._emit("after_step", loss)
+
     def result(self):
         """``(beta, rho)`` as Python floats (``None`` where no step was taken)."""
         if self.mode == "hip":
@@ -303,7 +486,7 @@ class ClientStepStats:
                 None if self._rho is None else self._rho.item())
 
 
-def client_train(self, net, local_iteration, *, keep_on_device=False, stats="auto", trace=None):
+def client_train(self, net, local_iteration, *, keep_on_device=False, stats="auto", trace=None, step="torch"):
     """``Client.train(self, net, local_iteration)`` (client.py:38-96) with the
     bookkeeping of :52-86 done by :class:`ClientStepStats`.
 
@@ -312,19 +495,28 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
     ``THRESHOLD_GRADS_RATIO`` are the ones of the module that defines
     ``type(self)`` (the reference's ``client`` module).  ``keep_on_device``
     returns ``net.state_dict()`` without the ``.cpu()`` of :73 / :96.
+    ``step`` is :class:`ClientStepStats`'s: with fused stepping and
+    ``args.client_optimizer == "sgd"`` one ``sgd_step(args.lr, ...)`` replaces
+    ``optimizer.step()`` and ``after_step()``; Adam is a ``TypeError`` under
+    ``"fused"`` and steps with torch under ``"auto"``.
     """
     mod = sys.modules[type(self).__module__]
     count, count_end, ratio = mod.count, mod.count_end, mod.THRESHOLD_GRADS_RATIO
-    if self.args.client_optimizer == "sgd":
+    sgd = self.args.client_optimizer == "sgd"
+    if sgd:
         optimizer = torch.optim.SGD(net.parameters(), lr=self.args.lr)
     else:
+        if step == "fused":
+            raise TypeError(f"step='fused' needs {_STEP_RULE}; args.client_optimizer is "
+                            f"{self.args.client_optimizer!r}")
         optimizer = torch.optim.Adam(filter(lambda p: p.requires_grad, net.parameters()), lr=self.args.lr,
                                      weight_decay=self.args.wd, amsgrad=True)
     cycles = []
     x, labels = next(iter(self.local_training_data))
     x, labels = x.to(self.device), labels.to(self.device)
     net.train()
-    tracker = ClientStepStats(net.parameters(), stats=stats, trace=trace)
+    tracker = ClientStepStats(net.parameters(), stats=stats, trace=trace, step=step if sgd else "torch")
+    fused = tracker.step_mode == "fused"
     last_loss = self.criterion(net(x), labels)
     torch.nn.utils.clip_grad_norm_(net.parameters(), self.args.clip)
     last_loss.backward()
@@ -344,9 +536,12 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
             if logger is not None:
                 logger.warning("grads too large than weights or meets nan with epoch {}".format(epoch))
             return done(), None, None, None, None, None
-        optimizer.step()
         loss = tracker.loss
-        tracker.after_step(loss, last_loss)
+        if fused:
+            tracker.sgd_step(self.args.lr, loss, last_loss)
+        else:
+            optimizer.step()
+            tracker.after_step(loss, last_loss)
         last_loss = loss
     # local_iteration == 0 leaves log_probs unbound, as in the reference (:93)
     _, predicted = torch.max(log_probs, -1)
@@ -377,14 +572,14 @@ class _Patch:
         return False
 
 
-def patch(cls, *, keep_on_device=False, stats="auto"):
+def patch(cls, *, keep_on_device=False, stats="auto", step="torch"):
     """Replace ``cls.train`` (the reference's ``Client.train``) with
     :func:`client_train`; returns a handle whose ``undo()`` restores the class."""
     had = "train" in vars(cls)
     old = vars(cls).get("train")
 
     def train(self, net, local_iteration):
-        return client_train(self, net, local_iteration, keep_on_device=keep_on_device, stats=stats)
+        return client_train(self, net, local_iteration, keep_on_device=keep_on_device, stats=stats, step=step)
 
     train.__wrapped_by__ = "mfl_amd.client_stats"
     setattr(cls, "train", train)
