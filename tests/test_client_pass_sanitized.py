@@ -1,10 +1,13 @@
-"""The fused client SGD step's HIP-free plan header (``csrc/client_step_plan.hpp``)
+"""The client passes' HIP-free plan header (``csrc/client_pass_plan.hpp``: the
+fp32 statistics, the bf16 / fp16 / fp64 statistics and the fused SGD step)
 under AddressSanitizer + UndefinedBehaviorSanitizer (no GPU), built as
 tests/test_native_sanitized.py builds its programs: g++ compiles
-``tests/native/client_step_check.cpp``, a stand-alone program, with
+``tests/native/client_pass_check.cpp``, a stand-alone program, with
 ``-fsanitize=address,undefined``; it fuzzes key counts 1..5,000, empty keys
 and numels around the unit edges, fills tables in buffers of exactly the
-reserved bytes and checks every written byte and every ``unit_start``.
+reserved bytes for both table entries and element sizes 2, 4 and 8, checks
+every written byte and every ``unit_start``, and that each key-list check
+refuses exactly the constructed bad key.
 """
 import os
 import shutil
@@ -23,10 +26,10 @@ def _gxx():
 
 
 @pytest.mark.skipif(_gxx() is None, reason="g++ not found")
-def test_client_step_plan_under_asan_ubsan(tmp_path):
-    exe = tmp_path / "client_step_check"
+def test_client_pass_plan_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "client_pass_check"
     cmd = [_gxx(), "-std=c++17", "-O1", "-g", *SAN, f"-I{CSRC}",
-           str(ROOT / "tests" / "native" / "client_step_check.cpp"), "-o", str(exe)]
+           str(ROOT / "tests" / "native" / "client_pass_check.cpp"), "-o", str(exe)]
     subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     for seed in (1234, 99):
