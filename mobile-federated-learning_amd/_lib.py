@@ -1,4 +1,4 @@
-"""ctypes binding of the native libraries ``build.ALL_LIBS`` describes (the C ABI
+"""ctypes binding of the native libraries ``build.EVERY_LIB`` describes (the C ABI
 in include/*.h): a signature table each, one loader and one status check.
 
 There is no fallback: if a HIP library is missing or does not export the
@@ -11,8 +11,8 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import (BY_KEY, CLIENTSTEP_LIB_PATH, CLIENTVEC_LIB_PATH, FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH,
-                    SEGVEC_LIB_PATH, NativeLib)
+from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTVEC_LIB_PATH, DESCRIBED, FUSEDVEC_LIB_PATH,
+                    LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH, NativeLib)
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -168,11 +168,27 @@ CLIENTSTEP_SIGNATURES = {
     "fedavg_client_sgd_step_f64": _CLIENTSTEP_STEP,
 }
 
+# libfedavg_amd_clientadam.so (include/fedavg_amd_clientadam.h)
+_CLIENTADAM_STEP = (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_int, _c_int, _vp, _c_i64, _vp, _vp, _vp,
+                             _c_i64, _vp])
+CLIENTADAM_SIGNATURES = {
+    "fedavg_clientadam_abi_version": (_c_int, []),
+    "fedavg_clientadam_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_adam_span": (_c_i64, [_c_i64]),
+    "fedavg_client_adam_workspace": (_c_i64, [_c_i64]),
+    "fedavg_client_adam_partials": (_c_i64, [_vp, _c_i64, _c_i64]),
+    "fedavg_client_adam_step_f32": _CLIENTADAM_STEP,
+    "fedavg_client_adam_step_bf16": _CLIENTADAM_STEP,
+    "fedavg_client_adam_step_f16": _CLIENTADAM_STEP,
+    "fedavg_client_adam_step_f64": _CLIENTADAM_STEP,
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
 CLIENTVEC_ABI_VERSION = BY_KEY["clientvec"].abi[1]
 CLIENTSTEP_ABI_VERSION = BY_KEY["clientstep"].abi[1]
+CLIENTADAM_ABI_VERSION = DESCRIBED["clientadam"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -199,6 +215,7 @@ _BINDING = {
     "segvec": ((SEGVEC_SIGNATURES,), "SEGVEC_LIB_PATH", "_segvec"),
     "clientvec": ((CLIENTVEC_SIGNATURES,), "CLIENTVEC_LIB_PATH", "_clientvec"),
     "clientstep": ((CLIENTSTEP_SIGNATURES,), "CLIENTSTEP_LIB_PATH", "_clientstep"),
+    "clientadam": ((CLIENTADAM_SIGNATURES,), "CLIENTADAM_LIB_PATH", "_clientadam"),
 }
 
 _lock = threading.Lock()
@@ -208,6 +225,7 @@ _fusedvec = None
 _segvec = None
 _clientvec = None
 _clientstep = None
+_clientadam = None
 
 
 def library_path() -> Path:
@@ -222,7 +240,7 @@ def _load(d: NativeLib) -> ctypes.CDLL:
     if g[slot] is not None:
         return g[slot]
     if d.needs:
-        _load(BY_KEY[d.needs])
+        _load(DESCRIBED[d.needs])
     with _lock:
         if g[slot] is not None:
             return g[slot]
@@ -290,10 +308,20 @@ def load_clientstep() -> ctypes.CDLL:
     return _clientstep if _clientstep is not None else _load(BY_KEY["clientstep"])
 
 
+def load_clientadam() -> ctypes.CDLL:
+    """The fused client Adam step library for fp32 / bf16 / fp16 / fp64 models (include/fedavg_amd_clientadam.h)."""
+    return _clientadam if _clientadam is not None else _load(DESCRIBED["clientadam"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
 check_clientstep = functools.partial(_check, BY_KEY["clientstep"])
+
+
+def check_clientadam(rc: int, what: str) -> None:
+    """``_check`` for the Adam step library (its description read at call time, as the loaders read theirs)."""
+    _check(DESCRIBED["clientadam"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

@@ -3,11 +3,14 @@
     python -m mfl_amd.build           # or __graft_entry__.build()
 
 ``LIBS`` is the five libraries tests/test_native_libs.py pins by name, with
-``up_to_date()`` over exactly those; a library added since is described with
-the same dataclass in ``LATER_LIBS``, and ``ALL_LIBS = LIBS + LATER_LIBS`` is
-what ``BY_KEY``, ``sources()`` and ``build()`` cover.
+``up_to_date()`` over exactly those.  ``LATER_LIBS`` is the sixth and
+``ALL_LIBS = LIBS + LATER_LIBS`` / ``BY_KEY`` the six, pinned in turn by
+tests/test_clientstep_abi.py.  A library added since is described with the
+same dataclass in ``NEWER_LIBS`` (a new one goes there), and ``EVERY_LIB =
+ALL_LIBS + NEWER_LIBS`` / ``DESCRIBED`` (by key) is what ``sources()``, the
+up-to-date rule and ``build()`` cover and what ``_lib`` loads from.
 
-Every translation unit of ``ALL_LIBS`` is compiled in parallel with hipcc for
+Every translation unit of ``EVERY_LIB`` is compiled in parallel with hipcc for
 ``--offload-arch=gfx950`` and each library is linked into ``lib/`` inside the
 package (in-tree, so the built libraries travel with the repo snapshot to the
 GPU box).  ``-ffp-contract=off`` keeps every multiply and add separately
@@ -96,7 +99,7 @@ LIBS = (
               abi=("fedavg_clientvec_abi_version", 1), last_error="fedavg_clientvec_last_error",
               no_fallback="; there is no fallback for the fused client statistics of bf16 / fp16 / fp64 models"),
 )
-# libraries added after the five above (a new one goes here: see the module docstring)
+# the library added after the five above
 LATER_LIBS = (
     # the client's plain SGD step fused with the weight statistics, fp32 / bf16 / fp16 / fp64; calls no other library
     NativeLib("clientstep", "libfedavg_amd_clientstep.so", "fedavg_amd_clientstep.h", ("fedavg_client_step.hip",),
@@ -105,8 +108,19 @@ LATER_LIBS = (
 )
 ALL_LIBS = LIBS + LATER_LIBS
 BY_KEY = {lib.key: lib for lib in ALL_LIBS}
+# libraries added after those six (a new one goes here: see the module docstring)
+NEWER_LIBS = (
+    # the client's Adam step (amsgrad) fused with the weight statistics, fp32 / bf16 / fp16 / fp64; calls no other
+    # library
+    NativeLib("clientadam", "libfedavg_amd_clientadam.so", "fedavg_amd_clientadam.h", ("fedavg_client_adam.hip",),
+              abi=("fedavg_clientadam_abi_version", 1), last_error="fedavg_clientadam_last_error",
+              no_fallback="; there is no fallback for the fused client Adam step"),
+)
+EVERY_LIB = ALL_LIBS + NEWER_LIBS
+DESCRIBED = {lib.key: lib for lib in EVERY_LIB}
 LIB_PATH, PROBE_LIB_PATH, FUSEDVEC_LIB_PATH, SEGVEC_LIB_PATH, CLIENTVEC_LIB_PATH = (lib.path for lib in LIBS)
 CLIENTSTEP_LIB_PATH = BY_KEY["clientstep"].path
+CLIENTADAM_LIB_PATH = DESCRIBED["clientadam"].path
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",
@@ -134,7 +148,7 @@ def hipcc_path() -> str:
 def sources():
     """Everything a library can depend on: every translation unit, every
     header in csrc/ and include/ (found, not listed) and this recipe."""
-    units = dict.fromkeys(src for lib in ALL_LIBS for src in lib.sources)
+    units = dict.fromkeys(src for lib in EVERY_LIB for src in lib.sources)
     return [*units, *sorted(CSRC_DIR.glob("*.hpp")), *sorted(INCLUDE.glob("*.h")), Path(__file__)]
 
 
@@ -144,9 +158,9 @@ def up_to_date() -> bool:
 
 
 def later_up_to_date() -> bool:
-    """The same rule for ``LATER_LIBS``: each built and no older than the newest source."""
+    """The same rule for ``LATER_LIBS`` and ``NEWER_LIBS``: each built and no older than the newest source."""
     newest = max(p.stat().st_mtime for p in sources())
-    return all(lib.path.exists() and lib.path.stat().st_mtime >= newest for lib in LATER_LIBS)
+    return all(lib.path.exists() and lib.path.stat().st_mtime >= newest for lib in LATER_LIBS + NEWER_LIBS)
 
 
 def collect_ext_path() -> Path:
@@ -201,14 +215,14 @@ def _link(objs, lib_path, verbose, extra=()):
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Build every library of ``ALL_LIBS``; returns the product library's path."""
+    """Build every library of ``EVERY_LIB``; returns the product library's path."""
     if not force and up_to_date() and later_up_to_date():
         return LIB_PATH
-    for lib in ALL_LIBS:
+    for lib in EVERY_LIB:
         (LIB_DIR / lib.obj_dir).mkdir(parents=True, exist_ok=True)
-    _compile_all([(CSRC_DIR / u, lib.obj(u), list(lib.defines)) for lib in ALL_LIBS for u in lib.units], verbose)
-    for lib in ALL_LIBS:  # in order: a library links after the one its link arguments name
-        objs = [lib.obj(u) for u in lib.units] + [BY_KEY[key].obj(u) for key, u in lib.reuse]
+    _compile_all([(CSRC_DIR / u, lib.obj(u), list(lib.defines)) for lib in EVERY_LIB for u in lib.units], verbose)
+    for lib in EVERY_LIB:  # in order: a library links after the one its link arguments name
+        objs = [lib.obj(u) for u in lib.units] + [DESCRIBED[key].obj(u) for key, u in lib.reuse]
         _link(objs, lib.path, verbose, extra=lib.link)
     return LIB_PATH
 

@@ -39,6 +39,14 @@ element instead of 24.  The bits it leaves must be torch's, and whether ATen's
 kernel fuses the multiply and the add is a property of the torch build:
 :func:`sgd_form` finds out on the GPU, once per (device, dtype).
 
+``optimizer="adam"`` with fused stepping does the same for the reference's
+default optimizer, ``torch.optim.Adam(lr, weight_decay=wd, amsgrad=True)``
+(``libfedavg_amd_clientadam.so``, ``fedavg_client_adam_step_*``): one kernel
+reads ``w``, ``g`` and the state ``m, v, vmax`` and writes ``w, m, v, vmax``
+where torch's multi-tensor Adam makes nine launches.  Four of its operations
+have the shape ``x + s * y``; which of them torch's kernels fuse is found by
+:func:`adam_form`, once per (device, dtype).
+
 :func:`client_train` is ``Client.train`` written against this class and
 :func:`patch` binds it to a ``Client`` class (opt in; ``install()`` does not).
 """
@@ -240,6 +248,239 @@ def sgd_form(device, dtype):
     return sgd_form_probe(device, dtype)["form"]
 
 
+# ------------------------------------------------------------------ fused Adam step
+# The dtypes the fused Adam step is offered for: those adam_form() found a mask for on the MI355X (torch 2.10 /
+# ROCm 7.0: mask 15, all four sites one fma, for fp32, bf16, fp16 and fp64).
+ADAM_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
+ADAM_SITES = 4  # A g + wd w, B the lerp, C the addcmul, E the addcdiv: bit i of a form mask fuses site i
+_ADAM_RULE = (f"the fused statistics ({_RULE}), a dtype adam_form() has a mask for, torch.optim.Adam with amsgrad=True "
+              "and beta1 > 0.5 over parameters that all require grad, and a form of the Adam step kernel that leaves "
+              "torch.optim.Adam's bits on this GPU (adam_form)")
+# The form is a property of torch's compiled kernels, not of the hyperparameters, so the probe picks hyperparameters
+# and values at which both terms of every site are of one magnitude (w, g ~ N(0, 1)): there two forms of a site leave
+# different fp32 bits on about every third element.  At the reference's own (wd = 0.001 against g ~ 1) they hardly
+# ever do.
+_ADAM_PROBE = dict(lr=0.3, betas=(0.6, 0.7), eps=1e-8, weight_decay=0.3)
+_ADAM_PROBE_STEPS = 3
+_adam_probes = {}  # (device index, dtype) -> the probe's findings
+
+
+def adam_coef(lr, beta1, beta2, eps, weight_decay, t):
+    """The seven coefficients of ``fedavg_client_adam_step_*`` for step ``t``
+    (from 1), in Python floats exactly as torch/optim/adam.py forms them."""
+    t = float(t)
+    bias_correction1 = 1 - beta1 ** t
+    bias_correction2 = 1 - beta2 ** t
+    step_size = (lr / bias_correction1) * -1
+    return np.array([weight_decay, 1 - beta1, beta2, 1 - beta2, bias_correction2 ** 0.5, eps, step_size],
+                    dtype=np.float64)
+
+
+class _AdamPass:
+    """The optimizer state (three planes ``m, v, vmax`` of ``state_elems``
+    elements in one zeroed buffer, key j at ``offset[j]``), the buffers of
+    ``fedavg_client_adam_step_*`` calls and the call.  The pinned key table is
+    reused under ``_StepPass``'s rule."""
+
+    def __init__(self, numel, offset, state_elems, dtype, device):
+        self.lib = _lib.load_clientadam()
+        self.name = f"fedavg_client_adam_step_{_STEP_SUFFIX[dtype]}"
+        self.fn = getattr(self.lib, self.name)
+        self.device = device
+        self.numel = np.ascontiguousarray(numel, dtype=np.int64)
+        self.offset = np.ascontiguousarray(offset, dtype=np.int64)
+        n = len(self.numel)
+        es = torch.empty(0, dtype=dtype).element_size()
+        self.state_elems = int(state_elems)
+        nparts = int(self.lib.fedavg_client_adam_partials(self.numel.ctypes.data, n, es))
+        ws = int(self.lib.fedavg_client_adam_workspace(n))
+        with torch.cuda.device(device):
+            self.state = torch.zeros(3 * max(self.state_elems, 16 // es), dtype=dtype, device=device)
+            self.partials = torch.empty(max(nparts, 1), dtype=torch.float64, device=device)
+            self.host_ws = torch.empty(max(ws, 16), dtype=torch.uint8, pin_memory=True)
+            self.dev_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=device)
+        self._free = None    # event: the stream has passed the last use of host_ws
+        self._staged = None  # the pointer tables host_ws holds
+
+    def plane(self, i):
+        """Plane i (0 ``m``, 1 ``v``, 2 ``vmax``) as a view of the state."""
+        return self.state[i * self.state_elems:(i + 1) * self.state_elems]
+
+    def launch(self, w_ptrs, g_ptrs, coef, first, form, stats_ptr, st):
+        table = w_ptrs.tobytes() + g_ptrs.tobytes()
+        if self._free is not None and table != self._staged:
+            self._free.synchronize()  # host_ws gets new bytes below (already passed after an iteration's sync)
+        self._staged = table
+        with torch.cuda.device(self.device):
+            rc = self.fn(w_ptrs.ctypes.data, g_ptrs.ctypes.data, self.numel.ctypes.data, self.offset.ctypes.data,
+                         len(self.numel), self.state.data_ptr(), self.state_elems, coef.ctypes.data, int(bool(first)),
+                         form, self.partials.data_ptr(), self.partials.numel(), stats_ptr, self.host_ws.data_ptr(),
+                         self.dev_ws.data_ptr(), self.host_ws.numel(), st.cuda_stream)
+            _lib.check_clientadam(rc, self.name)
+            if self._free is None:
+                self._free = torch.cuda.Event()
+            self._free.record(st)
+
+
+def _adam_probe_values(dtype):
+    """Seeded weights and gradients N(0, 1), the pool of 2^21: in a 16-bit
+    type the two forms of site A, B or E leave different bits on tens to
+    hundreds of its elements."""
+    rng = np.random.default_rng(20251)
+    return (torch.from_numpy(rng.normal(0.0, 1.0, _PROBE_POOL)).to(dtype),
+            torch.from_numpy(rng.normal(0.0, 1.0, _PROBE_POOL)).to(dtype))
+
+
+def _mine_site_c(dtype, most=64):
+    """``(beta2, g, v)`` for a 16-bit ``dtype`` on which site C's two forms,
+    ``v' = rT(v1 + value * g^2)`` with ``v1 = rT(v * beta2)`` and ``value = 1
+    - beta2``, store different bits: a Python float, one gradient value and up
+    to ``most`` second moments.
+
+    Random values never reach this site in a 16-bit type.  Both terms are
+    non-negative and ``v1`` is a value of the type, so the forms part only
+    when ``fl32(value * g^2)`` is inexact and lies half an fp32 ulp of the
+    sum from a rounding boundary of the type: its low 24 - p bits are all
+    ones with the exact product below it, or 0...01 with it above (p the
+    type's precision).  That is a property of ``(value, g)`` alone, one pair
+    in 2^(25 - p); a seeded search over ``value`` in (0.2, 0.4) and ``g ~ N(0,
+    1)`` finds such pairs, and for one of them every ``v`` of the type in
+    [2^-6, 16) is tried.  The forms are computed here in fp64 (the product
+    exact, the sum rounded once more): a filter, as in ``_probe_values``;
+    whether they differ on the device is adam_form's own check."""
+    prec = {torch.float16: 11, torch.bfloat16: 8}[dtype]
+    rng = np.random.default_rng(20253)
+    n = 1 << 21
+    value = rng.uniform(0.2, 0.4, n).astype(np.float32)
+    g = torch.from_numpy(rng.normal(0.0, 1.0, n)).to(dtype).float().numpy()
+    exact = value.astype(np.float64) * (g * g).astype(np.float64)  # g * g is exact in fp32 for a 16-bit g
+    with np.errstate(all="ignore"):
+        c = exact.astype(np.float32)
+    low = c.view(np.uint32) & np.uint32((1 << (24 - prec)) - 1)
+    cand = np.flatnonzero(((low == (1 << (24 - prec)) - 1) & (exact < c)) | ((low == 1) & (exact > c)))
+    every = torch.arange(0, 1 << 15, dtype=torch.int16).view(dtype).float().numpy()
+    every = every[(every >= 2.0 ** -6) & (every < 16.0)]
+    to_type = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dtype).float().numpy()  # noqa: E731
+    for i in cand:
+        beta2 = 1.0 - float(value[i])
+        if np.float32(1.0 - beta2) != value[i]:
+            continue
+        with np.errstate(all="ignore"):
+            v1 = to_type(every * np.float32(beta2))
+            apart = to_type(v1 + c[i])
+            once = to_type((v1.astype(np.float64) + exact[i]).astype(np.float32))
+        hit = np.flatnonzero(apart != once)[:most]
+        if len(hit):
+            return beta2, torch.tensor(float(g[i]), dtype=dtype), torch.from_numpy(every[hit]).to(dtype)
+    raise RuntimeError(f"no pair found for site C in {dtype}")
+
+
+def _probe_adam_form(device, dtype):
+    h = dict(_ADAM_PROBE)
+    w, g = _adam_probe_values(dtype)
+    mined = None
+    if dtype in (torch.float16, torch.bfloat16):
+        # the last elements of the probe are site C's: w = 0 (so g1 = g), and before step 2 their v and vmax are
+        # set to the mined second moments, in torch's state and in the kernel's alike
+        beta2, g_c, v_c = _mine_site_c(dtype)
+        h["betas"] = (h["betas"][0], beta2)
+        mined = slice(w.numel() - v_c.numel(), w.numel())
+        w[mined] = 0.0
+    bits = _BITS[w.element_size()]
+    n = w.numel()
+    with torch.cuda.device(device):
+        w, g = w.to(device), g.to(device)
+        grads = [torch.roll(g, 7 * t) for t in range(_ADAM_PROBE_STEPS)]  # another gradient every step
+        if mined is not None:
+            v_c = v_c.to(device)
+            grads[1][mined] = g_c.to(device)
+
+        def inject(w_t, v_t, vmax_t):
+            w_t[mined] = 0.0
+            v_t[mined] = v_c
+            vmax_t[mined] = v_c
+
+        p = torch.nn.Parameter(w.clone())
+        opt = torch.optim.Adam([p], lr=h["lr"], betas=h["betas"], eps=h["eps"], weight_decay=h["weight_decay"],
+                               amsgrad=True)
+        want = []
+        for t in range(_ADAM_PROBE_STEPS):
+            if mined is not None and t == 1:
+                with torch.no_grad():
+                    inject(p, opt.state[p]["exp_avg_sq"], opt.state[p]["max_exp_avg_sq"])
+            p.grad = grads[t].clone()
+            opt.step()
+            state = opt.state[p]
+            want.append([x.detach().view(bits).clone() for x in
+                         (p, state["exp_avg"], state["exp_avg_sq"], state["max_exp_avg_sq"])])
+        rec = torch.empty(4, dtype=torch.float64, device=device)
+        st = torch.cuda.current_stream(device)
+        numel, offset = np.array([n], dtype=np.int64), np.zeros(1, dtype=np.int64)
+        step = _AdamPass(numel, offset, n, dtype, device)
+        off = []
+        for form in range(1 << ADAM_SITES):
+            c = w.clone()
+            differ = torch.zeros((), dtype=torch.int64, device=device)
+            for t in range(_ADAM_PROBE_STEPS):
+                if mined is not None and t == 1:
+                    inject(c, step.plane(1), step.plane(2))
+                coef = adam_coef(h["lr"], *h["betas"], h["eps"], h["weight_decay"], t + 1)
+                step.launch(np.array([c.data_ptr()], dtype=np.int64), np.array([grads[t].data_ptr()], dtype=np.int64),
+                            coef, t == 0, form, rec.data_ptr(), st)
+                for a, b in zip([c.view(bits)] + [step.plane(i).view(bits) for i in range(3)], want[t]):
+                    differ += (a != b).sum()
+            off.append(int(differ))  # the one read per mask
+    # two masks that both equal torch equal each other on the whole probe: it cannot tell them apart, and a mask that
+    # equals torch differs from every one that does not.  So the answer is the ONE mask at 0, if there is exactly one.
+    match = tuple(o == 0 for o in off)
+    form = match.index(True) if sum(match) == 1 else None
+    return {"form": form, "match": match, "off": tuple(off), "n": int(n), "steps": _ADAM_PROBE_STEPS,
+            "mined_site_c": 0 if mined is None else int(v_c.numel()), "betas": h["betas"]}
+
+
+def adam_form_probe(device, dtype):
+    """What :func:`adam_form` found for (device, dtype), cached: ``form``,
+    ``match`` (per mask: equal to torch on every element of ``p, exp_avg,
+    exp_avg_sq, max_exp_avg_sq`` after each of ``steps`` steps), ``off`` (per
+    mask: the number of elements that differ from torch's) and ``n``."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TypeError(f"adam_form needs a GPU, not {device}")
+    index = torch.cuda.current_device() if device.index is None else device.index
+    key = (index, dtype)
+    if key not in _adam_probes:
+        _adam_probes[key] = _probe_adam_form(torch.device("cuda", index), dtype)
+    return _adam_probes[key]
+
+
+def adam_form(device, dtype):
+    """Which form mask of ``fedavg_client_adam_step_*`` leaves the bits of
+    ``torch.optim.Adam(params, lr, weight_decay=wd, amsgrad=True).step()`` on
+    this GPU, or ``None``.  Found by running torch's own optimizer for three
+    steps and the kernel under all 16 masks on the same seeded values (for a
+    16-bit type joined by pairs mined for site C, which random values never
+    reach there); the
+    answer is a mask that equals torch on every element of the parameter and
+    of the three state tensors at every step and differs from every other
+    mask somewhere on the probe.  Once per (device, dtype)."""
+    if dtype not in ADAM_DTYPES:
+        return None
+    return adam_form_probe(device, dtype)["form"]
+
+
+def _adam_hyper(adam):
+    """``adam`` with torch.optim.Adam's defaults filled in; ``lr`` is required."""
+    if adam is None or "lr" not in adam:
+        raise ValueError("optimizer='adam' needs adam=dict(lr=..., betas=(0.9, 0.999), eps=1e-8, weight_decay=0, "
+                         "amsgrad=True)")
+    unknown = set(adam) - {"lr", "betas", "eps", "weight_decay", "amsgrad"}
+    if unknown:
+        raise ValueError(f"adam: unknown keys {sorted(unknown)}")
+    h = {"betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.0, "amsgrad": True, **adam}
+    h["betas"] = (float(h["betas"][0]), float(h["betas"][1]))
+    return h
+
+
 class ClientStepStats:
     """Snapshots, key tables, workspaces and the running rho / beta of one
     ``Client.train`` call.
@@ -255,10 +496,22 @@ class ClientStepStats:
     needs the fused statistics and a form from :func:`sgd_form`, else
     ``TypeError``.  ``step="auto"`` falls back to ``"torch"`` instead;
     ``step_mode`` says which of the two the object was built for.
+
+    ``optimizer="adam"`` with ``adam=dict(lr, betas=(0.9, 0.999), eps=1e-8,
+    weight_decay=0, amsgrad=True)``: under fused stepping the object owns the
+    zeroed optimizer state and the step count, and ``adam_step()`` takes the
+    place of ``optimizer.step()`` and ``after_step()``.  ``amsgrad=False``, a
+    parameter that does not require grad, ``beta1 <= 0.5`` or a dtype without
+    a form from :func:`adam_form` are a ``TypeError`` under ``"fused"`` and
+    torch under ``"auto"``.
     """
 
-    def __init__(self, params, *, stream=None, stats="auto", trace=None, step="torch"):
+    def __init__(self, params, *, stream=None, stats="auto", trace=None, step="torch", optimizer="sgd", adam=None):
         self.params = list(params)
+        if optimizer not in ("sgd", "adam"):
+            raise ValueError(f"optimizer must be 'sgd' or 'adam', not {optimizer!r}")
+        self.optimizer = optimizer
+        self.adam = _adam_hyper(adam) if optimizer == "adam" else None
         if stats not in ("auto", "hip", "torch"):
             raise ValueError(f"stats must be 'auto', 'hip' or 'torch', not {stats!r}")
         if step not in ("torch", "fused", "auto"):
@@ -278,13 +531,23 @@ class ClientStepStats:
             self._last_w = self._last_grads = self._grads = None
             self._rho = self._beta = None
         self.step_mode = "torch"
-        if step != "torch":
+        if step != "torch" and optimizer == "sgd":
             self._form = sgd_form(self.device, self.dtype) if self.mode == "hip" else None
             if self._form is not None:
                 self.step_mode = "fused"
                 self._step = _StepPass(self._numel, self.dtype, self.device)
             elif step == "fused":
                 raise TypeError(f"step='fused' needs {_STEP_RULE}")
+        elif step != "torch":
+            h = self.adam
+            plain = h["amsgrad"] is True and h["betas"][0] > 0.5 and all(p.requires_grad for p in self.params)
+            self._form = adam_form(self.device, self.dtype) if self.mode == "hip" and plain else None
+            if self._form is not None:
+                self.step_mode = "fused"
+                self._t = 0
+                self._step = _AdamPass(self._numel, self._offset, self.P, self.dtype, self.device)
+            elif step == "fused":
+                raise TypeError(f"step='fused' needs {_ADAM_RULE}")
 
     # ------------------------------------------------------------------ fused
     def _init_hip(self):
@@ -464,11 +727,38 @@ class ClientStepStats:
         if self.step_mode != "fused":
             raise RuntimeError("sgd_step() needs an object built with step='fused' (or 'auto' where it applies): "
                                f"this one steps with torch ({self.step_mode=})")
+        if self.optimizer != "sgd":
+            raise RuntimeError("sgd_step() on an object built with optimizer='adam': adam_step() takes its step")
         if not self._begun:
             raise RuntimeError("begin() first")
         st = self._torch_stream()
         base = self._rec.data_ptr()
         self._step.launch(self._ptrs["w"], self._grad_ptrs(), lr, self._form, base + 8 * _W, st)
+        torch.autograd.graph.increment_version(self.params)  # the in-place update autograd did not see
+        with torch.cuda.device(self.device):
+            rc = self._track_fn(base + 8 * _STATE, base + 8 * _W, base + 8 * _G, abs(loss - last_loss), st.cuda_stream)
+        self._check(rc, self._track_name)
+        self._emit("after_step", loss)
+
+    def adam_step(self, loss, last_loss):
+        """client.py:74-86 in one kernel, in place of ``optimizer.step()`` and
+        ``after_step()``: the Adam step with torch.optim.Adam's bits on ``w``
+        and on the state this object owns, the weight record and the running
+        rho / beta.  The first call of an object does not read the state.  No
+        host sync."""
+        if self.step_mode != "fused":
+            raise RuntimeError("adam_step() needs an object built with step='fused' (or 'auto' where it applies): "
+                               f"this one steps with torch ({self.step_mode=})")
+        if self.optimizer != "adam":
+            raise RuntimeError("adam_step() on an object built with optimizer='sgd': sgd_step() takes its step")
+        if not self._begun:
+            raise RuntimeError("begin() first")
+        st = self._torch_stream()
+        base = self._rec.data_ptr()
+        h = self.adam
+        self._t += 1
+        coef = adam_coef(h["lr"], *h["betas"], h["eps"], h["weight_decay"], self._t)
+        self._step.launch(self._ptrs["w"], self._grad_ptrs(), coef, self._t == 1, self._form, base + 8 * _W, st)
         torch.autograd.graph.increment_version(self.params)  # the in-place update autograd did not see
         with torch.cuda.device(self.device):
             rc = self._track_fn(base + 8 * _STATE, base + 8 * _W, base + 8 * _G, abs(loss - last_loss), st.cuda_stream)
@@ -497,25 +787,33 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
     returns ``net.state_dict()`` without the ``.cpu()`` of :73 / :96.
     ``step`` is :class:`ClientStepStats`'s: with fused stepping and
     ``args.client_optimizer == "sgd"`` one ``sgd_step(args.lr, ...)`` replaces
-    ``optimizer.step()`` and ``after_step()``; Adam is a ``TypeError`` under
-    ``"fused"`` and steps with torch under ``"auto"``.
+    ``optimizer.step()`` and ``after_step()``.  Any other
+    ``args.client_optimizer`` is the reference's Adam (``lr``, ``wd``,
+    amsgrad): with fused stepping one ``adam_step()`` per iteration and no
+    torch optimizer at all; where the fused Adam step does not apply it is a
+    ``TypeError`` under ``"fused"`` and steps with torch under ``"auto"``.
     """
     mod = sys.modules[type(self).__module__]
     count, count_end, ratio = mod.count, mod.count_end, mod.THRESHOLD_GRADS_RATIO
     sgd = self.args.client_optimizer == "sgd"
+    tracker = None
+    if not sgd and step != "torch":  # refused, if it is, before anything runs
+        try:
+            tracker = ClientStepStats(net.parameters(), stats=stats, trace=trace, step=step, optimizer="adam",
+                                      adam=dict(lr=self.args.lr, weight_decay=self.args.wd, amsgrad=True))
+        except TypeError as e:
+            raise TypeError(f"{e}; args.client_optimizer is {self.args.client_optimizer!r}") from None
     if sgd:
         optimizer = torch.optim.SGD(net.parameters(), lr=self.args.lr)
-    else:
-        if step == "fused":
-            raise TypeError(f"step='fused' needs {_STEP_RULE}; args.client_optimizer is "
-                            f"{self.args.client_optimizer!r}")
+    elif tracker is None or tracker.step_mode != "fused":
         optimizer = torch.optim.Adam(filter(lambda p: p.requires_grad, net.parameters()), lr=self.args.lr,
                                      weight_decay=self.args.wd, amsgrad=True)
     cycles = []
     x, labels = next(iter(self.local_training_data))
     x, labels = x.to(self.device), labels.to(self.device)
     net.train()
-    tracker = ClientStepStats(net.parameters(), stats=stats, trace=trace, step=step if sgd else "torch")
+    if tracker is None:
+        tracker = ClientStepStats(net.parameters(), stats=stats, trace=trace, step=step if sgd else "torch")
     fused = tracker.step_mode == "fused"
     last_loss = self.criterion(net(x), labels)
     torch.nn.utils.clip_grad_norm_(net.parameters(), self.args.clip)
@@ -537,8 +835,10 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
                 logger.warning("grads too large than weights or meets nan with epoch {}".format(epoch))
             return done(), None, None, None, None, None
         loss = tracker.loss
-        if fused:
+        if fused and sgd:
             tracker.sgd_step(self.args.lr, loss, last_loss)
+        elif fused:
+            tracker.adam_step(loss, last_loss)
         else:
             optimizer.step()
             tracker.after_step(loss, last_loss)
