@@ -249,12 +249,23 @@ def sgd_form(device, dtype):
 
 
 # ------------------------------------------------------------------ fused Adam step
-# The dtypes the fused Adam step is offered for: those adam_form() found a mask for on the MI355X (torch 2.10 /
-# ROCm 7.0: mask 15, all four sites one fma, for fp32, bf16, fp16 and fp64).
-ADAM_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
+# The dtypes the fused Adam step is offered for.  Two findings on the MI355X (torch 2.10 / ROCm 7.0) decide it: the
+# probe below finds one mask that equals torch (mask 15, all four sites one fma, for fp32, bf16, fp16 and fp64), AND
+# the kernel under that mask equals torch.optim.Adam bit for bit over twelve-step chains at the reference's own
+# hyperparameters and three other sets, down to subnormal second moments (tests/test_gpu_client_adam_torch.py;
+# DESIGN.md §3).  fp16 passes the first and fails the second: torch's fp16 kernels round g + wd * w, v * beta2,
+# v1 + value * g1^2 and w + step * (m' / s3) ONCE, from the exact result straight to fp16 (scripts/probe_adam_ops.py
+# --fp16-ties, profiles/client_adam/ops_probe_fp16_ties.json; tests/test_gpu_client_adam_torch.py), where every
+# form of the kernel rounds to fp32 first.  The two part
+# where the exact result lies within half an fp32 ulp of an fp16 rounding midpoint, which the decimal scalars 0.001
+# and 0.999 make common for fp16 operands and the probe's scalars do not.  The same test file holds that finding on
+# the kernel's C entry.  fedavg_client_adam_step_f16 stays in the C ABI; nothing here calls it.  For a dtype outside
+# this tuple adam_form() answers None without probing; adam_form_probe() still runs the probe and reports what it
+# finds (for fp16: mask 15), which says that the mask matches torch on the probe's values and no more.
+ADAM_DTYPES = (torch.float32, torch.bfloat16, torch.float64)
 ADAM_SITES = 4  # A g + wd w, B the lerp, C the addcmul, E the addcdiv: bit i of a form mask fuses site i
-_ADAM_RULE = (f"the fused statistics ({_RULE}), a dtype adam_form() has a mask for, torch.optim.Adam with amsgrad=True "
-              "and beta1 > 0.5 over parameters that all require grad, and a form of the Adam step kernel that leaves "
+_ADAM_RULE = (f"the fused statistics ({_RULE}), a dtype of ADAM_DTYPES (fp32, bf16, fp64), torch.optim.Adam with "
+              "amsgrad=True and beta1 > 0.5 over parameters that all require grad, and a form of the Adam step kernel that leaves "
               "torch.optim.Adam's bits on this GPU (adam_form)")
 # The form is a property of torch's compiled kernels, not of the hyperparameters, so the probe picks hyperparameters
 # and values at which both terms of every site are of one magnitude (w, g ~ N(0, 1)): there two forms of a site leave
@@ -462,7 +473,10 @@ def adam_form(device, dtype):
     reach there); the
     answer is a mask that equals torch on every element of the parameter and
     of the three state tensors at every step and differs from every other
-    mask somewhere on the probe.  Once per (device, dtype)."""
+    mask somewhere on the probe.  Once per (device, dtype).  ``None``
+    without a probe for a dtype outside ``ADAM_DTYPES``: that tuple leaves
+    out fp16, whose mask equals torch on the probe but not at the
+    reference's hyperparameters (see the comment at ``ADAM_DTYPES``)."""
     if dtype not in ADAM_DTYPES:
         return None
     return adam_form_probe(device, dtype)["form"]

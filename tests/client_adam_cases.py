@@ -11,8 +11,15 @@ site_c() gives the pairs mined for it (client_stats._mine_site_c) and the
 later-step launch they are sent through.  In a 16-bit type a bit changes a stored element only
 where an fp32 result lies at a rounding boundary of the type, so such a case
 is joined by mined elements (mined()): pairs of a seeded pool on which the
-host reference's answers under the two settings of the bit differ."""
+host reference's answers under the two settings of the bit differ.
+
+The second half builds the chains that tests/test_gpu_client_adam_torch.py
+holds against torch.optim.Adam itself: twelve steps at the reference's own
+hyperparameters and three other sets, at gradient and weight scales down to
+where the second moment is subnormal or underflows, and the conditions those
+inputs must meet (tests/test_client_adam_torch_cases_cpu.py)."""
 import functools
+import math
 
 import numpy as np
 import torch
@@ -88,6 +95,8 @@ def sizes(name, key):
         return n
     if name == "long":
         return [257 * U + 3]
+    if name == "chain":
+        return [1, 3, P - 1, P, P + 1, 63, U - 1, U + 1, 2 * U + 3]
     raise KeyError(name)
 
 
@@ -95,13 +104,14 @@ class Case:
     """Keys in one buffer per side (w, g), PAD or more sentinels around each; the state planes are laid out as
     ClientStepStats lays them out: every key at the next multiple of 16 B."""
 
-    def __init__(self, name, key, steps=3):
+    def __init__(self, name, key, steps=3, values=None):
+        """``values``: (w, [g of step 1, ...]) in place of the seeded N(0, 1) draws and the mined elements."""
         self.name, self.key, self.dt, self.steps = name, key, DTYPES[key], steps
         P = KPER[key]
         self.numel = np.array(sizes(name, key), dtype=np.int64)
         n_keys, total = len(self.numel), int(self.numel.sum())
         j = np.arange(n_keys)
-        if name == "k130":  # every sub-16-B offset on either side, and all four (aligned, aligned) pairs
+        if name in ("k130", "chain"):  # every sub-16-B offset on either side, and all four (aligned, aligned) pairs
             self.off = {"w": j % P, "g": (3 * j + 1) % P}
             self.off["g"][j % (4 * P) == 0] = 0
             self.off["g"][j % (4 * P) == 1] = 1
@@ -122,6 +132,11 @@ class Case:
         i = np.arange(total) - first[key_of]
         self.pos = {side: self.start[side][key_of] + i for side in "wg"}
         self.pos["s"] = self.state_offset[key_of] + i
+        self._ref = {}
+        if values is not None:
+            self.w, self.g = values[0], list(values[1])
+            assert len(self.g) == steps and all(len(t) == total and t.dtype == self.dt for t in (self.w, *self.g))
+            return
         seed = sum(map(ord, name)) * 7 + len(key)
         self.w = normal(seed, total, self.dt)
         self.g = [normal(seed + 1 + t, total, self.dt) for t in range(steps)]
@@ -131,7 +146,6 @@ class Case:
             self.w[at], self.g[0][at] = mw[:len(at)], mg0[:len(at)]
             if steps > 1:
                 self.g[1][at] = mg1[:len(at)]
-        self._ref = {}
 
     def reference(self, form, **change):
         """Per step t = 1..steps: ((w', m', v', vmax'), record), each step from the one before; the first from zeros."""
@@ -159,10 +173,138 @@ def case(name, key):
     return Case(name, key, steps=1 if name == "long" else 3)
 
 
-def stored_differ(c, form_a, form_b):
+def stored_differ(c, form_a, form_b, **change):
     """Elements of any stored tensor at any step on which the reference's answers under two masks differ."""
     n = 0
-    for (ra, _), (rb, _) in zip(c.reference(form_a), c.reference(form_b)):
+    for (ra, _), (rb, _) in zip(c.reference(form_a, **change), c.reference(form_b, **change)):
         for a, b in zip(ra, rb):
             n += int(((A.bits(a) != A.bits(b)) & ~(torch.isnan(a) & torch.isnan(b))).sum())
     return n
+
+
+# --------------------------------------------------- chains held against torch.optim.Adam itself
+# tests/test_gpu_client_adam_torch.py runs these through torch.optim.Adam, through ClientStepStats.adam_step() and
+# through the host reference; tests/test_client_adam_torch_cases_cpu.py holds them to the conditions below.
+#
+# Twelve steps, a fresh seeded gradient each: g ~ 2^eg N(0, 1) in steps 1-6 and 2^(eg - 5) N(0, 1) in steps 7-12 (the
+# second moment then decays below its maximum and amsgrad engages), w ~ 2^ew N(0, 1).  A scale is the pair (eg, ew).
+#
+# ew = 0 is a model of ordinary weights under gradients of every size.  With weight decay it cannot reach a small
+# second moment: g1 = g + wd w is then wd w whatever g is, so at the reference's wd = 1e-3 and w ~ N(0, 1) v' is about
+# 1e-9 w^2, far above the subnormal range of bf16, fp32 and fp64 (it does reach fp16's).  The last scale of those
+# three types therefore shrinks the weights with the gradients (a "small model"), far enough that v' is subnormal or
+# underflows: v' = 0.001 g1^2 is below the least normal value (2^-126, fp64 2^-1022) for g1 below 2^-58 (fp64
+# 2^-506).  There sqrt(v) is far below eps, the step is lr m / eps, and with weight decay w grows about a
+# hundredfold a step (lr wd / eps = 100), so under (a) and (c) v' is subnormal in the first five steps from 2^-70
+# (fp64 2^-520); under (b), without weight decay, in all twelve.
+HYPERS = {
+    "a": dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, wd=1e-3),  # the reference's
+    "b": dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0),   # no op A
+    "c": dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-3, wd=1e-3),  # an eps fp16 keeps: a finite fp16 chain
+    "d": dict(HYPER),                                               # the probe's, here at small magnitudes too
+}
+CHAIN_STEPS = 12
+CHAIN_SHRINK = 5  # steps 7-12: the gradient scale over 32
+CHAIN_SCALES = {
+    "f32": ((0, 0), (-10, 0), (-20, 0), (-62, 0), (-70, -70)),
+    "bf16": ((0, 0), (-10, 0), (-20, 0), (-62, 0), (-70, -70)),
+    "f16": ((0, 0), (-6, 0), (-10, 0)),
+    "f64": ((0, 0), (-10, 0), (-20, 0), (-62, 0), (-520, -520)),
+}
+STORED = ("w", "exp_avg", "exp_avg_sq", "max_exp_avg_sq")
+
+
+def scale_id(scale):
+    return f"g2^{scale[0]}_w2^{scale[1]}"
+
+
+@functools.lru_cache(maxsize=None)
+def chain(key, scale):
+    """The Case of one dtype and scale: the "chain" sizes (1, 3, 16 B - 1, 16 B, 16 B + 1, 63, unit - 1, unit + 1
+    and 2 units + 3 elements), k130's offsets for the flat layout, CHAIN_STEPS seeded gradients."""
+    eg, ew = scale
+    dt, total = DTYPES[key], sum(sizes("chain", key))
+    seed = 5000 + 100 * KEYS.index(key) + 17 * CHAIN_SCALES[key].index(scale)
+    w = normal(seed, total, dt, 2.0 ** ew)
+    g = [normal(seed + 1 + t, total, dt, 2.0 ** (eg - (CHAIN_SHRINK if t >= CHAIN_STEPS // 2 else 0)))
+         for t in range(CHAIN_STEPS)]
+    return Case("chain", key, steps=CHAIN_STEPS, values=(w, g))
+
+
+def chain_reference(key, scale, hyper, form=15):
+    """Per step the host reference's (w', m', v', vmax') of the chain under hyperparameter set ``hyper`` (cached)."""
+    return [res for res, _ in chain(key, scale).reference(form, **HYPERS[hyper])]
+
+
+def subnormal(t):
+    """Elements of t that are non-zero and below the least normal value of its type."""
+    return (t != 0) & (t.abs() < torch.finfo(t.dtype).smallest_normal)
+
+
+def chain_counts(stored, g):
+    """What the conditions are about, per step, from the stored (w', m', v', vmax') of every step and the steps'
+    gradients: elements with vmax' > v', with a subnormal v', with v' == 0 under g != 0 (underflowed), and whether
+    all four tensors are finite."""
+    out = {"vmax_gt_v": [], "subnormal_v": [], "underflowed_v": [], "finite": []}
+    for (w, m, v, x), g_t in zip(stored, g):
+        out["vmax_gt_v"].append(int((x > v).sum()))
+        out["subnormal_v"].append(int(subnormal(v).sum()))
+        out["underflowed_v"].append(int(((v == 0) & (g_t != 0)).sum()))
+        out["finite"].append(all(bool(torch.isfinite(t).all()) for t in (w, m, v, x)))
+    return out
+
+
+def condition_sets(key):
+    """The hyperparameter sets check_conditions() reads for a dtype."""
+    return {"f16": ("a", "c"), "bf16": ("a", "d")}.get(key, ("a",))
+
+
+def check_conditions(key, counts):
+    """The conditions the chains' inputs must meet, on the counts (chain_counts) of every scale of one dtype:
+    ``counts[hyper][scale]`` for the sets of condition_sets(key).  They are the same for the host reference's states
+    and for torch's.  All are about set (a), the reference's, with two exceptions that arithmetic forces:
+
+    * bf16 never has vmax' > v' at beta2 = 0.999: v * 0.999 is within half a bf16 ulp of v (half an ulp is 2^-9 of
+      v or more, also downwards from a power of two, where v * 0.999 lies above the midpoint 0.998 v), so v1 =
+      rT(v * beta2) = v, v' >= v and the maximum is always the new value.  That is asserted, and amsgrad engaged is
+      asked of set (d), beta2 = 0.7.
+    * fp16 rounds s3 = s2 + 1e-8 to 0 where v is 0, so no fp16 chain under (a) stays finite; the finite one is (c)'s."""
+    total = sum(sizes("chain", key))
+    every = list(counts["a"].values())
+    # amsgrad engaged: somewhere a quarter of the elements keep an older maximum, and some do in every step from 7 on
+    engaged = every
+    if key == "bf16":
+        assert all(max(c["vmax_gt_v"]) == 0 for c in every), (key, [c["vmax_gt_v"] for c in every])
+        engaged = list(counts["d"].values())
+    assert any(max(c["vmax_gt_v"]) >= total / 4 for c in engaged), (key, [c["vmax_gt_v"] for c in engaged])
+    assert any(min(c["vmax_gt_v"][CHAIN_STEPS // 2:]) >= 1 for c in engaged), (key, [c["vmax_gt_v"] for c in engaged])
+    # a stored second moment that is subnormal in the model's type
+    assert any(max(c["subnormal_v"]) >= 64 for c in every), (key, [c["subnormal_v"] for c in every])
+    if key in ("bf16", "f16"):  # and one that underflowed
+        assert any(max(c["underflowed_v"]) >= 64 for c in every), (key, [c["underflowed_v"] for c in every])
+    # a chain that stays finite to the end
+    finite = counts["c" if key == "f16" else "a"]
+    assert any(all(c["finite"]) for c in finite.values()), (key, {s: c["finite"] for s, c in finite.items()})
+
+
+def plant_specials(c):
+    """test_special_values_equal_the_reference's elements in every step of Case ``c`` (sizes "edges" or "chain")."""
+    tiny = torch.finfo(c.dt).smallest_normal
+    for g in c.g:
+        g[0], g[1], g[2] = math.nan, math.inf, -math.inf
+        g[3], c.w[3] = 0.0, 0.0                       # wd * w + g = 0: v' = 0, s3 = eps, 0 / eps
+        g[4], c.w[4] = 0.0, -0.0
+        g[5], c.w[5] = math.sqrt(tiny) / 4, 0.0       # g1^2 subnormal: subnormal v and vmax
+        g[6], c.w[6] = tiny / 2, tiny / 4             # subnormal g and w
+        g[7], c.w[7] = 6.0e4, 6.0e4                   # g1^2 overflows fp16
+        g[len(g) - 1] = math.nan                      # in the ragged last slice of the last key
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def specials(key):
+    """Two steps on the chain sizes with the special values planted (w, g ~ N(0, 1) otherwise)."""
+    total = sum(sizes("chain", key))
+    seed = 7000 + KEYS.index(key)
+    values = (normal(seed, total, DTYPES[key]), [normal(seed + 1 + t, total, DTYPES[key]) for t in range(2)])
+    return plant_specials(Case("chain", key, steps=2, values=values))

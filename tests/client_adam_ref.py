@@ -118,6 +118,49 @@ def step(key, form, coef, w, g, m, v, x):
     return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dt) for a in (wn, mn, vn, xn))
 
 
+ONCE_OPS = ("A", "B", "mul", "C", "sqrt", "div", "add", "E")
+
+
+def _r16(x64):
+    """An fp64 array rounded ONCE to fp16 (numpy converts fp64 -> fp16 directly), widened to fp32."""
+    with np.errstate(all="ignore"):
+        return x64.astype(np.float16).astype(np.float32)
+
+
+def step_f16_once(coef, w, g, m, v, x, once=ONCE_OPS):
+    """fp16 only: the step with every op named in ``once`` rounded a single time, from its exact fp32-operand
+    result straight to fp16 (a mixed-precision operation that keeps no fp32 intermediate), and every other op as
+    the definition has it under mask 15 (rounded to fp32, then to fp16).  The fma sites: the fp64 product of two
+    fp32 values is exact, the fp64 sum is rounded to odd, and numpy rounds fp64 to fp16 once
+    (client_step_ref.step_f16_once).  The single operations (v * beta2, sqrt, s1 / bc2s, s2 + eps): formed in fp64,
+    where product and sum are exact and quotient and root carry 53 >= 2 * 11 + 2 bits, then rounded to fp16."""
+    key = "f16"
+    assert all(t.dtype == torch.float16 and t.dim() == 1 for t in (w, g, m, v, x)) and set(once) <= set(ONCE_OPS)
+    wd, lw, beta2, value, bc2s, eps, step_size = (np.float32(c) for c in coef)
+    w_, g_, m_, v_, x_ = (_widen(key, t) for t in (w, g, m, v, x))
+
+    def fma(name, s, y, a):
+        if name in once:
+            return _r16(R._exact_sum_to_odd(s, y, a))
+        return _rT(key, axpy(key, 1, s, y, a))
+
+    def one(name, exact64, plain32):
+        return _r16(exact64()) if name in once else _rT(key, plain32())
+
+    f64 = lambda a: a.astype(np.float64)  # noqa: E731
+    with np.errstate(all="ignore"):
+        g1 = g_ if coef[0] == 0 else fma("A", wd, w_, g_)
+        mn = fma("B", lw, g1 - m_, m_)
+        v1 = one("mul", lambda: f64(v_) * np.float64(beta2), lambda: v_ * beta2)
+        vn = fma("C", value, g1 * g1, v1)
+        xn = max_nan(x_, vn)
+        s1 = one("sqrt", lambda: np.sqrt(f64(xn)), lambda: sqrt(key, xn))
+        s2 = one("div", lambda: f64(s1) / np.float64(bc2s), lambda: divide(key, s1, np.full_like(s1, bc2s)))
+        s3 = one("add", lambda: f64(s2) + np.float64(eps), lambda: s2 + eps)
+        wn = fma("E", step_size, divide(key, mn, s3), w_)
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(torch.float16) for a in (wn, mn, vn, xn))
+
+
 def reference(key, form, coef, first, w, g, m=None, v=None, x=None):
     """((w', m', v', vmax'), record) of one call over the concatenated elements of all keys; ``first``: zero state."""
     if first:
