@@ -34,7 +34,7 @@ from .session import RoundSession
 from .multi import ShardedAggregator, ShardedRoundSession, sharded_aggregator
 from .fpf import FPFTracker
 from . import client_stats
-from .client_stats import ADAM_DTYPES, ClientStepStats, adam_form, adam_form_probe, client_train
+from .client_stats import ADAM_DTYPES, DEFAULT_AHEAD, ClientStepStats, adam_form, adam_form_probe, client_train
 
 __all__ = [
     "FedAvgLibraryError",
@@ -68,4 +68,5 @@ __all__ = [
     "ADAM_DTYPES",
     "adam_form",
     "adam_form_probe",
+    "DEFAULT_AHEAD",
 ]

@@ -1,4 +1,4 @@
-"""ctypes binding of the native libraries ``build.EVERY_LIB`` describes (the C ABI
+"""ctypes binding of the native libraries ``build.BUILT_LIBS`` describes (the C ABI
 in include/*.h): a signature table each, one loader and one status check.
 
 There is no fallback: if a HIP library is missing or does not export the
@@ -11,8 +11,8 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTVEC_LIB_PATH, DESCRIBED, FUSEDVEC_LIB_PATH,
-                    LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH, NativeLib)
+from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTVEC_LIB_PATH, DESCRIBED,
+                    EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH, NativeLib)
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -183,12 +183,34 @@ CLIENTADAM_SIGNATURES = {
     "fedavg_client_adam_step_f64": _CLIENTADAM_STEP,
 }
 
+# libfedavg_amd_clientloop.so (include/fedavg_amd_clientloop.h): the steps' arguments, then g_stats, gate, state, loss
+_CLIENTLOOP_GUARD = (_c_int, [_vp, _vp, _vp, _vp, ctypes.c_double, _c_i64, _vp])
+_CLIENTLOOP_SGD = (_c_int, _CLIENTSTEP_STEP[1] + [_vp, _vp, _vp, _vp])
+_CLIENTLOOP_ADAM = (_c_int, _CLIENTADAM_STEP[1] + [_vp, _vp, _vp, _vp])
+CLIENTLOOP_SIGNATURES = {
+    "fedavg_clientloop_abi_version": (_c_int, []),
+    "fedavg_clientloop_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_loop_span": (_c_i64, [_c_i64]),
+    "fedavg_client_loop_workspace": (_c_i64, [_c_i64, _c_int]),
+    "fedavg_client_loop_partials": (_c_i64, [_vp, _c_i64, _c_i64]),
+    "fedavg_client_guard_f32": _CLIENTLOOP_GUARD,
+    "fedavg_client_guard_bf16": _CLIENTLOOP_GUARD,
+    "fedavg_client_guard_f64": _CLIENTLOOP_GUARD,
+    "fedavg_client_sgd_step_gated_f32": _CLIENTLOOP_SGD,
+    "fedavg_client_sgd_step_gated_bf16": _CLIENTLOOP_SGD,
+    "fedavg_client_sgd_step_gated_f64": _CLIENTLOOP_SGD,
+    "fedavg_client_adam_step_gated_f32": _CLIENTLOOP_ADAM,
+    "fedavg_client_adam_step_gated_bf16": _CLIENTLOOP_ADAM,
+    "fedavg_client_adam_step_gated_f64": _CLIENTLOOP_ADAM,
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
 CLIENTVEC_ABI_VERSION = BY_KEY["clientvec"].abi[1]
 CLIENTSTEP_ABI_VERSION = BY_KEY["clientstep"].abi[1]
 CLIENTADAM_ABI_VERSION = DESCRIBED["clientadam"].abi[1]
+CLIENTLOOP_ABI_VERSION = EXTRA_BY_KEY["clientloop"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -217,6 +239,10 @@ _BINDING = {
     "clientstep": ((CLIENTSTEP_SIGNATURES,), "CLIENTSTEP_LIB_PATH", "_clientstep"),
     "clientadam": ((CLIENTADAM_SIGNATURES,), "CLIENTADAM_LIB_PATH", "_clientadam"),
 }
+# the same for the libraries of build.EXTRA_BY_KEY (a new one goes here)
+_EXTRA_BINDING = {
+    "clientloop": ((CLIENTLOOP_SIGNATURES,), "CLIENTLOOP_LIB_PATH", "_clientloop"),
+}
 
 _lock = threading.Lock()
 _lib = None
@@ -226,6 +252,7 @@ _segvec = None
 _clientvec = None
 _clientstep = None
 _clientadam = None
+_clientloop = None
 
 
 def library_path() -> Path:
@@ -235,12 +262,12 @@ def library_path() -> Path:
 def _load(d: NativeLib) -> ctypes.CDLL:
     """Load (once), type and version-check the library ``d`` describes.  No
     fallback: a missing, unloadable or stale library raises ``FedAvgLibraryError``."""
-    tables, path_name, slot = _BINDING[d.key]
+    tables, path_name, slot = _BINDING[d.key] if d.key in _BINDING else _EXTRA_BINDING[d.key]
     g = globals()
     if g[slot] is not None:
         return g[slot]
     if d.needs:
-        _load(DESCRIBED[d.needs])
+        _load(DESCRIBED[d.needs] if d.needs in DESCRIBED else EXTRA_BY_KEY[d.needs])
     with _lock:
         if g[slot] is not None:
             return g[slot]
@@ -313,6 +340,11 @@ def load_clientadam() -> ctypes.CDLL:
     return _clientadam if _clientadam is not None else _load(DESCRIBED["clientadam"])
 
 
+def load_clientloop() -> ctypes.CDLL:
+    """The device-side guard and gated step library for fp32 / bf16 / fp64 models (include/fedavg_amd_clientloop.h)."""
+    return _clientloop if _clientloop is not None else _load(EXTRA_BY_KEY["clientloop"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
@@ -322,6 +354,11 @@ check_clientstep = functools.partial(_check, BY_KEY["clientstep"])
 def check_clientadam(rc: int, what: str) -> None:
     """``_check`` for the Adam step library (its description read at call time, as the loaders read theirs)."""
     _check(DESCRIBED["clientadam"], rc, what)
+
+
+def check_clientloop(rc: int, what: str) -> None:
+    """``_check`` for the guard and gated step library (its description read at call time)."""
+    _check(EXTRA_BY_KEY["clientloop"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

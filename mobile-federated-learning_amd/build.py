@@ -6,11 +6,14 @@
 ``up_to_date()`` over exactly those.  ``LATER_LIBS`` is the sixth and
 ``ALL_LIBS = LIBS + LATER_LIBS`` / ``BY_KEY`` the six, pinned in turn by
 tests/test_clientstep_abi.py.  A library added since is described with the
-same dataclass in ``NEWER_LIBS`` (a new one goes there), and ``EVERY_LIB =
-ALL_LIBS + NEWER_LIBS`` / ``DESCRIBED`` (by key) is what ``sources()``, the
-up-to-date rule and ``build()`` cover and what ``_lib`` loads from.
+same dataclass in ``NEWER_LIBS``, and ``EVERY_LIB = ALL_LIBS + NEWER_LIBS`` /
+``DESCRIBED`` (by key) are the seven that tests/test_clientadam_abi.py pins.
+The eighth, and any after it, is described in ``EXTRA_LIBS`` / ``EXTRA_BY_KEY``
+(a new one goes there), and ``BUILT_LIBS = EVERY_LIB + EXTRA_LIBS`` is what
+``sources()``, the up-to-date rule and ``build()`` cover; ``_lib`` loads a
+library from the by-key table that holds it.
 
-Every translation unit of ``EVERY_LIB`` is compiled in parallel with hipcc for
+Every translation unit of ``BUILT_LIBS`` is compiled in parallel with hipcc for
 ``--offload-arch=gfx950`` and each library is linked into ``lib/`` inside the
 package (in-tree, so the built libraries travel with the repo snapshot to the
 GPU box).  ``-ffp-contract=off`` keeps every multiply and add separately
@@ -121,6 +124,16 @@ DESCRIBED = {lib.key: lib for lib in EVERY_LIB}
 LIB_PATH, PROBE_LIB_PATH, FUSEDVEC_LIB_PATH, SEGVEC_LIB_PATH, CLIENTVEC_LIB_PATH = (lib.path for lib in LIBS)
 CLIENTSTEP_LIB_PATH = BY_KEY["clientstep"].path
 CLIENTADAM_LIB_PATH = DESCRIBED["clientadam"].path
+# libraries added after those seven (a new one goes here: see the module docstring)
+EXTRA_LIBS = (
+    # the :71 guard on the device and the SGD / Adam steps behind its gate, fp32 / bf16 / fp64; calls no other library
+    NativeLib("clientloop", "libfedavg_amd_clientloop.so", "fedavg_amd_clientloop.h", ("fedavg_client_loop.hip",),
+              abi=("fedavg_clientloop_abi_version", 1), last_error="fedavg_clientloop_last_error",
+              no_fallback="; there is no fallback for the device-side client guard and the gated steps"),
+)
+EXTRA_BY_KEY = {lib.key: lib for lib in EXTRA_LIBS}
+BUILT_LIBS = EVERY_LIB + EXTRA_LIBS
+CLIENTLOOP_LIB_PATH = EXTRA_BY_KEY["clientloop"].path
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",
@@ -148,7 +161,7 @@ def hipcc_path() -> str:
 def sources():
     """Everything a library can depend on: every translation unit, every
     header in csrc/ and include/ (found, not listed) and this recipe."""
-    units = dict.fromkeys(src for lib in EVERY_LIB for src in lib.sources)
+    units = dict.fromkeys(src for lib in BUILT_LIBS for src in lib.sources)
     return [*units, *sorted(CSRC_DIR.glob("*.hpp")), *sorted(INCLUDE.glob("*.h")), Path(__file__)]
 
 
@@ -158,9 +171,11 @@ def up_to_date() -> bool:
 
 
 def later_up_to_date() -> bool:
-    """The same rule for ``LATER_LIBS`` and ``NEWER_LIBS``: each built and no older than the newest source."""
+    """The same rule for ``LATER_LIBS``, ``NEWER_LIBS`` and ``EXTRA_LIBS``: each built and no older than the newest
+    source."""
     newest = max(p.stat().st_mtime for p in sources())
-    return all(lib.path.exists() and lib.path.stat().st_mtime >= newest for lib in LATER_LIBS + NEWER_LIBS)
+    return all(lib.path.exists() and lib.path.stat().st_mtime >= newest
+               for lib in LATER_LIBS + NEWER_LIBS + EXTRA_LIBS)
 
 
 def collect_ext_path() -> Path:
@@ -215,14 +230,15 @@ def _link(objs, lib_path, verbose, extra=()):
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Build every library of ``EVERY_LIB``; returns the product library's path."""
+    """Build every library of ``BUILT_LIBS``; returns the product library's path."""
     if not force and up_to_date() and later_up_to_date():
         return LIB_PATH
-    for lib in EVERY_LIB:
+    for lib in BUILT_LIBS:
         (LIB_DIR / lib.obj_dir).mkdir(parents=True, exist_ok=True)
-    _compile_all([(CSRC_DIR / u, lib.obj(u), list(lib.defines)) for lib in EVERY_LIB for u in lib.units], verbose)
-    for lib in EVERY_LIB:  # in order: a library links after the one its link arguments name
-        objs = [lib.obj(u) for u in lib.units] + [DESCRIBED[key].obj(u) for key, u in lib.reuse]
+    _compile_all([(CSRC_DIR / u, lib.obj(u), list(lib.defines)) for lib in BUILT_LIBS for u in lib.units], verbose)
+    by_key = {**DESCRIBED, **EXTRA_BY_KEY}
+    for lib in BUILT_LIBS:  # in order: a library links after the one its link arguments name
+        objs = [lib.obj(u) for u in lib.units] + [by_key[key].obj(u) for key, u in lib.reuse]
         _link(objs, lib.path, verbose, extra=lib.link)
     return LIB_PATH
 

@@ -47,6 +47,12 @@ where torch's multi-tensor Adam makes nine launches.  Four of its operations
 have the shape ``x + s * y``; which of them torch's kernels fuse is found by
 :func:`adam_form`, once per (device, dtype).
 
+``guard="device"`` (opt in, with fused stepping) removes the one sync per
+iteration that is left: the :71 guard is decided on the device and the step is
+gated on it (``libfedavg_amd_clientloop.so``: ``fedavg_client_guard_*``,
+``fedavg_client_{sgd,adam}_step_gated_*``), so the host queues iterations
+without waiting and reads ONE record at the end of ``train``.
+
 :func:`client_train` is ``Client.train`` written against this class and
 :func:`patch` binds it to a ``Client`` class (opt in; ``install()`` does not).
 """
@@ -67,8 +73,13 @@ _VEC_DTYPES = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float64: "f64
 FUSED_DTYPES = (torch.float32, *_VEC_DTYPES)
 _RULE = "contiguous parameters on one GPU, all of one dtype among fp32, bf16, fp16 and fp64"
 
-# rec: one device record of doubles, read back in one D2H
-_W, _G, _STATE, _LOSS, _REC = 0, 4, 8, 12, 16
+# rec: one device record of doubles, read back in one D2H.  The device guard adds the previous loss, the gate and
+# the epoch of the first trip (include/fedavg_amd_clientloop.h: loss = rec[_LOSS:_LOSS + 2], gate = rec[_GATE:_GATE + 2])
+_W, _G, _STATE, _LOSS, _LAST, _GATE, _EPOCH, _REC = 0, 4, 8, 12, 13, 14, 15, 16
+# guard="device": how many iterations the host may queue before it waits for the oldest one's record
+DEFAULT_AHEAD = 1
+_GUARD_RULE = ("fused stepping (step='fused', or 'auto' where it applies): the step is gated on the device, which "
+               "optimizer.step() cannot be")
 
 
 def _fused_ok(params) -> bool:
@@ -152,19 +163,28 @@ class _StepPass:
             self.dev_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=device)
         self._free = None    # event: the stream has passed the last use of host_ws
         self._staged = None  # the pointer tables host_ws holds
+        self._gated = None
 
-    def launch(self, w_ptrs, g_ptrs, lr, form, stats_ptr, st):
+    def launch(self, w_ptrs, g_ptrs, lr, form, stats_ptr, st, gated=None):
         """w -= lr * g over the tensors at w_ptrs / g_ptrs on torch stream
-        ``st``; the record goes to the 4 device doubles at ``stats_ptr``."""
+        ``st``; the record goes to the 4 device doubles at ``stats_ptr``.
+        ``gated``: the device addresses ``(g_stats, gate, state, loss)`` of
+        ``fedavg_client_sgd_step_gated_*``, which then takes the call."""
         table = w_ptrs.tobytes() + g_ptrs.tobytes()
         if self._free is not None and table != self._staged:
             self._free.synchronize()  # host_ws gets new bytes below (already passed after an iteration's sync)
         self._staged = table
+        fn, name, check, more = self.fn, self.name, _lib.check_clientstep, ()
+        if gated is not None:
+            if self._gated is None:
+                self._gated = self.name.replace("_step_", "_step_gated_")
+                self._gated = (getattr(_lib.load_clientloop(), self._gated), self._gated)
+            (fn, name), check, more = self._gated, _lib.check_clientloop, gated
         with torch.cuda.device(self.device):
-            rc = self.fn(w_ptrs.ctypes.data, g_ptrs.ctypes.data, self.numel.ctypes.data, len(self.numel), float(lr),
-                         form, self.partials.data_ptr(), self.partials.numel(), stats_ptr, self.host_ws.data_ptr(),
-                         self.dev_ws.data_ptr(), self.host_ws.numel(), st.cuda_stream)
-            _lib.check_clientstep(rc, self.name)
+            rc = fn(w_ptrs.ctypes.data, g_ptrs.ctypes.data, self.numel.ctypes.data, len(self.numel), float(lr),
+                    form, self.partials.data_ptr(), self.partials.numel(), stats_ptr, self.host_ws.data_ptr(),
+                    self.dev_ws.data_ptr(), self.host_ws.numel(), st.cuda_stream, *more)
+            check(rc, name)
             if self._free is None:
                 self._free = torch.cuda.Event()
             self._free.record(st)
@@ -312,22 +332,30 @@ class _AdamPass:
             self.dev_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=device)
         self._free = None    # event: the stream has passed the last use of host_ws
         self._staged = None  # the pointer tables host_ws holds
+        self._gated = None
 
     def plane(self, i):
         """Plane i (0 ``m``, 1 ``v``, 2 ``vmax``) as a view of the state."""
         return self.state[i * self.state_elems:(i + 1) * self.state_elems]
 
-    def launch(self, w_ptrs, g_ptrs, coef, first, form, stats_ptr, st):
+    def launch(self, w_ptrs, g_ptrs, coef, first, form, stats_ptr, st, gated=None):
+        """``gated``: as ``_StepPass.launch``'s (``fedavg_client_adam_step_gated_*``)."""
         table = w_ptrs.tobytes() + g_ptrs.tobytes()
         if self._free is not None and table != self._staged:
             self._free.synchronize()  # host_ws gets new bytes below (already passed after an iteration's sync)
         self._staged = table
+        fn, name, check, more = self.fn, self.name, _lib.check_clientadam, ()
+        if gated is not None:
+            if self._gated is None:
+                self._gated = self.name.replace("_step_", "_step_gated_")
+                self._gated = (getattr(_lib.load_clientloop(), self._gated), self._gated)
+            (fn, name), check, more = self._gated, _lib.check_clientloop, gated
         with torch.cuda.device(self.device):
-            rc = self.fn(w_ptrs.ctypes.data, g_ptrs.ctypes.data, self.numel.ctypes.data, self.offset.ctypes.data,
-                         len(self.numel), self.state.data_ptr(), self.state_elems, coef.ctypes.data, int(bool(first)),
-                         form, self.partials.data_ptr(), self.partials.numel(), stats_ptr, self.host_ws.data_ptr(),
-                         self.dev_ws.data_ptr(), self.host_ws.numel(), st.cuda_stream)
-            _lib.check_clientadam(rc, self.name)
+            rc = fn(w_ptrs.ctypes.data, g_ptrs.ctypes.data, self.numel.ctypes.data, self.offset.ctypes.data,
+                    len(self.numel), self.state.data_ptr(), self.state_elems, coef.ctypes.data, int(bool(first)),
+                    form, self.partials.data_ptr(), self.partials.numel(), stats_ptr, self.host_ws.data_ptr(),
+                    self.dev_ws.data_ptr(), self.host_ws.numel(), st.cuda_stream, *more)
+            check(rc, name)
             if self._free is None:
                 self._free = torch.cuda.Event()
             self._free.record(st)
@@ -518,10 +546,31 @@ class ClientStepStats:
     parameter that does not require grad, ``beta1 <= 0.5`` or a dtype without
     a form from :func:`adam_form` are a ``TypeError`` under ``"fused"`` and
     torch under ``"auto"``.
+
+    ``guard="device"`` (opt in; the default ``"host"`` is everything above, to
+    the bit) decides :71 on the device (``libfedavg_amd_clientloop.so``) and
+    gates the fused step on that decision, so an iteration is
+    ``guarded_step()`` alone, with no host sync: it queues the gradient pass,
+    the guard, the gated step (whose finalize also tracks rho / beta) and an
+    asynchronous copy of the record into a pinned ring of ``ahead`` slots.
+    ``poll()`` reads whichever slots have arrived, never blocking, and
+    ``finish()`` is the one sync of the whole loop.  It needs fused stepping
+    (``TypeError`` otherwise; ``guard="auto"`` falls back to ``"host"``);
+    ``guard_mode`` says which one the object got.  A tripped guard leaves the
+    parameters and the optimizer state exactly as the host guard does (no
+    gated launch writes once the gate is set), but the host may have queued up
+    to ``ahead`` more forward / backward passes before it noticed: module
+    buffers (BatchNorm running statistics) and the RNG stream dropout draws
+    from can be ahead of the reference's.  ``trace`` receives ``loss=None``.
     """
 
-    def __init__(self, params, *, stream=None, stats="auto", trace=None, step="torch", optimizer="sgd", adam=None):
+    def __init__(self, params, *, stream=None, stats="auto", trace=None, step="torch", optimizer="sgd", adam=None,
+                 guard="host", ahead=None):
         self.params = list(params)
+        if guard not in ("host", "device", "auto"):
+            raise ValueError(f"guard must be 'host', 'device' or 'auto', not {guard!r}")
+        if ahead is not None and (int(ahead) != ahead or ahead < 1):
+            raise ValueError(f"ahead must be a positive integer, not {ahead!r}")
         if optimizer not in ("sgd", "adam"):
             raise ValueError(f"optimizer must be 'sgd' or 'adam', not {optimizer!r}")
         self.optimizer = optimizer
@@ -562,8 +611,36 @@ class ClientStepStats:
                 self._step = _AdamPass(self._numel, self._offset, self.P, self.dtype, self.device)
             elif step == "fused":
                 raise TypeError(f"step='fused' needs {_ADAM_RULE}")
+        self.guard_mode = "host"
+        if guard != "host":
+            if self.step_mode == "fused":
+                self.guard_mode = "device"
+                self._init_device_guard(DEFAULT_AHEAD if ahead is None else int(ahead))
+            elif guard == "device":
+                raise TypeError(f"guard='device' needs {_GUARD_RULE}")
 
     # ------------------------------------------------------------------ fused
+    def _init_device_guard(self, ahead):
+        lib = _lib.load_clientloop()
+        self._guard_name = f"fedavg_client_guard_{_STEP_SUFFIX[self.dtype]}"
+        self._guard_fn = getattr(lib, self._guard_name)
+        self.ahead = ahead
+        with torch.cuda.device(self.device):
+            self._ring = torch.zeros(ahead, _REC, dtype=torch.float64, pin_memory=True)
+        self._ring_np = self._ring.numpy()
+        self._ring_ev = [None] * ahead
+        self._issued = 0      # guarded_step() calls so far: the next epoch
+        self._seen = 0        # ring records read so far, in order
+        self._trip = None     # the epoch of the first trip a record showed
+        self.ring_waits = 0   # times a full ring made guarded_step() wait for its oldest record
+
+    def _see(self, i):
+        """Read the arrived record of iteration i."""
+        rec = self._ring_np[i % self.ahead]
+        if self._trip is None and rec[_GATE] != 0.0:
+            self._trip = int(rec[_EPOCH])
+        self._seen = i + 1
+
     def _init_hip(self):
         self.device = self.params[0].device
         self.dtype = dt = self.params[0].dtype
@@ -665,7 +742,17 @@ class ClientStepStats:
 
     def begin(self, loss=None):
         """client.py:52-57: the first snapshots of the weights and, after the
-        caller's first backward, of the gradients."""
+        caller's first backward, of the gradients.  Under the device guard
+        ``loss`` is the prologue's loss TENSOR, copied into the record on the
+        stream (no ``.item()``)."""
+        if self.guard_mode == "device":
+            if not torch.is_tensor(loss):
+                raise TypeError("begin() under guard='device' takes the prologue's loss tensor: the record keeps it "
+                                "on the device as the first last_loss")
+            st = self._torch_stream()
+            with torch.cuda.stream(st), torch.no_grad():
+                self._rec[_LAST:_LAST + 1].copy_(loss.detach().reshape(1))
+            loss = None
         if self.mode == "hip":
             self._pass("w", 0)
             self._pass("g", 0)
@@ -679,6 +766,9 @@ class ClientStepStats:
         """client.py:69-71: the gradient pass and the guard.  ``True`` when the
         reference would give up: a NaN in the gradients, a NaN loss, or
         ``norm(grads) > lr * ratio * norm(last_w)``."""
+        if self.guard_mode == "device":
+            raise RuntimeError("after_backward() on an object built with guard='device': guarded_step() takes the "
+                               "guard, the step and the bookkeeping of the iteration")
         if not self._begun:
             raise RuntimeError("begin() first")
         if self.mode == "hip":
@@ -743,6 +833,8 @@ class ClientStepStats:
                                f"this one steps with torch ({self.step_mode=})")
         if self.optimizer != "sgd":
             raise RuntimeError("sgd_step() on an object built with optimizer='adam': adam_step() takes its step")
+        if self.guard_mode == "device":
+            raise RuntimeError("sgd_step() on an object built with guard='device': guarded_step() takes its step")
         if not self._begun:
             raise RuntimeError("begin() first")
         st = self._torch_stream()
@@ -765,6 +857,8 @@ class ClientStepStats:
                                f"this one steps with torch ({self.step_mode=})")
         if self.optimizer != "adam":
             raise RuntimeError("adam_step() on an object built with optimizer='sgd': sgd_step() takes its step")
+        if self.guard_mode == "device":
+            raise RuntimeError("adam_step() on an object built with guard='device': guarded_step() takes its step")
         if not self._begun:
             raise RuntimeError("begin() first")
         st = self._torch_stream()
@@ -779,6 +873,81 @@ class ClientStepStats:
         self._check(rc, self._track_name)
         self._emit("after_step", loss)
 
+    # ------------------------------------------------------------ device guard
+    def _need_device_guard(self, what):
+        if self.guard_mode != "device":
+            raise RuntimeError(f"{what} needs an object built with guard='device' (or 'auto' where it applies): "
+                               f"this one decides the guard on the host ({self.guard_mode=})")
+
+    def guarded_step(self, loss_tensor, lr, ratio):
+        """client.py:69-86 of one iteration, queued on the stream with no host
+        sync: the gradient pass, the loss into the record, the :71 guard on
+        the device, the step behind its gate (the finalize also tracks rho /
+        beta and moves ``loss`` to ``last_loss``) and a copy of the record
+        into slot ``i % ahead`` of the pinned ring.  With the ring full it
+        first waits for the oldest record alone, so the host is never more
+        than ``ahead`` iterations in front."""
+        self._need_device_guard("guarded_step()")
+        if not self._begun:
+            raise RuntimeError("begin() first")
+        i, slot = self._issued, self._issued % self.ahead
+        if i - self._seen >= self.ahead:  # the slot's last record (iteration i - ahead) has not been read
+            self._ring_ev[slot].synchronize()
+            self.ring_waits += 1
+            self._see(i - self.ahead)
+        st = self._torch_stream()
+        self._pass("g", 1)
+        with torch.cuda.stream(st), torch.no_grad():
+            self._rec[_LOSS:_LOSS + 1].copy_(loss_tensor.detach().reshape(1))
+        self._emit("after_backward", None)
+        base = self._rec.data_ptr()
+        with torch.cuda.device(self.device):
+            rc = self._guard_fn(base + 8 * _G, base + 8 * _W, base + 8 * _LOSS, base + 8 * _GATE, float(lr * ratio), i,
+                                st.cuda_stream)
+        _lib.check_clientloop(rc, self._guard_name)
+        gated = (base + 8 * _G, base + 8 * _GATE, base + 8 * _STATE, base + 8 * _LOSS)
+        if self.optimizer == "sgd":
+            self._step.launch(self._ptrs["w"], self._grad_ptrs(), lr, self._form, base + 8 * _W, st, gated=gated)
+        else:
+            h = self.adam
+            self._t += 1  # past a trip the count runs on, and no gated launch reads the state it counts for
+            coef = adam_coef(h["lr"], *h["betas"], h["eps"], h["weight_decay"], self._t)
+            self._step.launch(self._ptrs["w"], self._grad_ptrs(), coef, self._t == 1, self._form, base + 8 * _W, st,
+                              gated=gated)
+        torch.autograd.graph.increment_version(self.params)  # the in-place update autograd did not see
+        with torch.cuda.stream(st):
+            self._ring[slot].copy_(self._rec, non_blocking=True)
+            if self._ring_ev[slot] is None:
+                self._ring_ev[slot] = torch.cuda.Event()
+            self._ring_ev[slot].record(st)
+        self._issued = i + 1
+        self._emit("after_step", None)
+
+    def poll(self):
+        """The epoch of the first trip among the records that have arrived,
+        else ``None``.  Never blocks: ``event.query()`` on the ring slots not
+        yet read, in order."""
+        self._need_device_guard("poll()")
+        while self._seen < self._issued and self._ring_ev[self._seen % self.ahead].query():
+            self._see(self._seen)
+        return self._trip
+
+    def finish(self):
+        """The one sync of the loop: ``(trip_epoch_or_None, loss, beta, rho)``
+        from the record as the stream leaves it.  ``loss`` is the last
+        iteration's; ``None`` before any ``guarded_step()`` and after a trip
+        (iterations queued behind the tripping one have overwritten its slot,
+        and the reference returns none either)."""
+        self._need_device_guard("finish()")
+        rec = self._read_record()
+        self._seen = self._issued
+        if rec[_GATE] != 0.0:
+            self._trip = int(rec[_EPOCH])
+        self.loss = float(rec[_LOSS]) if self._issued and self._trip is None else None
+        rho = float(rec[_STATE]) if rec[_STATE + 2] else None
+        beta = float(rec[_STATE + 1]) if rec[_STATE + 3] else None
+        return self._trip, self.loss, beta, rho
+
     def result(self):
         """``(beta, rho)`` as Python floats (``None`` where no step was taken)."""
         if self.mode == "hip":
@@ -790,7 +959,8 @@ class ClientStepStats:
                 None if self._rho is None else self._rho.item())
 
 
-def client_train(self, net, local_iteration, *, keep_on_device=False, stats="auto", trace=None, step="torch"):
+def client_train(self, net, local_iteration, *, keep_on_device=False, stats="auto", trace=None, step="torch",
+                 guard="host"):
     """``Client.train(self, net, local_iteration)`` (client.py:38-96) with the
     bookkeeping of :52-86 done by :class:`ClientStepStats`.
 
@@ -806,6 +976,12 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
     amsgrad): with fused stepping one ``adam_step()`` per iteration and no
     torch optimizer at all; where the fused Adam step does not apply it is a
     ``TypeError`` under ``"fused"`` and steps with torch under ``"auto"``.
+    ``guard`` is :class:`ClientStepStats`'s: under the device guard an
+    iteration is forward, backward and ``guarded_step()``, the loop leaves as
+    soon as ``poll()`` shows a trip and ``finish()`` after it is the one host
+    sync of the bookkeeping.  The return values are the host guard's to the
+    bit; after a trip the parameters are too, while module buffers and the
+    RNG stream may be up to ``ahead`` iterations further (see the class).
     """
     mod = sys.modules[type(self).__module__]
     count, count_end, ratio = mod.count, mod.count_end, mod.THRESHOLD_GRADS_RATIO
@@ -814,7 +990,7 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
     if not sgd and step != "torch":  # refused, if it is, before anything runs
         try:
             tracker = ClientStepStats(net.parameters(), stats=stats, trace=trace, step=step, optimizer="adam",
-                                      adam=dict(lr=self.args.lr, weight_decay=self.args.wd, amsgrad=True))
+                                      adam=dict(lr=self.args.lr, weight_decay=self.args.wd, amsgrad=True), guard=guard)
         except TypeError as e:
             raise TypeError(f"{e}; args.client_optimizer is {self.args.client_optimizer!r}") from None
     if sgd:
@@ -827,14 +1003,41 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
     x, labels = x.to(self.device), labels.to(self.device)
     net.train()
     if tracker is None:
-        tracker = ClientStepStats(net.parameters(), stats=stats, trace=trace, step=step if sgd else "torch")
+        tracker = ClientStepStats(net.parameters(), stats=stats, trace=trace, step=step if sgd else "torch",
+                                  guard=guard)
     fused = tracker.step_mode == "fused"
     last_loss = self.criterion(net(x), labels)
     torch.nn.utils.clip_grad_norm_(net.parameters(), self.args.clip)
     last_loss.backward()
+    done = lambda: net.state_dict() if keep_on_device else net.cpu().state_dict()  # noqa: E731
+
+    def gave_up(epoch):
+        logger = getattr(mod, "logger", None)
+        if logger is not None:
+            logger.warning("grads too large than weights or meets nan with epoch {}".format(epoch))
+        return done(), None, None, None, None, None
+
+    if tracker.guard_mode == "device":
+        tracker.begin(last_loss.detach())
+        for epoch in range(local_iteration):
+            start = count()
+            net.zero_grad()
+            log_probs = net(x)
+            loss = self.criterion(log_probs, labels)
+            torch.nn.utils.clip_grad_norm_(net.parameters(), self.args.clip)
+            loss.backward()
+            cycles.append(count_end() - start)
+            tracker.guarded_step(loss, self.args.lr, ratio)
+            if tracker.poll() is not None:
+                break
+        trip, loss, beta, rho = tracker.finish()
+        if trip is not None:
+            return gave_up(trip)
+        _, predicted = torch.max(log_probs, -1)
+        correct = predicted.eq(labels).sum()
+        return done(), loss, beta, rho, correct.item() / labels.size(0), sum(cycles) / len(cycles)
     last_loss = last_loss.item()
     tracker.begin(last_loss)
-    done = lambda: net.state_dict() if keep_on_device else net.cpu().state_dict()  # noqa: E731
     for epoch in range(local_iteration):
         start = count()
         net.zero_grad()
@@ -844,10 +1047,7 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
         loss.backward()
         cycles.append(count_end() - start)
         if tracker.after_backward(loss, self.args.lr, ratio):
-            logger = getattr(mod, "logger", None)
-            if logger is not None:
-                logger.warning("grads too large than weights or meets nan with epoch {}".format(epoch))
-            return done(), None, None, None, None, None
+            return gave_up(epoch)
         loss = tracker.loss
         if fused and sgd:
             tracker.sgd_step(self.args.lr, loss, last_loss)
@@ -886,14 +1086,15 @@ class _Patch:
         return False
 
 
-def patch(cls, *, keep_on_device=False, stats="auto", step="torch"):
+def patch(cls, *, keep_on_device=False, stats="auto", step="torch", guard="host"):
     """Replace ``cls.train`` (the reference's ``Client.train``) with
     :func:`client_train`; returns a handle whose ``undo()`` restores the class."""
     had = "train" in vars(cls)
     old = vars(cls).get("train")
 
     def train(self, net, local_iteration):
-        return client_train(self, net, local_iteration, keep_on_device=keep_on_device, stats=stats, step=step)
+        return client_train(self, net, local_iteration, keep_on_device=keep_on_device, stats=stats, step=step,
+                            guard=guard)
 
     train.__wrapped_by__ = "mfl_amd.client_stats"
     setattr(cls, "train", train)

@@ -1,8 +1,10 @@
-// client_pass.hpp -- the one pass behind the three client libraries' kernels:
-// the statistics of fp32 models (fedavg_client.hip), of bf16 / fp16 / fp64
-// models (fedavg_client_vec.hip) and the SGD step fused with the weight
-// statistics (fedavg_client_step.hip).  Each of those files keeps its dtype
-// rules, its __global__ entry points and its C ABI; the pass is here, once.
+// client_pass.hpp -- the one pass behind the client libraries' kernels: the
+// statistics of fp32 models (fedavg_client.hip), of bf16 / fp16 / fp64 models
+// (fedavg_client_vec.hip), the SGD and Adam steps fused with the weight
+// statistics (fedavg_client_step.hip, fedavg_client_adam.hip) and their gated
+// forms (fedavg_client_loop.hip).  Each of those files keeps its __global__
+// entry points and its C ABI; the pass is here, once, and the steps' dtype
+// rules are in client_step_rules.hpp / client_adam_rules.hpp, once.
 //
 // The host stages a table of 32 B per key (client_pass_plan.hpp) and launches
 // one workgroup of 256 threads per unit of 16 KiB of a tensor.  The workgroup
@@ -50,6 +52,9 @@ struct CliSlice {
 };
 
 __device__ __forceinline__ CliSlice cli_slice(u32x4 v) { return CliSlice{{v.x, v.y, v.z, v.w}}; }
+
+// acc += x^2 in fp64, one rounding
+__device__ __forceinline__ void add_sq(double& acc, double x) { acc = __builtin_fma(x, x, acc); }
 
 // The element of ES bytes, how many a slice holds, element <-> slice (put
 // into a zeroed slice).  A dtype rule derives from one of these.
@@ -264,6 +269,55 @@ __device__ __forceinline__ void track_update(double* __restrict__ x, double* __r
 }
 
 // ---------------------------------------------------------------------------
+// The scalar arithmetic of a model's type T on values held in doubles: rt(x)
+// is rT(x) of an fp32 opmath result, as ATen casts it (fp32: x itself).  fp64
+// models compute in fp64 and never call it.
+// ---------------------------------------------------------------------------
+struct CliOpF32 {
+  static constexpr bool kF64 = false;
+  __device__ static double rt(float x) { return static_cast<double>(x); }
+};
+
+template <class R>  // BF16Pk / F16Pk
+struct CliOpHalf {
+  static constexpr bool kF64 = false;
+  __device__ static double rt(float x) { return static_cast<double>(R::unpack(R::pack(opaque2(f32x2{x, 0.f}))).x); }
+};
+
+struct CliOpF64 {
+  static constexpr bool kF64 = true;
+  __device__ static double rt(float x) { return static_cast<double>(x); }
+};
+
+// client.py:78-84 on the device in the model's type; `state` = {rho, beta,
+// has rho, has beta} holds values of T exactly.  Every fp32 operation is
+// formed in fp64 from fp32 operands and rounded once to fp32 (for sqrt, a
+// quotient and a product of fp32 values that is the correctly rounded fp32
+// result, 53 >= 2 * 24 + 2), then rounded to T as ATen casts its opmath
+// result.  fp64 models: the same operations in fp64.  One thread calls it.
+template <class Op>
+__device__ __forceinline__ void cli_track(double* state, const double* w_stats, const double* g_stats,
+                                          double abs_dloss) {
+  double rho_tmp, beta_tmp;
+  if constexpr (Op::kF64) {
+    const double n_w = __builtin_sqrt(w_stats[2]);  // norm(w - last_w)
+    const double n_g = __builtin_sqrt(g_stats[2]);  // norm(grads - last_grads)
+    const double recip = 1.0 / n_w;
+    rho_tmp = recip * abs_dloss;
+    beta_tmp = n_g / n_w;
+  } else {
+    const double n_w = Op::rt(static_cast<float>(__builtin_sqrt(w_stats[2])));
+    const double n_g = Op::rt(static_cast<float>(__builtin_sqrt(g_stats[2])));
+    const double recip = Op::rt(static_cast<float>(1.0 / n_w));
+    const double dl = static_cast<double>(static_cast<float>(abs_dloss));
+    rho_tmp = Op::rt(static_cast<float>(recip * dl));
+    beta_tmp = Op::rt(static_cast<float>(n_g / n_w));
+  }
+  track_update(state + 0, state + 2, rho_tmp);
+  track_update(state + 1, state + 3, beta_tmp);
+}
+
+// ---------------------------------------------------------------------------
 // The host side.  Hidden: no library exports these or binds to another's copy.
 // ---------------------------------------------------------------------------
 #pragma GCC visibility push(hidden)
@@ -324,10 +378,10 @@ inline int check_tensors(const ClientLib& lib, const char* what, const int64_t* 
   return FEDAVG_OK;
 }
 
-// the one H2D of the staged table, pass(), the library's finalize
-template <class Pass>
-int stage_and_launch(const ClientLib& lib, const char* what, const void* host_ws, void* dev_ws, int64_t ws_bytes,
-                     double* partials, int64_t units, double* stats, hipStream_t s, Pass pass) {
+// the one H2D of the staged table, pass(), then fin(): the launch that adds the partials up
+template <class Pass, class Fin>
+int stage_then(const ClientLib& lib, const char* what, const void* host_ws, void* dev_ws, int64_t ws_bytes,
+               hipStream_t s, Pass pass, Fin fin) {
   const hipError_t e = hipMemcpyAsync(dev_ws, host_ws, static_cast<size_t>(ws_bytes), hipMemcpyHostToDevice, s);
   if (e != hipSuccess) {
     (void)hipGetLastError();
@@ -336,8 +390,17 @@ int stage_and_launch(const ClientLib& lib, const char* what, const void* host_ws
   pass();
   const int rc = lib.launched(what);
   if (rc) return rc;
-  hipLaunchKernelGGL(lib.finalize, dim3(1), dim3(kBlock), 0, s, partials, units, stats);
+  fin();
   return lib.launched(what);
+}
+
+// the same with the library's own finalize
+template <class Pass>
+int stage_and_launch(const ClientLib& lib, const char* what, const void* host_ws, void* dev_ws, int64_t ws_bytes,
+                     double* partials, int64_t units, double* stats, hipStream_t s, Pass pass) {
+  return stage_then(lib, what, host_ws, dev_ws, ws_bytes, s, pass, [&] {
+    hipLaunchKernelGGL(lib.finalize, dim3(1), dim3(kBlock), 0, s, partials, units, stats);
+  });
 }
 
 // A statistics entry point of rule T; kernels[has_snap] is the library's pass.

@@ -108,21 +108,12 @@ __global__ __launch_bounds__(kBlock) void client_stats_finalize_kernel(const dou
   cli_finalize(partials, units, stats);
 }
 
-// client.py:78-84 on the device.  Every fp32 operation is formed in fp64 from
-// fp32 operands and rounded once to fp32: for sqrt, a quotient and a product
-// of fp32 values that is the correctly rounded fp32 result (53 >= 2 * 24 + 2).
-// The state holds fp32 values in doubles and is compared in fp32.
+// client.py:78-84 on the device (client_pass.hpp's cli_track in fp32).  The
+// state holds fp32 values in doubles.
 __global__ __launch_bounds__(64) void client_track_kernel(double* __restrict__ state, const double* __restrict__ w_stats,
                                                           const double* __restrict__ g_stats, double abs_dloss) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const float n_w = static_cast<float>(__builtin_sqrt(w_stats[2]));  // norm(w - last_w)
-  const float n_g = static_cast<float>(__builtin_sqrt(g_stats[2]));  // norm(grads - last_grads)
-  const float recip = static_cast<float>(1.0 / static_cast<double>(n_w));
-  const float dl = static_cast<float>(abs_dloss);
-  const float rho_tmp = static_cast<float>(static_cast<double>(recip) * static_cast<double>(dl));
-  const float beta_tmp = static_cast<float>(static_cast<double>(n_g) / static_cast<double>(n_w));
-  track_update(state + 0, state + 2, rho_tmp);
-  track_update(state + 1, state + 3, beta_tmp);
+  cli_track<CliOpF32>(state, w_stats, g_stats, abs_dloss);
 }
 
 int bad_tensor(const char* what, int64_t key, int64_t) {

@@ -37,7 +37,7 @@ int cv_launch_status(const char* what) { return launch_status(g_cv_err, what); }
 // bf16 / fp16; R = BF16Pk / F16Pk (common.hpp): two elements per 32-bit word
 template <class R>
 struct CvHalf : CliElem<2> {
-  static constexpr bool kF64 = false;
+  typedef CliOpHalf<R> scalar;
   template <bool HAS>
   __device__ static void add(const CliSlice& c, const CliSlice& s, int& nans, double& a_cur, double& a_d) {
 #pragma unroll
@@ -56,12 +56,10 @@ struct CvHalf : CliElem<2> {
       }
     }
   }
-  // rT(x) as a double
-  __device__ static double rt(float x) { return static_cast<double>(R::unpack(R::pack(opaque2(f32x2{x, 0.f}))).x); }
 };
 
 struct CvF64 : CliElem<8> {
-  static constexpr bool kF64 = true;
+  typedef CliOpF64 scalar;
   template <bool HAS>
   __device__ static void add(const CliSlice& c, const CliSlice& s, int& nans, double& a_cur, double& a_d) {
 #pragma unroll
@@ -89,33 +87,13 @@ __global__ __launch_bounds__(kBlock) void clientvec_finalize_kernel(const double
   cli_finalize(partials, units, stats);
 }
 
-// client.py:78-84 on the device in the model's type; `state` holds values of
-// T exactly.  Every fp32 operation is formed in fp64 from fp32 operands and
-// rounded once to fp32 (for sqrt, a quotient and a product of fp32 values that
-// is the correctly rounded fp32 result, 53 >= 2 * 24 + 2), then rounded to T
-// as ATen casts its opmath result.  fp64 models: the same operations in fp64.
+// client.py:78-84 on the device in the model's type (client_pass.hpp's cli_track)
 template <class T>
 __global__ __launch_bounds__(64) void clientvec_track_kernel(double* __restrict__ state,
                                                              const double* __restrict__ w_stats,
                                                              const double* __restrict__ g_stats, double abs_dloss) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double rho_tmp, beta_tmp;
-  if constexpr (T::kF64) {
-    const double n_w = __builtin_sqrt(w_stats[2]);  // norm(w - last_w)
-    const double n_g = __builtin_sqrt(g_stats[2]);  // norm(grads - last_grads)
-    const double recip = 1.0 / n_w;
-    rho_tmp = recip * abs_dloss;
-    beta_tmp = n_g / n_w;
-  } else {
-    const double n_w = T::rt(static_cast<float>(__builtin_sqrt(w_stats[2])));
-    const double n_g = T::rt(static_cast<float>(__builtin_sqrt(g_stats[2])));
-    const double recip = T::rt(static_cast<float>(1.0 / n_w));
-    const double dl = static_cast<double>(static_cast<float>(abs_dloss));
-    rho_tmp = T::rt(static_cast<float>(recip * dl));
-    beta_tmp = T::rt(static_cast<float>(n_g / n_w));
-  }
-  track_update(state + 0, state + 2, rho_tmp);
-  track_update(state + 1, state + 3, beta_tmp);
+  cli_track<typename T::scalar>(state, w_stats, g_stats, abs_dloss);
 }
 
 int bad_tensor(const char* what, int64_t key, int64_t elem_size) {
