@@ -15,6 +15,8 @@ Layers:
   multi                    one process, N GPUs: host rounds by columns over N PCIe links
   fpf                      FPF2 bookkeeping (local_w_diffs / A_mat / G_mat) in HBM
   client_stats             Client.train's rho / beta / guard statistics, one fused pass per step
+  client_passes            its native calls' buffers and the reuse rule of their pinned key tables
+  client_forms             the probes behind sgd_form / adam_form, once per (device, dtype)
 """
 from ._lib import FedAvgLibraryError, library_path
 from .aggregate import (

@@ -55,6 +55,8 @@ without waiting and reads ONE record at the end of ``train``.
 
 :func:`client_train` is ``Client.train`` written against this class and
 :func:`patch` binds it to a ``Client`` class (opt in; ``install()`` does not).
+The native calls' buffers and their reuse rule are :mod:`client_passes`'s, the
+probes behind :func:`sgd_form` and :func:`adam_form` :mod:`client_forms`'s.
 """
 from __future__ import annotations
 
@@ -65,13 +67,9 @@ import numpy as np
 import torch
 
 from . import _lib
-
-ALIGN = 4  # fp32 snapshot key offsets are multiples of 4 elements (16 B)
-
-# dtype -> (entry suffix, numpy type of the snapshot's bits); fp32 is the product library's
-_VEC_DTYPES = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float64: "f64"}
-FUSED_DTYPES = (torch.float32, *_VEC_DTYPES)
-_RULE = "contiguous parameters on one GPU, all of one dtype among fp32, bf16, fp16 and fp64"
+from .client_forms import _ADAM_PROBE, _mine_site_c, _probe_adam_form, _probe_sgd_form, _probe_values  # noqa: F401
+from .client_passes import (ADAM_SITES, FUSED_DTYPES, _RULE, _STEP_SUFFIX, _AdamPass, _KeyPass,  # noqa: F401
+                            _STATS_LIBS, _StepPass, _fused_ok, _guard_bound, _norm_of, _round_to, adam_coef)
 
 # rec: one device record of doubles, read back in one D2H.  The device guard adds the previous loss, the gate and
 # the epoch of the first trip (include/fedavg_amd_clientloop.h: loss = rec[_LOSS:_LOSS + 2], gate = rec[_GATE:_GATE + 2])
@@ -82,179 +80,36 @@ _GUARD_RULE = ("fused stepping (step='fused', or 'auto' where it applies): the s
                "optimizer.step() cannot be")
 
 
-def _fused_ok(params) -> bool:
-    return bool(params) and all(p.is_cuda and p.is_contiguous() for p in params) and \
-        len({p.device for p in params}) == 1 and len({p.dtype for p in params}) == 1 and \
-        params[0].dtype in FUSED_DTYPES
-
-
-def _round_to(x, dtype):
-    """rT(fl32(x)) as a Python float: x rounded to fp32, then to ``dtype``
-    (nearest even both times), as ATen casts an opmath result.  fp64: x."""
-    if dtype == torch.float64:
-        return float(x)
-    with np.errstate(all="ignore"):
-        f = np.float32(x)
-        if dtype == torch.float32:
-            return float(f)
-        if dtype == torch.float16:
-            return float(np.float16(f))
-    if math.isnan(f):
-        return math.nan
-    u = int(f.view(np.uint32))
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000  # bf16: the upper half of the fp32 word
-    return float(np.uint32(u).view(np.float32))
-
-
-def _norm_of(sumsq, dtype):
-    """norm(S) = rT(fl32(sqrt(S))) (fp64: sqrt(S)): the exactly rounded value
-    of what ATen's norm approximates in opmath."""
-    if math.isnan(sumsq):
-        return math.nan
-    return _round_to(math.sqrt(sumsq), dtype)
-
-
-def _guard_bound(n_w, lr_ratio, dtype):
-    """``lr * ratio * norm(last_w)`` (:71): python_float * tensor, the scalar
-    rounded to opmath, the product to the tensor's type."""
-    if dtype == torch.float64:
-        return n_w * lr_ratio
-    with np.errstate(all="ignore"):
-        # the fp64 product of two fp32 values is exact: one rounding to fp32
-        return _round_to(np.float64(n_w) * np.float64(np.float32(lr_ratio)), dtype)
-
-
 # ------------------------------------------------------------------ fused step
 # The dtypes the fused step is offered for: those sgd_form() found a form for on the MI355X (torch 2.10 / ROCm 7.0:
 # form 1 for fp32, bf16 and fp64).  Not fp16: there torch's kernel rounds fma(alpha, g, w) ONCE, to fp16 (a
 # mixed-precision fma), while both forms round to fp32 first; on sgd_form's probe form 1 differs from torch on 2 of
 # 571 elements, form 0 on 61 (DESIGN.md §3).  fedavg_client_sgd_step_f16 stays in the C ABI; nothing here calls it.
 STEP_DTYPES = (torch.float32, torch.bfloat16, torch.float64)
-_STEP_SUFFIX = {torch.float32: "f32", **_VEC_DTYPES}
 _STEP_RULE = (f"the fused statistics ({_RULE}), fp32, bf16 or fp64 parameters, a plain SGD step (client_optimizer "
               "'sgd': no momentum, no weight decay) and a form of the step kernel that leaves torch.optim.SGD's bits "
               "on this GPU (sgd_form)")
-_BITS = {2: torch.int16, 4: torch.int32, 8: torch.int64}
-_PROBE_LR = 0.03
-_PROBE_N = 512
-_PROBE_POOL = 1 << 21
-_probes = {}  # (device index, dtype) -> the probe's findings
+_probes = {}  # (device index, dtype) -> the SGD probe's findings
+_adam_probes = {}  # the same for the Adam probe
 
 
-class _StepPass:
-    """The buffers of ``fedavg_client_sgd_step_*`` calls over tensors of
-    ``numel`` elements, and the call.  The pinned key table is reused under
-    ``ClientStepStats._pass``'s rule: new bytes only after the stream has
-    passed the last call that shipped the old ones."""
-
-    def __init__(self, numel, dtype, device):
-        self.lib = _lib.load_clientstep()
-        self.name = f"fedavg_client_sgd_step_{_STEP_SUFFIX[dtype]}"
-        self.fn = getattr(self.lib, self.name)
-        self.device = device
-        self.numel = np.ascontiguousarray(numel, dtype=np.int64)
-        n = len(self.numel)
-        es = torch.empty(0, dtype=dtype).element_size()
-        nparts = int(self.lib.fedavg_client_step_partials(self.numel.ctypes.data, n, es))
-        ws = int(self.lib.fedavg_client_step_workspace(n))
-        with torch.cuda.device(device):
-            self.partials = torch.empty(max(nparts, 1), dtype=torch.float64, device=device)
-            self.host_ws = torch.empty(max(ws, 16), dtype=torch.uint8, pin_memory=True)
-            self.dev_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=device)
-        self._free = None    # event: the stream has passed the last use of host_ws
-        self._staged = None  # the pointer tables host_ws holds
-        self._gated = None
-
-    def launch(self, w_ptrs, g_ptrs, lr, form, stats_ptr, st, gated=None):
-        """w -= lr * g over the tensors at w_ptrs / g_ptrs on torch stream
-        ``st``; the record goes to the 4 device doubles at ``stats_ptr``.
-        ``gated``: the device addresses ``(g_stats, gate, state, loss)`` of
-        ``fedavg_client_sgd_step_gated_*``, which then takes the call."""
-        table = w_ptrs.tobytes() + g_ptrs.tobytes()
-        if self._free is not None and table != self._staged:
-            self._free.synchronize()  # host_ws gets new bytes below (already passed after an iteration's sync)
-        self._staged = table
-        fn, name, check, more = self.fn, self.name, _lib.check_clientstep, ()
-        if gated is not None:
-            if self._gated is None:
-                self._gated = self.name.replace("_step_", "_step_gated_")
-                self._gated = (getattr(_lib.load_clientloop(), self._gated), self._gated)
-            (fn, name), check, more = self._gated, _lib.check_clientloop, gated
-        with torch.cuda.device(self.device):
-            rc = fn(w_ptrs.ctypes.data, g_ptrs.ctypes.data, self.numel.ctypes.data, len(self.numel), float(lr),
-                    form, self.partials.data_ptr(), self.partials.numel(), stats_ptr, self.host_ws.data_ptr(),
-                    self.dev_ws.data_ptr(), self.host_ws.numel(), st.cuda_stream, *more)
-            check(rc, name)
-            if self._free is None:
-                self._free = torch.cuda.Event()
-            self._free.record(st)
-
-
-def _probe_values(dtype):
-    """Seeded model-like weights N(0, 0.05^2) and gradients N(0, 1) of type
-    ``dtype`` for the probe.  In fp32 and fp64 the two forms differ on about
-    every third random element.  In a 16-bit type they differ only where the
-    fp32 results lie on either side of a rounding boundary of the type (one
-    element in tens of thousands), so the first _PROBE_N values of a larger
-    seeded pool are joined by those of its elements at which a host
-    computation of the two forms differs; whether they differ on the device
-    is sgd_form's own check."""
-    wide = dtype in (torch.float32, torch.float64)
-    rng = np.random.default_rng(20250)
-    n = _PROBE_N if wide else _PROBE_POOL
-    w = torch.from_numpy(rng.normal(0.0, 0.05, n)).to(dtype)
-    g = torch.from_numpy(rng.normal(0.0, 1.0, n)).to(dtype)
-    if wide:
-        return w, g
-    wf, gf = w.float().numpy(), g.float().numpy()
-    alpha = np.float32(-_PROBE_LR)
-    with np.errstate(all="ignore"):
-        apart = torch.from_numpy(wf + alpha * gf).to(dtype)  # two fp32 roundings, then the type's
-        once = torch.from_numpy((wf.astype(np.float64) + np.float64(alpha) * gf.astype(np.float64))
-                                .astype(np.float32)).to(dtype)  # the product is exact in fp64
-    picked = torch.nonzero(apart.view(torch.int16) != once.view(torch.int16)).view(-1).numpy()[:_PROBE_N]
-    idx = torch.from_numpy(np.union1d(np.arange(_PROBE_N), picked))
-    return w[idx].clone(), g[idx].clone()
-
-
-def _probe_sgd_form(device, dtype):
-    w, g = _probe_values(dtype)
-    bits = _BITS[w.element_size()]
-    with torch.cuda.device(device):
-        w, g = w.to(device), g.to(device)
-        p = torch.nn.Parameter(w.clone())
-        p.grad = g.clone()
-        torch.optim.SGD([p], lr=_PROBE_LR).step()
-        want = p.detach().view(bits)
-        step = _StepPass([w.numel()], dtype, device)
-        rec = torch.empty(4, dtype=torch.float64, device=device)
-        st = torch.cuda.current_stream(device)
-        got = []
-        for form in (0, 1):
-            c = w.clone()
-            step.launch(np.array([c.data_ptr()], dtype=np.int64), np.array([g.data_ptr()], dtype=np.int64),
-                        _PROBE_LR, form, rec.data_ptr(), st)
-            got.append(c.view(bits))
-        differ = int((got[0] != got[1]).sum())
-        match = tuple(bool(torch.equal(c, want)) for c in got)
-    form = None
-    if differ:  # equal outputs would say nothing about which one torch computes
-        form = 0 if match[0] else 1 if match[1] else None
-    return {"form": form, "differ": differ, "match": match, "n": int(w.numel())}
+def _cached_probe(what, cache, probe, device, dtype):
+    """``probe(device, dtype)``'s findings, from ``cache`` after the first call for a (device index, dtype)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TypeError(f"{what} needs a GPU, not {device}")
+    index = torch.cuda.current_device() if device.index is None else device.index
+    key = (index, dtype)
+    if key not in cache:
+        cache[key] = probe(torch.device("cuda", index), dtype)
+    return cache[key]
 
 
 def sgd_form_probe(device, dtype):
     """What :func:`sgd_form` found for (device, dtype), cached: ``form``, the
     number of probe elements on which the kernel's two forms ``differ``,
     ``match`` (form 0 / form 1 equal to torch on every element) and ``n``."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise TypeError(f"sgd_form needs a GPU, not {device}")
-    index = torch.cuda.current_device() if device.index is None else device.index
-    key = (index, dtype)
-    if key not in _probes:
-        _probes[key] = _probe_sgd_form(torch.device("cuda", index), dtype)
-    return _probes[key]
+    return _cached_probe("sgd_form", _probes, _probe_sgd_form, device, dtype)
 
 
 def sgd_form(device, dtype):
@@ -270,7 +125,7 @@ def sgd_form(device, dtype):
 
 # ------------------------------------------------------------------ fused Adam step
 # The dtypes the fused Adam step is offered for.  Two findings on the MI355X (torch 2.10 / ROCm 7.0) decide it: the
-# probe below finds one mask that equals torch (mask 15, all four sites one fma, for fp32, bf16, fp16 and fp64), AND
+# probe of client_forms.py finds one mask that equals torch (mask 15, all four sites one fma, for all four dtypes), AND
 # the kernel under that mask equals torch.optim.Adam bit for bit over twelve-step chains at the reference's own
 # hyperparameters and three other sets, down to subnormal second moments (tests/test_gpu_client_adam_torch.py;
 # DESIGN.md §3).  fp16 passes the first and fails the second: torch's fp16 kernels round g + wd * w, v * beta2,
@@ -283,198 +138,9 @@ def sgd_form(device, dtype):
 # this tuple adam_form() answers None without probing; adam_form_probe() still runs the probe and reports what it
 # finds (for fp16: mask 15), which says that the mask matches torch on the probe's values and no more.
 ADAM_DTYPES = (torch.float32, torch.bfloat16, torch.float64)
-ADAM_SITES = 4  # A g + wd w, B the lerp, C the addcmul, E the addcdiv: bit i of a form mask fuses site i
 _ADAM_RULE = (f"the fused statistics ({_RULE}), a dtype of ADAM_DTYPES (fp32, bf16, fp64), torch.optim.Adam with "
               "amsgrad=True and beta1 > 0.5 over parameters that all require grad, and a form of the Adam step kernel that leaves "
               "torch.optim.Adam's bits on this GPU (adam_form)")
-# The form is a property of torch's compiled kernels, not of the hyperparameters, so the probe picks hyperparameters
-# and values at which both terms of every site are of one magnitude (w, g ~ N(0, 1)): there two forms of a site leave
-# different fp32 bits on about every third element.  At the reference's own (wd = 0.001 against g ~ 1) they hardly
-# ever do.
-_ADAM_PROBE = dict(lr=0.3, betas=(0.6, 0.7), eps=1e-8, weight_decay=0.3)
-_ADAM_PROBE_STEPS = 3
-_adam_probes = {}  # (device index, dtype) -> the probe's findings
-
-
-def adam_coef(lr, beta1, beta2, eps, weight_decay, t):
-    """The seven coefficients of ``fedavg_client_adam_step_*`` for step ``t``
-    (from 1), in Python floats exactly as torch/optim/adam.py forms them."""
-    t = float(t)
-    bias_correction1 = 1 - beta1 ** t
-    bias_correction2 = 1 - beta2 ** t
-    step_size = (lr / bias_correction1) * -1
-    return np.array([weight_decay, 1 - beta1, beta2, 1 - beta2, bias_correction2 ** 0.5, eps, step_size],
-                    dtype=np.float64)
-
-
-class _AdamPass:
-    """The optimizer state (three planes ``m, v, vmax`` of ``state_elems``
-    elements in one zeroed buffer, key j at ``offset[j]``), the buffers of
-    ``fedavg_client_adam_step_*`` calls and the call.  The pinned key table is
-    reused under ``_StepPass``'s rule."""
-
-    def __init__(self, numel, offset, state_elems, dtype, device):
-        self.lib = _lib.load_clientadam()
-        self.name = f"fedavg_client_adam_step_{_STEP_SUFFIX[dtype]}"
-        self.fn = getattr(self.lib, self.name)
-        self.device = device
-        self.numel = np.ascontiguousarray(numel, dtype=np.int64)
-        self.offset = np.ascontiguousarray(offset, dtype=np.int64)
-        n = len(self.numel)
-        es = torch.empty(0, dtype=dtype).element_size()
-        self.state_elems = int(state_elems)
-        nparts = int(self.lib.fedavg_client_adam_partials(self.numel.ctypes.data, n, es))
-        ws = int(self.lib.fedavg_client_adam_workspace(n))
-        with torch.cuda.device(device):
-            self.state = torch.zeros(3 * max(self.state_elems, 16 // es), dtype=dtype, device=device)
-            self.partials = torch.empty(max(nparts, 1), dtype=torch.float64, device=device)
-            self.host_ws = torch.empty(max(ws, 16), dtype=torch.uint8, pin_memory=True)
-            self.dev_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=device)
-        self._free = None    # event: the stream has passed the last use of host_ws
-        self._staged = None  # the pointer tables host_ws holds
-        self._gated = None
-
-    def plane(self, i):
-        """Plane i (0 ``m``, 1 ``v``, 2 ``vmax``) as a view of the state."""
-        return self.state[i * self.state_elems:(i + 1) * self.state_elems]
-
-    def launch(self, w_ptrs, g_ptrs, coef, first, form, stats_ptr, st, gated=None):
-        """``gated``: as ``_StepPass.launch``'s (``fedavg_client_adam_step_gated_*``)."""
-        table = w_ptrs.tobytes() + g_ptrs.tobytes()
-        if self._free is not None and table != self._staged:
-            self._free.synchronize()  # host_ws gets new bytes below (already passed after an iteration's sync)
-        self._staged = table
-        fn, name, check, more = self.fn, self.name, _lib.check_clientadam, ()
-        if gated is not None:
-            if self._gated is None:
-                self._gated = self.name.replace("_step_", "_step_gated_")
-                self._gated = (getattr(_lib.load_clientloop(), self._gated), self._gated)
-            (fn, name), check, more = self._gated, _lib.check_clientloop, gated
-        with torch.cuda.device(self.device):
-            rc = fn(w_ptrs.ctypes.data, g_ptrs.ctypes.data, self.numel.ctypes.data, self.offset.ctypes.data,
-                    len(self.numel), self.state.data_ptr(), self.state_elems, coef.ctypes.data, int(bool(first)),
-                    form, self.partials.data_ptr(), self.partials.numel(), stats_ptr, self.host_ws.data_ptr(),
-                    self.dev_ws.data_ptr(), self.host_ws.numel(), st.cuda_stream, *more)
-            check(rc, name)
-            if self._free is None:
-                self._free = torch.cuda.Event()
-            self._free.record(st)
-
-
-def _adam_probe_values(dtype):
-    """Seeded weights and gradients N(0, 1), the pool of 2^21: in a 16-bit
-    type the two forms of site A, B or E leave different bits on tens to
-    hundreds of its elements."""
-    rng = np.random.default_rng(20251)
-    return (torch.from_numpy(rng.normal(0.0, 1.0, _PROBE_POOL)).to(dtype),
-            torch.from_numpy(rng.normal(0.0, 1.0, _PROBE_POOL)).to(dtype))
-
-
-def _mine_site_c(dtype, most=64):
-    """``(beta2, g, v)`` for a 16-bit ``dtype`` on which site C's two forms,
-    ``v' = rT(v1 + value * g^2)`` with ``v1 = rT(v * beta2)`` and ``value = 1
-    - beta2``, store different bits: a Python float, one gradient value and up
-    to ``most`` second moments.
-
-    Random values never reach this site in a 16-bit type.  Both terms are
-    non-negative and ``v1`` is a value of the type, so the forms part only
-    when ``fl32(value * g^2)`` is inexact and lies half an fp32 ulp of the
-    sum from a rounding boundary of the type: its low 24 - p bits are all
-    ones with the exact product below it, or 0...01 with it above (p the
-    type's precision).  That is a property of ``(value, g)`` alone, one pair
-    in 2^(25 - p); a seeded search over ``value`` in (0.2, 0.4) and ``g ~ N(0,
-    1)`` finds such pairs, and for one of them every ``v`` of the type in
-    [2^-6, 16) is tried.  The forms are computed here in fp64 (the product
-    exact, the sum rounded once more): a filter, as in ``_probe_values``;
-    whether they differ on the device is adam_form's own check."""
-    prec = {torch.float16: 11, torch.bfloat16: 8}[dtype]
-    rng = np.random.default_rng(20253)
-    n = 1 << 21
-    value = rng.uniform(0.2, 0.4, n).astype(np.float32)
-    g = torch.from_numpy(rng.normal(0.0, 1.0, n)).to(dtype).float().numpy()
-    exact = value.astype(np.float64) * (g * g).astype(np.float64)  # g * g is exact in fp32 for a 16-bit g
-    with np.errstate(all="ignore"):
-        c = exact.astype(np.float32)
-    low = c.view(np.uint32) & np.uint32((1 << (24 - prec)) - 1)
-    cand = np.flatnonzero(((low == (1 << (24 - prec)) - 1) & (exact < c)) | ((low == 1) & (exact > c)))
-    every = torch.arange(0, 1 << 15, dtype=torch.int16).view(dtype).float().numpy()
-    every = every[(every >= 2.0 ** -6) & (every < 16.0)]
-    to_type = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dtype).float().numpy()  # noqa: E731
-    for i in cand:
-        beta2 = 1.0 - float(value[i])
-        if np.float32(1.0 - beta2) != value[i]:
-            continue
-        with np.errstate(all="ignore"):
-            v1 = to_type(every * np.float32(beta2))
-            apart = to_type(v1 + c[i])
-            once = to_type((v1.astype(np.float64) + exact[i]).astype(np.float32))
-        hit = np.flatnonzero(apart != once)[:most]
-        if len(hit):
-            return beta2, torch.tensor(float(g[i]), dtype=dtype), torch.from_numpy(every[hit]).to(dtype)
-    raise RuntimeError(f"no pair found for site C in {dtype}")
-
-
-def _probe_adam_form(device, dtype):
-    h = dict(_ADAM_PROBE)
-    w, g = _adam_probe_values(dtype)
-    mined = None
-    if dtype in (torch.float16, torch.bfloat16):
-        # the last elements of the probe are site C's: w = 0 (so g1 = g), and before step 2 their v and vmax are
-        # set to the mined second moments, in torch's state and in the kernel's alike
-        beta2, g_c, v_c = _mine_site_c(dtype)
-        h["betas"] = (h["betas"][0], beta2)
-        mined = slice(w.numel() - v_c.numel(), w.numel())
-        w[mined] = 0.0
-    bits = _BITS[w.element_size()]
-    n = w.numel()
-    with torch.cuda.device(device):
-        w, g = w.to(device), g.to(device)
-        grads = [torch.roll(g, 7 * t) for t in range(_ADAM_PROBE_STEPS)]  # another gradient every step
-        if mined is not None:
-            v_c = v_c.to(device)
-            grads[1][mined] = g_c.to(device)
-
-        def inject(w_t, v_t, vmax_t):
-            w_t[mined] = 0.0
-            v_t[mined] = v_c
-            vmax_t[mined] = v_c
-
-        p = torch.nn.Parameter(w.clone())
-        opt = torch.optim.Adam([p], lr=h["lr"], betas=h["betas"], eps=h["eps"], weight_decay=h["weight_decay"],
-                               amsgrad=True)
-        want = []
-        for t in range(_ADAM_PROBE_STEPS):
-            if mined is not None and t == 1:
-                with torch.no_grad():
-                    inject(p, opt.state[p]["exp_avg_sq"], opt.state[p]["max_exp_avg_sq"])
-            p.grad = grads[t].clone()
-            opt.step()
-            state = opt.state[p]
-            want.append([x.detach().view(bits).clone() for x in
-                         (p, state["exp_avg"], state["exp_avg_sq"], state["max_exp_avg_sq"])])
-        rec = torch.empty(4, dtype=torch.float64, device=device)
-        st = torch.cuda.current_stream(device)
-        numel, offset = np.array([n], dtype=np.int64), np.zeros(1, dtype=np.int64)
-        step = _AdamPass(numel, offset, n, dtype, device)
-        off = []
-        for form in range(1 << ADAM_SITES):
-            c = w.clone()
-            differ = torch.zeros((), dtype=torch.int64, device=device)
-            for t in range(_ADAM_PROBE_STEPS):
-                if mined is not None and t == 1:
-                    inject(c, step.plane(1), step.plane(2))
-                coef = adam_coef(h["lr"], *h["betas"], h["eps"], h["weight_decay"], t + 1)
-                step.launch(np.array([c.data_ptr()], dtype=np.int64), np.array([grads[t].data_ptr()], dtype=np.int64),
-                            coef, t == 0, form, rec.data_ptr(), st)
-                for a, b in zip([c.view(bits)] + [step.plane(i).view(bits) for i in range(3)], want[t]):
-                    differ += (a != b).sum()
-            off.append(int(differ))  # the one read per mask
-    # two masks that both equal torch equal each other on the whole probe: it cannot tell them apart, and a mask that
-    # equals torch differs from every one that does not.  So the answer is the ONE mask at 0, if there is exactly one.
-    match = tuple(o == 0 for o in off)
-    form = match.index(True) if sum(match) == 1 else None
-    return {"form": form, "match": match, "off": tuple(off), "n": int(n), "steps": _ADAM_PROBE_STEPS,
-            "mined_site_c": 0 if mined is None else int(v_c.numel()), "betas": h["betas"]}
 
 
 def adam_form_probe(device, dtype):
@@ -482,14 +148,7 @@ def adam_form_probe(device, dtype):
     ``match`` (per mask: equal to torch on every element of ``p, exp_avg,
     exp_avg_sq, max_exp_avg_sq`` after each of ``steps`` steps), ``off`` (per
     mask: the number of elements that differ from torch's) and ``n``."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise TypeError(f"adam_form needs a GPU, not {device}")
-    index = torch.cuda.current_device() if device.index is None else device.index
-    key = (index, dtype)
-    if key not in _adam_probes:
-        _adam_probes[key] = _probe_adam_form(torch.device("cuda", index), dtype)
-    return _adam_probes[key]
+    return _cached_probe("adam_form", _adam_probes, _probe_adam_form, device, dtype)
 
 
 def adam_form(device, dtype):
@@ -644,40 +303,25 @@ class ClientStepStats:
     def _init_hip(self):
         self.device = self.params[0].device
         self.dtype = dt = self.params[0].dtype
-        es = self.params[0].element_size()
-        if dt == torch.float32:
-            self.lib, self._check = _lib.load(), lambda rc, what: _lib.check(rc, what, self.lib)
-            self._stats_name, self._track_name = "fedavg_client_stats_f32", "fedavg_client_track"
-        else:
-            self.lib, self._check = _lib.load_clientvec(), _lib.check_clientvec
-            self._stats_name = f"fedavg_client_stats_{_VEC_DTYPES[dt]}"
-            self._track_name = f"fedavg_client_track_{_VEC_DTYPES[dt]}"
-        self._stats_fn, self._track_fn = getattr(self.lib, self._stats_name), getattr(self.lib, self._track_name)
-        ALIGN = 16 // es  # snapshot key offsets are multiples of 16 B
-        n = len(self.params)
+        align = 16 // self.params[0].element_size()  # snapshot key offsets are multiples of 16 B
         self._numel = np.array([p.numel() for p in self.params], dtype=np.int64)
-        padded = (self._numel + (ALIGN - 1)) // ALIGN * ALIGN
+        padded = (self._numel + (align - 1)) // align * align
         self._offset = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
         self.P = int(padded.sum())
         self._ptrs = {"w": np.array([p.data_ptr() for p in self.params], dtype=np.int64),
-                      "g": np.zeros(n, dtype=np.int64)}
+                      "g": np.zeros(len(self.params), dtype=np.int64)}
+        load, self._check, self._stats_name, self._track_name, sizing, by_size = _STATS_LIBS[dt]
+        lib = load()
+        self._stats_fn, self._track_fn = getattr(lib, self._stats_name), getattr(lib, self._track_name)
+        n = len(self.params)
+        more = (self.params[0].element_size(),) if by_size else ()
+        nparts = int(getattr(lib, sizing + "_partials")(self._numel.ctypes.data, n, *more))
+        ws_bytes = int(getattr(lib, sizing + "_workspace")(n))
+        self._passes = {k: _KeyPass(nparts, ws_bytes, self.device) for k in "wg"}
         with torch.cuda.device(self.device):
-            if dt == torch.float32:
-                nparts = int(self.lib.fedavg_client_stats_partials(self._numel.ctypes.data, n))
-                self._ws_bytes = int(self.lib.fedavg_client_stats_workspace(n))
-            else:
-                nparts = int(self.lib.fedavg_client_stats_vec_partials(self._numel.ctypes.data, n, es))
-                self._ws_bytes = int(self.lib.fedavg_client_stats_vec_workspace(n))
-            self._snap = {k: torch.zeros(max(self.P, ALIGN), dtype=dt, device=self.device) for k in "wg"}
-            self._partials = {k: torch.empty(max(nparts, 1), dtype=torch.float64, device=self.device) for k in "wg"}
-            self._host_ws = {k: torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, pin_memory=True) for k in "wg"}
-            self._dev_ws = {k: torch.empty(max(self._ws_bytes, 16), dtype=torch.uint8, device=self.device)
-                            for k in "wg"}
+            self._snap = {k: torch.zeros(max(self.P, align), dtype=dt, device=self.device) for k in "wg"}
             self._rec = torch.zeros(_REC, dtype=torch.float64, device=self.device)
             self._rec_host = torch.zeros(_REC, dtype=torch.float64, pin_memory=True)
-            self._ws_free = {k: None for k in "wg"}  # event: the stream has passed the last use of host_ws[k]
-            self._staged = {k: None for k in "wg"}   # the pointer table host_ws[k] holds
-        self._nparts = nparts
 
     def _torch_stream(self):
         return self.stream if self.stream is not None else torch.cuda.current_stream(self.device)
@@ -698,23 +342,23 @@ class ClientStepStats:
     def _pass(self, which: str, has_snap: int):
         """One fused pass over the weights ('w') or the gradients ('g') on the stream."""
         ptrs = self._ptrs["w"] if which == "w" else self._grad_ptrs()
-        st = self._torch_stream()
-        ev = self._ws_free[which]
-        table = ptrs.tobytes()
-        if ev is not None and table != self._staged[which]:
-            ev.synchronize()  # host_ws gets new bytes below (already passed after an iteration's sync)
-        self._staged[which] = table
+        self._passes[which].call(
+            self._stats_fn, self._stats_name, self._check, ptrs.tobytes(),
+            (ptrs.ctypes.data, self._numel.ctypes.data, self._offset.ctypes.data, len(self.params),
+             self._snap[which].data_ptr(), self.P, has_snap),
+            self._rec.data_ptr() + 8 * (_W if which == "w" else _G), self._torch_stream())
+
+    def _put_loss(self, slot, loss_tensor):
+        """``loss_tensor`` into ``rec[slot]`` on the stream (no ``.item()``)."""
+        with torch.cuda.stream(self._torch_stream()), torch.no_grad():
+            self._rec[slot:slot + 1].copy_(loss_tensor.detach().reshape(1))
+
+    def _track(self, loss, last_loss, st):
+        """client.py:78-84 on the device: rho / beta from the weight and gradient records."""
+        base = self._rec.data_ptr()
         with torch.cuda.device(self.device):
-            rc = self._stats_fn(
-                ptrs.ctypes.data, self._numel.ctypes.data, self._offset.ctypes.data, len(self.params),
-                self._snap[which].data_ptr(), self.P, has_snap, self._partials[which].data_ptr(),
-                self._partials[which].numel(), self._rec.data_ptr() + 8 * (_W if which == "w" else _G),
-                self._host_ws[which].data_ptr(), self._dev_ws[which].data_ptr(), self._host_ws[which].numel(),
-                st.cuda_stream)
-            self._check(rc, self._stats_name)
-            if ev is None:
-                ev = self._ws_free[which] = torch.cuda.Event()
-            ev.record(st)
+            rc = self._track_fn(base + 8 * _STATE, base + 8 * _W, base + 8 * _G, abs(loss - last_loss), st.cuda_stream)
+        self._check(rc, self._track_name)
 
     def _read_record(self):
         st = self._torch_stream()
@@ -749,9 +393,7 @@ class ClientStepStats:
             if not torch.is_tensor(loss):
                 raise TypeError("begin() under guard='device' takes the prologue's loss tensor: the record keeps it "
                                 "on the device as the first last_loss")
-            st = self._torch_stream()
-            with torch.cuda.stream(st), torch.no_grad():
-                self._rec[_LAST:_LAST + 1].copy_(loss.detach().reshape(1))
+            self._put_loss(_LAST, loss)
             loss = None
         if self.mode == "hip":
             self._pass("w", 0)
@@ -773,21 +415,13 @@ class ClientStepStats:
             raise RuntimeError("begin() first")
         if self.mode == "hip":
             self._pass("g", 1)
-            st = self._torch_stream()
-            with torch.cuda.stream(st), torch.no_grad():
-                self._rec[_LOSS:_LOSS + 1].copy_(loss_tensor.detach().reshape(1))
+            self._put_loss(_LOSS, loss_tensor)
             rec = self._read_record()
             self.loss = float(rec[_LOSS])
-            if self.dtype == torch.float32:
-                n_g = np.float32(math.sqrt(rec[_G + 1])) if not math.isnan(rec[_G + 1]) else np.float32("nan")
-                n_w = np.float32(math.sqrt(rec[_W + 1])) if not math.isnan(rec[_W + 1]) else np.float32("nan")
-                with np.errstate(all="ignore"):
-                    bound = np.float32(lr * ratio) * n_w  # python_float * fp32 tensor: the scalar rounded to fp32
-            else:
-                n_g, n_w = _norm_of(float(rec[_G + 1]), self.dtype), _norm_of(float(rec[_W + 1]), self.dtype)
-                bound = _guard_bound(n_w, lr * ratio, self.dtype)
-            self.grad_norm, self.weight_norm = float(n_g), float(n_w)
-            trip = bool(rec[_G] > 0 or math.isnan(self.loss) or n_g > bound)
+            # every dtype alike, as the device guard decides it (fp32: fl32(sqrt(S)) and fl32(lr * ratio) * n_w)
+            self.grad_norm = n_g = _norm_of(float(rec[_G + 1]), self.dtype)
+            self.weight_norm = n_w = _norm_of(float(rec[_W + 1]), self.dtype)
+            trip = bool(rec[_G] > 0 or math.isnan(self.loss) or n_g > _guard_bound(n_w, lr * ratio, self.dtype))
         else:
             with torch.no_grad():
                 grads = self._grads = self._flat(True)
@@ -806,11 +440,7 @@ class ClientStepStats:
                                "keeps no weight snapshot for this pass to compare with")
         if self.mode == "hip":
             self._pass("w", 1)
-            base = self._rec.data_ptr()
-            with torch.cuda.device(self.device):
-                rc = self._track_fn(base + 8 * _STATE, base + 8 * _W, base + 8 * _G, abs(loss - last_loss),
-                                    self._torch_stream().cuda_stream)
-            self._check(rc, self._track_name)
+            self._track(loss, last_loss, self._torch_stream())
         else:
             with torch.no_grad():
                 w = self._flat(False)
@@ -828,23 +458,7 @@ class ClientStepStats:
         ``after_step()``: ``w -= lr * g`` with torch.optim.SGD's bits, the
         weight record (``sum w'^2`` for the next guard, ``sum rT(w' - w)^2``
         for :78 / :82) and the running rho / beta.  No host sync."""
-        if self.step_mode != "fused":
-            raise RuntimeError("sgd_step() needs an object built with step='fused' (or 'auto' where it applies): "
-                               f"this one steps with torch ({self.step_mode=})")
-        if self.optimizer != "sgd":
-            raise RuntimeError("sgd_step() on an object built with optimizer='adam': adam_step() takes its step")
-        if self.guard_mode == "device":
-            raise RuntimeError("sgd_step() on an object built with guard='device': guarded_step() takes its step")
-        if not self._begun:
-            raise RuntimeError("begin() first")
-        st = self._torch_stream()
-        base = self._rec.data_ptr()
-        self._step.launch(self._ptrs["w"], self._grad_ptrs(), lr, self._form, base + 8 * _W, st)
-        torch.autograd.graph.increment_version(self.params)  # the in-place update autograd did not see
-        with torch.cuda.device(self.device):
-            rc = self._track_fn(base + 8 * _STATE, base + 8 * _W, base + 8 * _G, abs(loss - last_loss), st.cuda_stream)
-        self._check(rc, self._track_name)
-        self._emit("after_step", loss)
+        self._host_step("sgd", lr, loss, last_loss)
 
     def adam_step(self, loss, last_loss):
         """client.py:74-86 in one kernel, in place of ``optimizer.step()`` and
@@ -852,33 +466,45 @@ class ClientStepStats:
         and on the state this object owns, the weight record and the running
         rho / beta.  The first call of an object does not read the state.  No
         host sync."""
-        if self.step_mode != "fused":
-            raise RuntimeError("adam_step() needs an object built with step='fused' (or 'auto' where it applies): "
+        self._host_step("adam", None, loss, last_loss)
+
+    def _built_for(self, what, optimizer=None, begun=True):
+        """``what`` needs the fused ``optimizer`` step under the host guard or, with none named, the device guard."""
+        if optimizer is None and self.guard_mode != "device":
+            raise RuntimeError(f"{what} needs an object built with guard='device' (or 'auto' where it applies): "
+                               f"this one decides the guard on the host ({self.guard_mode=})")
+        if optimizer is not None and self.step_mode != "fused":
+            raise RuntimeError(f"{what} needs an object built with step='fused' (or 'auto' where it applies): "
                                f"this one steps with torch ({self.step_mode=})")
-        if self.optimizer != "adam":
-            raise RuntimeError("adam_step() on an object built with optimizer='sgd': sgd_step() takes its step")
-        if self.guard_mode == "device":
-            raise RuntimeError("adam_step() on an object built with guard='device': guarded_step() takes its step")
-        if not self._begun:
+        if optimizer is not None and self.optimizer != optimizer:
+            raise RuntimeError(f"{what} on an object built with optimizer='{self.optimizer}': {self.optimizer}_step() "
+                               "takes its step")
+        if optimizer is not None and self.guard_mode == "device":
+            raise RuntimeError(f"{what} on an object built with guard='device': guarded_step() takes its step")
+        if begun and not self._begun:
             raise RuntimeError("begin() first")
-        st = self._torch_stream()
-        base = self._rec.data_ptr()
-        h = self.adam
-        self._t += 1
-        coef = adam_coef(h["lr"], *h["betas"], h["eps"], h["weight_decay"], self._t)
-        self._step.launch(self._ptrs["w"], self._grad_ptrs(), coef, self._t == 1, self._form, base + 8 * _W, st)
+
+    def _launch_step(self, lr, st, gated=None):
+        """The object's fused step on ``st``: SGD with ``lr``, or Adam with its own hyperparameters and step
+        count; the record goes to ``rec[_W:]``.  ``gated``: the gated entry's four device addresses."""
+        stats_ptr = self._rec.data_ptr() + 8 * _W
+        if self.optimizer == "sgd":
+            self._step.launch(self._ptrs["w"], self._grad_ptrs(), lr, self._form, stats_ptr, st, gated)
+        else:
+            h = self.adam
+            self._t += 1  # past a trip the count runs on, and no gated launch reads the state it counts for
+            coef = adam_coef(h["lr"], *h["betas"], h["eps"], h["weight_decay"], self._t)
+            self._step.launch(self._ptrs["w"], self._grad_ptrs(), coef, self._t == 1, self._form, stats_ptr, st, gated)
         torch.autograd.graph.increment_version(self.params)  # the in-place update autograd did not see
-        with torch.cuda.device(self.device):
-            rc = self._track_fn(base + 8 * _STATE, base + 8 * _W, base + 8 * _G, abs(loss - last_loss), st.cuda_stream)
-        self._check(rc, self._track_name)
+
+    def _host_step(self, optimizer, lr, loss, last_loss):
+        self._built_for(f"{optimizer}_step()", optimizer)
+        st = self._torch_stream()
+        self._launch_step(lr, st)
+        self._track(loss, last_loss, st)
         self._emit("after_step", loss)
 
     # ------------------------------------------------------------ device guard
-    def _need_device_guard(self, what):
-        if self.guard_mode != "device":
-            raise RuntimeError(f"{what} needs an object built with guard='device' (or 'auto' where it applies): "
-                               f"this one decides the guard on the host ({self.guard_mode=})")
-
     def guarded_step(self, loss_tensor, lr, ratio):
         """client.py:69-86 of one iteration, queued on the stream with no host
         sync: the gradient pass, the loss into the record, the :71 guard on
@@ -887,9 +513,7 @@ class ClientStepStats:
         into slot ``i % ahead`` of the pinned ring.  With the ring full it
         first waits for the oldest record alone, so the host is never more
         than ``ahead`` iterations in front."""
-        self._need_device_guard("guarded_step()")
-        if not self._begun:
-            raise RuntimeError("begin() first")
+        self._built_for("guarded_step()")
         i, slot = self._issued, self._issued % self.ahead
         if i - self._seen >= self.ahead:  # the slot's last record (iteration i - ahead) has not been read
             self._ring_ev[slot].synchronize()
@@ -897,24 +521,14 @@ class ClientStepStats:
             self._see(i - self.ahead)
         st = self._torch_stream()
         self._pass("g", 1)
-        with torch.cuda.stream(st), torch.no_grad():
-            self._rec[_LOSS:_LOSS + 1].copy_(loss_tensor.detach().reshape(1))
+        self._put_loss(_LOSS, loss_tensor)
         self._emit("after_backward", None)
         base = self._rec.data_ptr()
         with torch.cuda.device(self.device):
             rc = self._guard_fn(base + 8 * _G, base + 8 * _W, base + 8 * _LOSS, base + 8 * _GATE, float(lr * ratio), i,
                                 st.cuda_stream)
         _lib.check_clientloop(rc, self._guard_name)
-        gated = (base + 8 * _G, base + 8 * _GATE, base + 8 * _STATE, base + 8 * _LOSS)
-        if self.optimizer == "sgd":
-            self._step.launch(self._ptrs["w"], self._grad_ptrs(), lr, self._form, base + 8 * _W, st, gated=gated)
-        else:
-            h = self.adam
-            self._t += 1  # past a trip the count runs on, and no gated launch reads the state it counts for
-            coef = adam_coef(h["lr"], *h["betas"], h["eps"], h["weight_decay"], self._t)
-            self._step.launch(self._ptrs["w"], self._grad_ptrs(), coef, self._t == 1, self._form, base + 8 * _W, st,
-                              gated=gated)
-        torch.autograd.graph.increment_version(self.params)  # the in-place update autograd did not see
+        self._launch_step(lr, st, (base + 8 * _G, base + 8 * _GATE, base + 8 * _STATE, base + 8 * _LOSS))
         with torch.cuda.stream(st):
             self._ring[slot].copy_(self._rec, non_blocking=True)
             if self._ring_ev[slot] is None:
@@ -927,7 +541,7 @@ class ClientStepStats:
         """The epoch of the first trip among the records that have arrived,
         else ``None``.  Never blocks: ``event.query()`` on the ring slots not
         yet read, in order."""
-        self._need_device_guard("poll()")
+        self._built_for("poll()", begun=False)
         while self._seen < self._issued and self._ring_ev[self._seen % self.ahead].query():
             self._see(self._seen)
         return self._trip
@@ -938,23 +552,24 @@ class ClientStepStats:
         iteration's; ``None`` before any ``guarded_step()`` and after a trip
         (iterations queued behind the tripping one have overwritten its slot,
         and the reference returns none either)."""
-        self._need_device_guard("finish()")
+        self._built_for("finish()", begun=False)
         rec = self._read_record()
         self._seen = self._issued
         if rec[_GATE] != 0.0:
             self._trip = int(rec[_EPOCH])
         self.loss = float(rec[_LOSS]) if self._issued and self._trip is None else None
-        rho = float(rec[_STATE]) if rec[_STATE + 2] else None
-        beta = float(rec[_STATE + 1]) if rec[_STATE + 3] else None
-        return self._trip, self.loss, beta, rho
+        return self._trip, self.loss, *self._beta_rho(rec)
+
+    @staticmethod
+    def _beta_rho(rec):
+        """``(beta, rho)`` of a record read back: ``rec[_STATE:]`` is ``rho, beta, has_rho, has_beta``."""
+        return (float(rec[_STATE + 1]) if rec[_STATE + 3] else None,
+                float(rec[_STATE]) if rec[_STATE + 2] else None)
 
     def result(self):
         """``(beta, rho)`` as Python floats (``None`` where no step was taken)."""
         if self.mode == "hip":
-            rec = self._read_record()
-            rho = float(rec[_STATE]) if rec[_STATE + 2] else None
-            beta = float(rec[_STATE + 1]) if rec[_STATE + 3] else None
-            return beta, rho
+            return self._beta_rho(self._read_record())
         return (None if self._beta is None else self._beta.item(),
                 None if self._rho is None else self._rho.item())
 
@@ -1017,26 +632,8 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
             logger.warning("grads too large than weights or meets nan with epoch {}".format(epoch))
         return done(), None, None, None, None, None
 
-    if tracker.guard_mode == "device":
-        tracker.begin(last_loss.detach())
-        for epoch in range(local_iteration):
-            start = count()
-            net.zero_grad()
-            log_probs = net(x)
-            loss = self.criterion(log_probs, labels)
-            torch.nn.utils.clip_grad_norm_(net.parameters(), self.args.clip)
-            loss.backward()
-            cycles.append(count_end() - start)
-            tracker.guarded_step(loss, self.args.lr, ratio)
-            if tracker.poll() is not None:
-                break
-        trip, loss, beta, rho = tracker.finish()
-        if trip is not None:
-            return gave_up(trip)
-        _, predicted = torch.max(log_probs, -1)
-        correct = predicted.eq(labels).sum()
-        return done(), loss, beta, rho, correct.item() / labels.size(0), sum(cycles) / len(cycles)
-    last_loss = last_loss.item()
+    device_guard = tracker.guard_mode == "device"
+    last_loss = last_loss.detach() if device_guard else last_loss.item()  # the device guard keeps it on the device
     tracker.begin(last_loss)
     for epoch in range(local_iteration):
         start = count()
@@ -1046,6 +643,11 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
         torch.nn.utils.clip_grad_norm_(net.parameters(), self.args.clip)
         loss.backward()
         cycles.append(count_end() - start)
+        if device_guard:
+            tracker.guarded_step(loss, self.args.lr, ratio)
+            if tracker.poll() is not None:
+                break
+            continue
         if tracker.after_backward(loss, self.args.lr, ratio):
             return gave_up(epoch)
         loss = tracker.loss
@@ -1057,10 +659,15 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
             optimizer.step()
             tracker.after_step(loss, last_loss)
         last_loss = loss
+    if device_guard:
+        trip, loss, beta, rho = tracker.finish()
+        if trip is not None:
+            return gave_up(trip)
     # local_iteration == 0 leaves log_probs unbound, as in the reference (:93)
     _, predicted = torch.max(log_probs, -1)
     correct = predicted.eq(labels).sum()
-    beta, rho = tracker.result()
+    if not device_guard:
+        beta, rho = tracker.result()
     return done(), loss, beta, rho, correct.item() / labels.size(0), sum(cycles) / len(cycles)
 
 

@@ -160,6 +160,57 @@ def test_host_rounding_equals_torch_cpu_casts(key):
     assert client_stats._norm_of(math.inf, dt) == math.inf
 
 
+_TIES = 600
+
+
+def _fp32_guard_sums():
+    """Sums of squares whose roots sit at the edges of fp32: zero, the
+    subnormal ends, the overflow end, inf and nan, then for _TIES seeded fp32
+    rounding midpoints m the sums (m (1 - 2^-40))^2 and (m (1 + 2^-40))^2,
+    whose roots lie either side of the tie, and m^2 with its two fp64
+    neighbours, whose fp64 roots may land on the tie itself."""
+    rng = np.random.default_rng(71)
+    f = (rng.uniform(1.0, 2.0, _TIES) * 2.0 ** rng.integers(-140, 127, _TIES)).astype(np.float32)
+    mid = (f.astype(np.float64) + np.nextafter(f, np.float32(np.inf)).astype(np.float64)) / 2  # exact in fp64
+    sq = mid * mid
+    return [0.0, 5e-324, 2.0 ** -149, 2.0 ** -126, 2.0 ** 127, 2.0 ** 128, 2.0 ** 256, 1e300, math.inf, math.nan,
+            *((mid * (1 - 2.0 ** -40)) ** 2).tolist(), *((mid * (1 + 2.0 ** -40)) ** 2).tolist(),
+            *np.nextafter(sq, 0.0).tolist(), *sq.tolist(), *np.nextafter(sq, np.inf).tolist()]
+
+
+def test_fp32_guard_terms_equal_the_inline_fp32_expressions_bit_for_bit():
+    """_norm_of / _guard_bound at fp32 against the expressions the fp32 guard
+    was written with (``np.float32(math.sqrt(s))``, NaN kept apart, and
+    ``np.float32(lr * ratio) * n_w``): equal bits, NaN matched as NaN, and the
+    same ``n_g > bound`` on the whole cross product.  No case is left out."""
+    dt = torch.float32
+    bits = lambda a: np.asarray(a, dtype=np.float32).view(np.uint32)  # noqa: E731
+    sums = _fp32_guard_sums()
+    lr_ratios = [0.0, 1e-30, 0.1, 1e10, 1e12 * 0.01, 1e39, math.inf]
+    with np.errstate(all="ignore"):
+        inline = np.array([np.float32(math.sqrt(s)) if not math.isnan(s) else np.float32("nan") for s in sums])
+        norms = np.array([client_stats._norm_of(s, dt) for s in sums])  # Python floats
+        assert np.array_equal(norms.astype(np.float32).astype(np.float64), norms, equal_nan=True)  # fp32 values
+        nan = np.isnan(inline)
+        assert np.array_equal(nan, np.isnan(norms)) and nan.sum() == 1
+        assert np.array_equal(bits(inline)[~nan], bits(norms)[~nan])
+        assert {0.0, math.inf} <= set(norms[~nan].tolist())
+        assert (norms[10:10 + _TIES] < norms[10 + _TIES:10 + 2 * _TIES]).all()  # the two sides of every tie part
+        inline_b = np.array([[np.float32(r) * n_w for n_w in inline] for r in lr_ratios])
+        bounds = np.array([[client_stats._guard_bound(float(n_w), r, dt) for n_w in norms] for r in lr_ratios])
+    nan_b = np.isnan(inline_b)
+    assert np.array_equal(nan_b, np.isnan(bounds)) and nan_b.any() and not nan_b.all()  # inf * 0, NaN norms
+    assert np.array_equal(bits(inline_b)[~nan_b], bits(bounds)[~nan_b])
+    assert np.isinf(bounds[~nan_b]).any() and (bounds[~nan_b] == 0.0).any()
+    flat_inline, flat = inline_b.reshape(-1), bounds.reshape(-1)
+    trips = 0
+    for n_inline, n in zip(inline, norms):  # n_g over every (lr * ratio, n_w)
+        want = n_inline > flat_inline
+        assert np.array_equal(want, n > flat)
+        trips += int(want.sum())
+    assert 0 < trips < len(sums) * flat.size
+
+
 def test_host_rounding_fp64_is_plain_fp64():
     dt = torch.float64
     assert client_stats._round_to(0.1, dt) == 0.1

@@ -334,3 +334,68 @@ def test_keep_on_device_feeds_the_device_round(dev):
     out = mfl_amd.aggregate(w_locals, device=dev)
     for k, v in out.items():
         assert v.is_cuda and bool(torch.isfinite(v).all()), k
+
+
+def _reuse_run(dev, w0, grads, fresh, optimizer, guard):
+    """Three iterations on a two-key model of 5 and 3 elements; ``fresh``: every
+    p.grad is a new tensor each time (the old ones kept alive, so the addresses
+    differ), else the values are copied into fixed grad tensors.  Returns the
+    weights, the record and, in the fresh run, the waits the reuse rule made."""
+    flat = torch.cat(w0)
+    params = [torch.nn.Parameter(flat[:5]), torch.nn.Parameter(flat[5:])]
+    assert params[1].data_ptr() % 16 == 4  # not 16-B aligned
+    kw = dict(optimizer="adam", adam=dict(lr=0.01, weight_decay=0.001)) if optimizer == "adam" else {}
+    t = mfl_amd.ClientStepStats(params, stats="hip", step="fused", guard=guard, ahead=1 if guard == "device" else None,
+                                **kw)
+    assert (t.step_mode, t.guard_mode, t._offset.tolist()) == ("fused", guard, [0, 8])  # the second offset is padded
+    kept, waits = [], []
+
+    def give(gs):
+        for p, g in zip(params, gs):
+            if fresh or p.grad is None:
+                kept.append(p.grad)
+                p.grad = g.clone()
+            else:
+                p.grad.copy_(g)
+        waits.append(t._passes["g"].stage(t._grad_ptrs().tobytes()))  # the pass below ships this very table
+        waits.append(t._passes["g"].stage(t._grad_ptrs().tobytes()))  # and the same addresses again never wait
+
+    losses = [torch.tensor(v, device=dev) for v in (2.5, 2.25, 1.75, 1.5)]
+    give(grads[0])
+    if guard == "device":
+        t.begin(losses[0])
+        for i in range(3):
+            give(grads[i + 1])
+            t.guarded_step(losses[i + 1], 0.05, 1000.0)
+        assert t.finish()[0] is None
+    else:
+        t.begin(2.5)
+        last = 2.5
+        for i in range(3):
+            give(grads[i + 1])
+            assert not t.after_backward(losses[i + 1], 0.05, 1000.0)
+            t.adam_step(t.loss, last) if optimizer == "adam" else t.sgd_step(0.05, t.loss, last)
+            last = t.loss
+        t.result()
+    state = t._step.state.clone() if optimizer == "adam" else torch.zeros(0, device=dev)
+    return [x.view(torch.int64 if x.dtype == torch.float64 else torch.int32).cpu()
+            for x in (flat.detach(), t._rec, state)], waits
+
+
+@pytest.mark.parametrize("optimizer,guard", [("sgd", "host"), ("adam", "host"), ("sgd", "device"), ("adam", "device")])
+def test_key_table_reuse_rule_and_fresh_grads_equal_fixed_grads(dev, optimizer, guard):
+    """The pinned key table's reuse rule (_KeyPass.stage): no wait before the
+    first call nor for the same addresses, one wait when every grad is a new
+    tensor, none when those addresses come again; and the weights, the record
+    and Adam's state after three iterations are the same bits whether the
+    gradients arrive in new tensors or in fixed ones."""
+    rng = np.random.default_rng(53)
+    w0, *grads = [[torch.from_numpy(rng.normal(0.0, scale, n).astype(np.float32)).to(dev) for n in (5, 3)]
+                  for scale in (0.3, 1.0, 1.0, 1.0, 1.0)]
+    moved, waits = _reuse_run(dev, w0, grads, True, optimizer, guard)
+    assert waits == [False, False] + [True, False] * 3
+    fixed, waits = _reuse_run(dev, w0, grads, False, optimizer, guard)
+    assert waits == [False] * 8
+    for a, b, what in zip(moved, fixed, ("weights", "record", "adam state")):
+        assert torch.equal(a, b), what
+    assert not torch.equal(moved[0], torch.cat(w0).view(torch.int32).cpu())  # the steps were taken
