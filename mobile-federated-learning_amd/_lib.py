@@ -11,8 +11,8 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTVEC_LIB_PATH, DESCRIBED,
-                    EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, PROBE_LIB_PATH, SEGVEC_LIB_PATH, NativeLib)
+from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTVEC_LIB_PATH, DESCRIBED,
+                    EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, LINEAR_BY_KEY, PROBE_LIB_PATH, SEGVEC_LIB_PATH, NativeLib)
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -204,6 +204,15 @@ CLIENTLOOP_SIGNATURES = {
     "fedavg_client_adam_step_gated_f64": _CLIENTLOOP_ADAM,
 }
 
+# libfedavg_amd_clientlinear.so (include/fedavg_amd_clientlinear.h)
+CLIENTLINEAR_SIGNATURES = {
+    "fedavg_clientlinear_abi_version": (_c_int, []),
+    "fedavg_clientlinear_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_linear_limits": (None, [_vp, _vp, _vp, _vp]),
+    "fedavg_client_linear_loop_f32": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
+                                               ctypes.c_double, ctypes.c_double, _c_int, _vp, _vp, _vp]),
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
@@ -211,6 +220,7 @@ CLIENTVEC_ABI_VERSION = BY_KEY["clientvec"].abi[1]
 CLIENTSTEP_ABI_VERSION = BY_KEY["clientstep"].abi[1]
 CLIENTADAM_ABI_VERSION = DESCRIBED["clientadam"].abi[1]
 CLIENTLOOP_ABI_VERSION = EXTRA_BY_KEY["clientloop"].abi[1]
+CLIENTLINEAR_ABI_VERSION = LINEAR_BY_KEY["clientlinear"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -243,6 +253,10 @@ _BINDING = {
 _EXTRA_BINDING = {
     "clientloop": ((CLIENTLOOP_SIGNATURES,), "CLIENTLOOP_LIB_PATH", "_clientloop"),
 }
+# the same for the libraries of build.LINEAR_BY_KEY (a new one goes here)
+_LINEAR_BINDING = {
+    "clientlinear": ((CLIENTLINEAR_SIGNATURES,), "CLIENTLINEAR_LIB_PATH", "_clientlinear"),
+}
 
 _lock = threading.Lock()
 _lib = None
@@ -253,6 +267,7 @@ _clientvec = None
 _clientstep = None
 _clientadam = None
 _clientloop = None
+_clientlinear = None
 
 
 def library_path() -> Path:
@@ -262,12 +277,12 @@ def library_path() -> Path:
 def _load(d: NativeLib) -> ctypes.CDLL:
     """Load (once), type and version-check the library ``d`` describes.  No
     fallback: a missing, unloadable or stale library raises ``FedAvgLibraryError``."""
-    tables, path_name, slot = _BINDING[d.key] if d.key in _BINDING else _EXTRA_BINDING[d.key]
+    tables, path_name, slot = next(t[d.key] for t in (_BINDING, _EXTRA_BINDING, _LINEAR_BINDING) if d.key in t)
     g = globals()
     if g[slot] is not None:
         return g[slot]
     if d.needs:
-        _load(DESCRIBED[d.needs] if d.needs in DESCRIBED else EXTRA_BY_KEY[d.needs])
+        _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY) if d.needs in t))
     with _lock:
         if g[slot] is not None:
             return g[slot]
@@ -345,6 +360,11 @@ def load_clientloop() -> ctypes.CDLL:
     return _clientloop if _clientloop is not None else _load(EXTRA_BY_KEY["clientloop"])
 
 
+def load_clientlinear() -> ctypes.CDLL:
+    """The fused local loop of a linear softmax client, fp32 (include/fedavg_amd_clientlinear.h)."""
+    return _clientlinear if _clientlinear is not None else _load(LINEAR_BY_KEY["clientlinear"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
@@ -359,6 +379,11 @@ def check_clientadam(rc: int, what: str) -> None:
 def check_clientloop(rc: int, what: str) -> None:
     """``_check`` for the guard and gated step library (its description read at call time)."""
     _check(EXTRA_BY_KEY["clientloop"], rc, what)
+
+
+def check_clientlinear(rc: int, what: str) -> None:
+    """``_check`` for the linear client loop library (its description read at call time)."""
+    _check(LINEAR_BY_KEY["clientlinear"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

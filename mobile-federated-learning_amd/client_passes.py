@@ -1,9 +1,11 @@
 """The keyed passes behind :mod:`client_stats`: the buffers of a native call
 over a model's tensors and the reuse rule of its pinned key table
 (:class:`_KeyPass`), the fused SGD and Adam steps as its users, the statistics
-library per dtype and the host side of the :71 guard's arithmetic."""
+library per dtype, the host side of the :71 guard's arithmetic and the whole
+local loop of a linear softmax client as one launch (:class:`_LinearLoop`)."""
 from __future__ import annotations
 
+import ctypes
 import math
 
 import numpy as np
@@ -187,3 +189,94 @@ class _AdamPass(_FusedStep):
         ``gated``: as ``_StepPass.launch``'s (``fedavg_client_adam_step_gated_*``)."""
         self._launch(w_ptrs, g_ptrs, (self.offset.ctypes.data, len(self.numel), self.state.data_ptr(), self.state_elems,
                                       coef.ctypes.data, int(bool(first)), form), stats_ptr, st, gated)
+
+
+# ------------------------------------------------------------------ the fused local loop of a linear client
+LINEAR_LOOPS = {"linear": 0, "linear_sigmoid": 1}  # client_train's ``loop`` -> the library's activation code
+_LINEAR_RULE = ("loop='linear' / 'linear_sigmoid' needs a model of exactly two parameters, a contiguous fp32 [C, D] "
+                "weight and a [C] bias that both require grad, on one GPU; a batch whose x.flatten(1) has D columns "
+                "with int64 labels of its length; a default nn.CrossEntropyLoss (mean reduction, no class weights, "
+                "no label smoothing); sizes inside fedavg_client_linear_limits; and a form of the step kernel that "
+                "leaves torch's bits on this GPU (sgd_form / adam_form)")
+
+
+def linear_limits():
+    """``(max B, max D, max C, resident bytes)`` of ``fedavg_client_linear_limits``."""
+    out = [ctypes.c_int64() for _ in range(4)]
+    _lib.load_clientlinear().fedavg_client_linear_limits(*[ctypes.byref(v) for v in out])
+    return tuple(v.value for v in out)
+
+
+class _LinearLoop:
+    """One ``fedavg_client_linear_loop_f32`` call: the checks of what the
+    caller asserts by choosing the loop (``TypeError`` naming the rule, before
+    anything runs) and the launch.  The record and Adam's coefficient table
+    lie in pinned host memory kept per device: the kernel writes the one and
+    reads the other where they lie, and ``run`` returns only after the stream
+    has passed the launch, so the next call may reuse both."""
+
+    _pinned = {}  # device -> [record of 8 doubles, coefficient table [rows, 7]]
+
+    def __init__(self, params, x, labels, criterion, form_of):
+        """``form_of(device)``: the step form for fp32 on ``device``, or ``None``."""
+        def refuse(why):
+            raise TypeError(f"{why}: {_LINEAR_RULE}")
+
+        params = list(params)
+        if len(params) != 2:
+            refuse(f"the model has {len(params)} parameters, not two")
+        w, b = params
+        if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous():
+            refuse("the first parameter is no contiguous fp32 [C, D] weight")
+        if b.dtype != torch.float32 or b.shape != (w.shape[0],) or not b.is_contiguous():
+            refuse("the second parameter is no contiguous fp32 [C] bias")
+        if not (w.requires_grad and b.requires_grad):
+            refuse("a parameter does not require grad")
+        C, D = w.shape
+        if x.dim() < 2 or x.dtype != torch.float32 or x.flatten(1).shape[1] != D:
+            refuse(f"x.flatten(1) is no fp32 batch of {D} columns")
+        B = x.shape[0]
+        if labels.dtype != torch.int64 or labels.shape != (B,):
+            refuse(f"the labels are not int64 of length {B}")
+        if not (type(criterion) is torch.nn.CrossEntropyLoss and criterion.reduction == "mean"
+                and criterion.weight is None and criterion.label_smoothing == 0.0 and criterion.ignore_index == -100):
+            refuse("the criterion is no default nn.CrossEntropyLoss")
+        max_b, max_d, max_c, _ = linear_limits()
+        if not (1 <= B <= max_b and 1 <= D <= max_d and 2 <= C <= max_c):
+            refuse(f"B = {B}, D = {D}, C = {C} lie outside B <= {max_b}, D <= {max_d}, 2 <= C <= {max_c}")
+        if not (w.is_cuda and b.device == w.device and x.device == w.device and labels.device == w.device):
+            refuse("the parameters and the batch are not on one GPU")
+        self.form = form_of(w.device)
+        if self.form is None:
+            refuse("no form of the step kernel leaves torch's bits on this GPU")
+        self.w, self.b, self.x, self.labels = w, b, x.flatten(1).contiguous(), labels.contiguous()
+        self.B, self.D, self.C, self.device = B, D, C, w.device
+
+    def _buffers(self, rows):
+        held = self._pinned.get(self.device)
+        if held is None or held[1].shape[0] < rows:
+            with torch.cuda.device(self.device):
+                held = [torch.zeros(8, dtype=torch.float64, pin_memory=True),
+                        torch.zeros(max(rows, 16), 7, dtype=torch.float64, pin_memory=True)]
+            self._pinned[self.device] = held
+        return held
+
+    def run(self, iters, activation, lr, lr_ratio, adam=None):
+        """The loop on the current stream and the one host sync; returns the
+        record as 8 floats.  ``adam``: ``(beta1, beta2, eps, weight_decay)``
+        of the reference's Adam, else plain SGD."""
+        rec, table = self._buffers(iters if adam else 0)
+        if adam:
+            for t in range(iters):
+                table[t] = torch.from_numpy(adam_coef(lr, *adam, t + 1))
+        st = torch.cuda.current_stream(self.device)
+        name = "fedavg_client_linear_loop_f32"
+        with torch.cuda.device(self.device), torch.no_grad():
+            rc = getattr(_lib.load_clientlinear(), name)(
+                self.w.data_ptr(), self.b.data_ptr(), self.x.data_ptr(), self.labels.data_ptr(), self.B, self.D,
+                self.C, iters, activation, 1 if adam else 0, float(lr), float(lr_ratio), self.form,
+                table.data_ptr() if adam else None, rec.data_ptr(), st.cuda_stream)
+        _lib.check_clientlinear(rc, name)
+        torch.autograd.graph.increment_version([self.w, self.b])  # the in-place update autograd did not see
+        st.synchronize()
+        return rec.tolist()

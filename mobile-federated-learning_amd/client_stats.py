@@ -68,8 +68,8 @@ import torch
 
 from . import _lib
 from .client_forms import _ADAM_PROBE, _mine_site_c, _probe_adam_form, _probe_sgd_form, _probe_values  # noqa: F401
-from .client_passes import (ADAM_SITES, FUSED_DTYPES, _RULE, _STEP_SUFFIX, _AdamPass, _KeyPass,  # noqa: F401
-                            _STATS_LIBS, _StepPass, _fused_ok, _guard_bound, _norm_of, _round_to, adam_coef)
+from .client_passes import (ADAM_SITES, FUSED_DTYPES, LINEAR_LOOPS, _RULE, _STEP_SUFFIX, _AdamPass,  # noqa: F401
+                            _KeyPass, _LinearLoop, _STATS_LIBS, _StepPass, _fused_ok, _guard_bound, _norm_of, _round_to, adam_coef)
 
 # rec: one device record of doubles, read back in one D2H.  The device guard adds the previous loss, the gate and
 # the epoch of the first trip (include/fedavg_amd_clientloop.h: loss = rec[_LOSS:_LOSS + 2], gate = rec[_GATE:_GATE + 2])
@@ -574,8 +574,34 @@ class ClientStepStats:
                 None if self._rho is None else self._rho.item())
 
 
+def _linear_train(self, net, local_iteration, loop, keep_on_device, mod):
+    """``client_train`` under ``loop="linear"`` / ``"linear_sigmoid"``: client.py:38-96 as ONE launch of
+    ``fedavg_client_linear_loop_f32`` and one host sync."""
+    sgd = self.args.client_optimizer == "sgd"
+    x, labels = next(iter(self.local_training_data))
+    x, labels = x.to(self.device), labels.to(self.device)
+    form_of = (lambda dev: sgd_form(dev, torch.float32)) if sgd else (lambda dev: adam_form(dev, torch.float32))
+    plan = _LinearLoop(net.parameters(), x, labels, self.criterion, form_of)  # refused, if it is, before anything runs
+    net.train()
+    start = mod.count()
+    rec = plan.run(local_iteration, LINEAR_LOOPS[loop], self.args.lr, self.args.lr * mod.THRESHOLD_GRADS_RATIO,
+                   None if sgd else (0.9, 0.999, 1e-8, self.args.wd))
+    cycles = (mod.count_end() - start) / local_iteration  # one launch: there is no per-iteration host time
+    trip, loss, beta, rho, correct, bad_label = rec[:6]
+    if bad_label:
+        raise IndexError(f"a label lies outside [0, {plan.C}): the kernel refused the batch and left the parameters "
+                         "untouched")
+    sd = net.state_dict() if keep_on_device else net.cpu().state_dict()
+    if trip >= 0:
+        logger = getattr(mod, "logger", None)
+        if logger is not None:
+            logger.warning("grads too large than weights or meets nan with epoch {}".format(int(trip)))
+        return sd, None, None, None, None, None
+    return sd, loss, beta, rho, correct / plan.B, cycles
+
+
 def client_train(self, net, local_iteration, *, keep_on_device=False, stats="auto", trace=None, step="torch",
-                 guard="host"):
+                 guard="host", loop="torch"):
     """``Client.train(self, net, local_iteration)`` (client.py:38-96) with the
     bookkeeping of :52-86 done by :class:`ClientStepStats`.
 
@@ -597,8 +623,24 @@ def client_train(self, net, local_iteration, *, keep_on_device=False, stats="aut
     sync of the bookkeeping.  The return values are the host guard's to the
     bit; after a trip the parameters are too, while module buffers and the
     RNG stream may be up to ``ahead`` iterations further (see the class).
+
+    ``loop="linear"`` / ``"linear_sigmoid"`` (opt in; the default ``"torch"``
+    is everything above) runs the WHOLE loop, forward and backward included,
+    in one persistent kernel (``libfedavg_amd_clientlinear.so``).  By choosing
+    it the caller asserts that ``net(x)`` is ``linear(x.flatten(1))``,
+    followed by a sigmoid for ``"linear_sigmoid"``; what the host can check of
+    that it checks, and raises ``TypeError`` naming the rule before anything
+    runs.  ``stats``, ``step``, ``guard`` and ``trace`` play no part.  The
+    tuple is the reference's; ``cycles`` is the host cycle count around the
+    launch and the record read divided by ``local_iteration``; ``p.grad`` is
+    not populated; a label outside ``[0, C)`` raises ``IndexError`` with the
+    parameters untouched.  ``local_iteration == 0`` takes the torch path.
     """
     mod = sys.modules[type(self).__module__]
+    if loop != "torch" and loop not in LINEAR_LOOPS:
+        raise ValueError(f"loop must be 'torch', 'linear' or 'linear_sigmoid', not {loop!r}")
+    if loop != "torch" and local_iteration > 0:
+        return _linear_train(self, net, local_iteration, loop, keep_on_device, mod)
     count, count_end, ratio = mod.count, mod.count_end, mod.THRESHOLD_GRADS_RATIO
     sgd = self.args.client_optimizer == "sgd"
     tracker = None
@@ -693,7 +735,7 @@ class _Patch:
         return False
 
 
-def patch(cls, *, keep_on_device=False, stats="auto", step="torch", guard="host"):
+def patch(cls, *, keep_on_device=False, stats="auto", step="torch", guard="host", loop="torch"):
     """Replace ``cls.train`` (the reference's ``Client.train``) with
     :func:`client_train`; returns a handle whose ``undo()`` restores the class."""
     had = "train" in vars(cls)
@@ -701,7 +743,7 @@ def patch(cls, *, keep_on_device=False, stats="auto", step="torch", guard="host"
 
     def train(self, net, local_iteration):
         return client_train(self, net, local_iteration, keep_on_device=keep_on_device, stats=stats, step=step,
-                            guard=guard)
+                            guard=guard, loop=loop)
 
     train.__wrapped_by__ = "mfl_amd.client_stats"
     setattr(cls, "train", train)

@@ -289,6 +289,24 @@ struct CliOpF64 {
   __device__ static double rt(float x) { return static_cast<double>(x); }
 };
 
+// The two norms of the :71 guard and its bound.  Every fp32 operation is
+// formed in fp64 from fp32 operands and rounded once to fp32, as cli_track
+// forms them.
+template <class Op>
+__device__ __forceinline__ double guard_norm(double sumsq) {
+  const double r = __builtin_sqrt(sumsq);  // a NaN sum gives a NaN norm
+  if constexpr (Op::kF64) return r;
+  return Op::rt(static_cast<float>(r));
+}
+
+// lr * ratio * norm(last_w): python_float * tensor, the scalar rounded to opmath, the product to the tensor's type
+template <class Op>
+__device__ __forceinline__ double guard_bound(double n_w, double lr_ratio) {
+  if constexpr (Op::kF64) return n_w * lr_ratio;
+  const double s = static_cast<double>(static_cast<float>(lr_ratio));
+  return Op::rt(static_cast<float>(s * n_w));  // the fp64 product of two fp32 values is exact: one rounding
+}
+
 // client.py:78-84 on the device in the model's type; `state` = {rho, beta,
 // has rho, has beta} holds values of T exactly.  Every fp32 operation is
 // formed in fp64 from fp32 operands and rounded once to fp32 (for sqrt, a

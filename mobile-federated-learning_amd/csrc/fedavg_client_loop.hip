@@ -42,25 +42,8 @@ int cl_error(int code, const char* fmt, ...) {
 int cl_launch_status(const char* what) { return launch_status(g_cl_err, what); }
 
 // ---------------------------------------------------------------------------
-// The guard.  Op: the scalar arithmetic of the model's type (client_pass.hpp).
-// Every fp32 operation is formed in fp64 from fp32 operands and rounded once
-// to fp32, as cli_track forms them.
+// The guard: guard_norm / guard_bound of client_pass.hpp, decided by one thread.
 // ---------------------------------------------------------------------------
-template <class Op>
-__device__ __forceinline__ double guard_norm(double sumsq) {
-  const double r = __builtin_sqrt(sumsq);  // a NaN sum gives a NaN norm
-  if constexpr (Op::kF64) return r;
-  return Op::rt(static_cast<float>(r));
-}
-
-// lr * ratio * norm(last_w): python_float * tensor, the scalar rounded to opmath, the product to the tensor's type
-template <class Op>
-__device__ __forceinline__ double guard_bound(double n_w, double lr_ratio) {
-  if constexpr (Op::kF64) return n_w * lr_ratio;
-  const double s = static_cast<double>(static_cast<float>(lr_ratio));
-  return Op::rt(static_cast<float>(s * n_w));  // the fp64 product of two fp32 values is exact: one rounding
-}
-
 template <class Op>
 __global__ __launch_bounds__(64) void client_guard_kernel(const double* rec_g, const double* rec_w,
                                                           const double* loss, double* gate, double lr_ratio,

@@ -98,9 +98,8 @@ class Pool {
       std::lock_guard<std::mutex> lk(mu_);
       job_ = &fn;
       njobs_ = n;
-      next_.store(1);
+      next_ = 1;
       pending_ = n - 1;
-      ++gen_;
     }
     cv_.notify_all();
     fn(0);
@@ -113,7 +112,6 @@ class Pool {
     {
       std::lock_guard<std::mutex> lk(mu_);
       stop_ = true;
-      ++gen_;
     }
     cv_.notify_all();
     for (auto& t : threads_) t.join();
@@ -124,24 +122,24 @@ class Pool {
     while (static_cast<int>(threads_.size()) < workers) threads_.emplace_back([this] { loop(); });
   }
 
+  // A worker takes the job and one of its indices in ONE critical section, and only while a job is published with
+  // indices left: job_ is cleared after the last taken index has finished, so a worker that starts or wakes late
+  // (between two runs, or while the next one is being published) can never pair one run's index with another
+  // run's job, or with the cleared pointer.
   void loop() {
-    uint64_t seen = 0;
     for (;;) {
       const std::function<void(int)>* job;
+      int t;
       {
         std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
+        cv_.wait(lk, [&] { return stop_ || (job_ && next_ < njobs_); });
         if (stop_) return;
-        seen = gen_;
         job = job_;
+        t = next_++;
       }
-      for (;;) {
-        const int t = next_.fetch_add(1);
-        if (t >= njobs_) break;
-        (*job)(t);
-        std::lock_guard<std::mutex> lk(mu_);
-        if (--pending_ == 0) done_cv_.notify_one();
-      }
+      (*job)(t);
+      std::lock_guard<std::mutex> lk(mu_);
+      if (--pending_ == 0) done_cv_.notify_one();
     }
   }
 
@@ -149,10 +147,9 @@ class Pool {
   std::condition_variable cv_, done_cv_;
   std::vector<std::thread> threads_;
   const std::function<void(int)>* job_ = nullptr;
-  std::atomic<int> next_{0};
+  int next_ = 0;
   int njobs_ = 0;
   int pending_ = 0;
-  uint64_t gen_ = 0;
   bool stop_ = false;
 };
 

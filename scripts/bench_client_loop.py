@@ -7,7 +7,10 @@ then the last read), with real models, under three kinds of bookkeeping:
   fused   : step="fused"  -- the fused SGD / Adam step, still one sync per
             iteration;
   device  : step="fused", guard="device" at ahead in --ahead -- the guard
-            decided on the device, the step gated on it, one sync per loop.
+            decided on the device, the step gated on it, one sync per loop;
+  linear  : loop="linear" -- the whole loop, forward and backward included,
+            in one persistent kernel and one sync (the fp32 logistic
+            regression rows only: the one model it serves).
 
     python scripts/bench_client_loop.py [--models ...] [--dtypes f32,bf16] [--reps 30] [--out-dir profiles/client_loop]
 
@@ -133,7 +136,7 @@ def make_client(x, labels, dev, optimizer):
 def one_loop(client, net, start, iters, arm):
     """Wall-clock microseconds of one local loop from the weights ``start``."""
     net.load_state_dict(start)
-    kw = dict(step="torch") if arm == "torch" else dict(step="fused")
+    kw = dict(step="torch") if arm == "torch" else dict(loop="linear") if arm == "linear" else dict(step="fused")
     if arm.startswith("device"):
         kw["guard"] = "device"
         client_stats.DEFAULT_AHEAD = int(arm.split("_")[1])
@@ -161,7 +164,7 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     default_ahead = client_stats.DEFAULT_AHEAD
-    arms = ["torch", "fused"] + [f"device_{a}" for a in args.ahead.split(",")]
+    base_arms = ["torch", "fused"] + [f"device_{a}" for a in args.ahead.split(",")]
     lines = []
     for name in args.models.split(","):
         make, shape, classes = MODELS[name]
@@ -173,8 +176,10 @@ def main():
             labels = torch.randint(0, classes, (BATCH,), device=dev)
             start = copy.deepcopy(net.state_dict())
             P = sum(p.numel() for p in net.parameters())
+            linear = name == "mnist_lr" and key == "f32"
             for optimizer in args.optimizers.split(","):
                 client = make_client(x, labels, dev, optimizer)
+                arms = base_arms + ["linear"] * linear
                 times = {arm: [] for arm in arms}
                 for rep in range(args.warmup + args.reps):
                     for arm in arms:
@@ -188,6 +193,10 @@ def main():
                         "us_min": {arm: round(min(ts), 1) for arm, ts in times.items()},
                         "vs_fused": {arm: round(m / med["fused"], 3) for arm, m in med.items()},
                         "device": torch.cuda.get_device_name(0), "torch": torch.__version__}
+                if linear:  # the arms alternate within a repetition: compare repetition by repetition
+                    line["linear_below_every_device_arm_in_reps"] = sum(
+                        all(t < times[arm][r] for arm in arms if arm.startswith("device"))
+                        for r, t in enumerate(times["linear"]))
                 print(json.dumps(line), flush=True)
                 lines.append(line)
             del net
