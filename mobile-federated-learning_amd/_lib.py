@@ -11,8 +11,9 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTVEC_LIB_PATH, DESCRIBED,
-                    EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, LINEAR_BY_KEY, PROBE_LIB_PATH, SEGVEC_LIB_PATH, NativeLib)
+from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
+                    CLIENTVEC_LIB_PATH, DESCRIBED, EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, LINEAR_BY_KEY, PROBE_LIB_PATH,
+                    SEGVEC_LIB_PATH, STREAM_BY_KEY, NativeLib)
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -213,6 +214,15 @@ CLIENTLINEAR_SIGNATURES = {
                                                ctypes.c_double, ctypes.c_double, _c_int, _vp, _vp, _vp]),
 }
 
+# libfedavg_amd_clientstream.so (include/fedavg_amd_clientstream.h)
+CLIENTSTREAM_SIGNATURES = {
+    "fedavg_clientstream_abi_version": (_c_int, []),
+    "fedavg_clientstream_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_stream_limits": (None, [_vp, _vp, _vp, _vp]),
+    "fedavg_client_stream_group_rows": (_c_i64, [_c_i64]),
+    "fedavg_client_linear_stream_f32": CLIENTLINEAR_SIGNATURES["fedavg_client_linear_loop_f32"],
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
@@ -221,6 +231,7 @@ CLIENTSTEP_ABI_VERSION = BY_KEY["clientstep"].abi[1]
 CLIENTADAM_ABI_VERSION = DESCRIBED["clientadam"].abi[1]
 CLIENTLOOP_ABI_VERSION = EXTRA_BY_KEY["clientloop"].abi[1]
 CLIENTLINEAR_ABI_VERSION = LINEAR_BY_KEY["clientlinear"].abi[1]
+CLIENTSTREAM_ABI_VERSION = STREAM_BY_KEY["clientstream"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -257,6 +268,10 @@ _EXTRA_BINDING = {
 _LINEAR_BINDING = {
     "clientlinear": ((CLIENTLINEAR_SIGNATURES,), "CLIENTLINEAR_LIB_PATH", "_clientlinear"),
 }
+# the same for the libraries of build.STREAM_BY_KEY (a new one goes here)
+_STREAM_BINDING = {
+    "clientstream": ((CLIENTSTREAM_SIGNATURES,), "CLIENTSTREAM_LIB_PATH", "_clientstream"),
+}
 
 _lock = threading.Lock()
 _lib = None
@@ -268,6 +283,7 @@ _clientstep = None
 _clientadam = None
 _clientloop = None
 _clientlinear = None
+_clientstream = None
 
 
 def library_path() -> Path:
@@ -277,12 +293,13 @@ def library_path() -> Path:
 def _load(d: NativeLib) -> ctypes.CDLL:
     """Load (once), type and version-check the library ``d`` describes.  No
     fallback: a missing, unloadable or stale library raises ``FedAvgLibraryError``."""
-    tables, path_name, slot = next(t[d.key] for t in (_BINDING, _EXTRA_BINDING, _LINEAR_BINDING) if d.key in t)
+    tables, path_name, slot = next(t[d.key] for t in (_BINDING, _EXTRA_BINDING, _LINEAR_BINDING, _STREAM_BINDING)
+                                   if d.key in t)
     g = globals()
     if g[slot] is not None:
         return g[slot]
     if d.needs:
-        _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY) if d.needs in t))
+        _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY, STREAM_BY_KEY) if d.needs in t))
     with _lock:
         if g[slot] is not None:
             return g[slot]
@@ -365,6 +382,11 @@ def load_clientlinear() -> ctypes.CDLL:
     return _clientlinear if _clientlinear is not None else _load(LINEAR_BY_KEY["clientlinear"])
 
 
+def load_clientstream() -> ctypes.CDLL:
+    """The streamed local loop of a linear softmax client, fp32 (include/fedavg_amd_clientstream.h)."""
+    return _clientstream if _clientstream is not None else _load(STREAM_BY_KEY["clientstream"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
@@ -384,6 +406,11 @@ def check_clientloop(rc: int, what: str) -> None:
 def check_clientlinear(rc: int, what: str) -> None:
     """``_check`` for the linear client loop library (its description read at call time)."""
     _check(LINEAR_BY_KEY["clientlinear"], rc, what)
+
+
+def check_clientstream(rc: int, what: str) -> None:
+    """``_check`` for the streamed linear client loop library (its description read at call time)."""
+    _check(STREAM_BY_KEY["clientstream"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

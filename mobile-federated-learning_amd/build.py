@@ -11,10 +11,12 @@ same dataclass in ``NEWER_LIBS``, and ``EVERY_LIB = ALL_LIBS + NEWER_LIBS`` /
 The eighth, and any after it, is described in ``EXTRA_LIBS`` / ``EXTRA_BY_KEY``
 and ``BUILT_LIBS = EVERY_LIB + EXTRA_LIBS`` is the eight that
 tests/test_clientloop_abi.py pins.  The ninth, and any after it, is described
-in ``LINEAR_LIBS`` / ``LINEAR_BY_KEY`` (a new one goes there);
-``BUILT_LIBS + LINEAR_LIBS`` is what ``sources()``, the up-to-date rule and
-``build()`` cover, and ``_lib`` loads a library from the by-key table that
-holds it.
+in ``LINEAR_LIBS`` / ``LINEAR_BY_KEY``, which tests/test_clientlinear_abi.py
+pins to that one key.  The tenth, and any after it, is described in
+``STREAM_LIBS`` / ``STREAM_BY_KEY`` (a new one goes there);
+``BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS`` is what ``sources()``, the
+up-to-date rule and ``build()`` cover, and ``_lib`` loads a library from the
+by-key table that holds it.
 
 Every translation unit of ``BUILT_LIBS`` is compiled in parallel with hipcc for
 ``--offload-arch=gfx950`` and each library is linked into ``lib/`` inside the
@@ -147,6 +149,18 @@ LINEAR_LIBS = (
 )
 LINEAR_BY_KEY = {lib.key: lib for lib in LINEAR_LIBS}
 CLIENTLINEAR_LIB_PATH = LINEAR_BY_KEY["clientlinear"].path
+# libraries added after those nine (a new one goes here: see the module docstring)
+STREAM_LIBS = (
+    # the same loop for batches of up to 16384 samples, streamed through LDS in groups of rows, fp32; calls no other
+    # library.  Its unit is compiled without packed fp32 instructions.
+    NativeLib("clientstream", "libfedavg_amd_clientstream.so", "fedavg_amd_clientstream.h",
+              ("fedavg_client_stream.hip",), abi=("fedavg_clientstream_abi_version", 1),
+              last_error="fedavg_clientstream_last_error",
+              no_fallback="; there is no fallback for the streamed local loop of a linear client",
+              defines=("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")),
+)
+STREAM_BY_KEY = {lib.key: lib for lib in STREAM_LIBS}
+CLIENTSTREAM_LIB_PATH = STREAM_BY_KEY["clientstream"].path
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",
@@ -174,7 +188,7 @@ def hipcc_path() -> str:
 def sources():
     """Everything a library can depend on: every translation unit, every
     header in csrc/ and include/ (found, not listed) and this recipe."""
-    units = dict.fromkeys(src for lib in BUILT_LIBS + LINEAR_LIBS for src in lib.sources)
+    units = dict.fromkeys(src for lib in BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS for src in lib.sources)
     return [*units, *sorted(CSRC_DIR.glob("*.hpp")), *sorted(INCLUDE.glob("*.h")), Path(__file__)]
 
 
@@ -184,11 +198,11 @@ def up_to_date() -> bool:
 
 
 def later_up_to_date() -> bool:
-    """The same rule for ``LATER_LIBS``, ``NEWER_LIBS``, ``EXTRA_LIBS`` and ``LINEAR_LIBS``: each built and no older
-    than the newest source."""
+    """The same rule for ``LATER_LIBS``, ``NEWER_LIBS``, ``EXTRA_LIBS``, ``LINEAR_LIBS`` and ``STREAM_LIBS``: each
+    built and no older than the newest source."""
     newest = max(p.stat().st_mtime for p in sources())
     return all(lib.path.exists() and lib.path.stat().st_mtime >= newest
-               for lib in LATER_LIBS + NEWER_LIBS + EXTRA_LIBS + LINEAR_LIBS)
+               for lib in LATER_LIBS + NEWER_LIBS + EXTRA_LIBS + LINEAR_LIBS + STREAM_LIBS)
 
 
 def collect_ext_path() -> Path:
@@ -243,14 +257,14 @@ def _link(objs, lib_path, verbose, extra=()):
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Build every library of ``BUILT_LIBS + LINEAR_LIBS``; returns the product library's path."""
+    """Build every library of ``BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS``; returns the product library's path."""
     if not force and up_to_date() and later_up_to_date():
         return LIB_PATH
-    libs = BUILT_LIBS + LINEAR_LIBS
+    libs = BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS
     for lib in libs:
         (LIB_DIR / lib.obj_dir).mkdir(parents=True, exist_ok=True)
     _compile_all([(CSRC_DIR / u, lib.obj(u), list(lib.defines)) for lib in libs for u in lib.units], verbose)
-    by_key = {**DESCRIBED, **EXTRA_BY_KEY, **LINEAR_BY_KEY}
+    by_key = {**DESCRIBED, **EXTRA_BY_KEY, **LINEAR_BY_KEY, **STREAM_BY_KEY}
     for lib in libs:  # in order: a library links after the one its link arguments name
         objs = [lib.obj(u) for u in lib.units] + [by_key[key].obj(u) for key, u in lib.reuse]
         _link(objs, lib.path, verbose, extra=lib.link)

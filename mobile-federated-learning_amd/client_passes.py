@@ -196,8 +196,9 @@ LINEAR_LOOPS = {"linear": 0, "linear_sigmoid": 1}  # client_train's ``loop`` -> 
 _LINEAR_RULE = ("loop='linear' / 'linear_sigmoid' needs a model of exactly two parameters, a contiguous fp32 [C, D] "
                 "weight and a [C] bias that both require grad, on one GPU; a batch whose x.flatten(1) has D columns "
                 "with int64 labels of its length; a default nn.CrossEntropyLoss (mean reduction, no class weights, "
-                "no label smoothing); sizes inside fedavg_client_linear_limits; and a form of the step kernel that "
-                "leaves torch's bits on this GPU (sgd_form / adam_form)")
+                "no label smoothing); sizes inside fedavg_client_linear_limits (B <= 64, one resident batch) or "
+                "fedavg_client_stream_limits (longer batches, streamed in groups of rows); and a form of the step "
+                "kernel that leaves torch's bits on this GPU (sgd_form / adam_form)")
 
 
 def linear_limits():
@@ -207,8 +208,17 @@ def linear_limits():
     return tuple(v.value for v in out)
 
 
+def linear_stream_limits():
+    """``(max B, max D, max C, LDS bytes of the two row buffers)`` of ``fedavg_client_stream_limits``."""
+    out = [ctypes.c_int64() for _ in range(4)]
+    _lib.load_clientstream().fedavg_client_stream_limits(*[ctypes.byref(v) for v in out])
+    return tuple(v.value for v in out)
+
+
 class _LinearLoop:
-    """One ``fedavg_client_linear_loop_f32`` call: the checks of what the
+    """One ``fedavg_client_linear_loop_f32`` call, or for a batch of more than
+    ``linear_limits()[0]`` samples one ``fedavg_client_linear_stream_f32``
+    call (the same arguments and record): the checks of what the
     caller asserts by choosing the loop (``TypeError`` naming the rule, before
     anything runs) and the launch.  The record and Adam's coefficient table
     lie in pinned host memory kept per device: the kernel writes the one and
@@ -241,9 +251,11 @@ class _LinearLoop:
         if not (type(criterion) is torch.nn.CrossEntropyLoss and criterion.reduction == "mean"
                 and criterion.weight is None and criterion.label_smoothing == 0.0 and criterion.ignore_index == -100):
             refuse("the criterion is no default nn.CrossEntropyLoss")
-        max_b, max_d, max_c, _ = linear_limits()
+        self.resident_b = linear_limits()[0]
+        max_b, max_d, max_c, _ = linear_stream_limits()
         if not (1 <= B <= max_b and 1 <= D <= max_d and 2 <= C <= max_c):
-            refuse(f"B = {B}, D = {D}, C = {C} lie outside B <= {max_b}, D <= {max_d}, 2 <= C <= {max_c}")
+            refuse(f"B = {B}, D = {D}, C = {C} lie outside B <= {max_b} (resident up to {self.resident_b}, streamed "
+                   f"above), D <= {max_d}, 2 <= C <= {max_c}")
         if not (w.is_cuda and b.device == w.device and x.device == w.device and labels.device == w.device):
             refuse("the parameters and the batch are not on one GPU")
         self.form = form_of(w.device)
@@ -270,13 +282,16 @@ class _LinearLoop:
             for t in range(iters):
                 table[t] = torch.from_numpy(adam_coef(lr, *adam, t + 1))
         st = torch.cuda.current_stream(self.device)
-        name = "fedavg_client_linear_loop_f32"
+        if self.B <= self.resident_b:
+            name, load, check = "fedavg_client_linear_loop_f32", _lib.load_clientlinear, _lib.check_clientlinear
+        else:
+            name, load, check = "fedavg_client_linear_stream_f32", _lib.load_clientstream, _lib.check_clientstream
         with torch.cuda.device(self.device), torch.no_grad():
-            rc = getattr(_lib.load_clientlinear(), name)(
+            rc = getattr(load(), name)(
                 self.w.data_ptr(), self.b.data_ptr(), self.x.data_ptr(), self.labels.data_ptr(), self.B, self.D,
                 self.C, iters, activation, 1 if adam else 0, float(lr), float(lr_ratio), self.form,
                 table.data_ptr() if adam else None, rec.data_ptr(), st.cuda_stream)
-        _lib.check_clientlinear(rc, name)
+        check(rc, name)
         torch.autograd.graph.increment_version([self.w, self.b])  # the in-place update autograd did not see
         st.synchronize()
         return rec.tolist()

@@ -576,7 +576,8 @@ class ClientStepStats:
 
 def _linear_train(self, net, local_iteration, loop, keep_on_device, mod):
     """``client_train`` under ``loop="linear"`` / ``"linear_sigmoid"``: client.py:38-96 as ONE launch of
-    ``fedavg_client_linear_loop_f32`` and one host sync."""
+    ``fedavg_client_linear_loop_f32`` (``fedavg_client_linear_stream_f32`` for more than 64 samples) and one host
+    sync."""
     sgd = self.args.client_optimizer == "sgd"
     x, labels = next(iter(self.local_training_data))
     x, labels = x.to(self.device), labels.to(self.device)
