@@ -37,7 +37,8 @@ from .session import RoundSession
 from .multi import ShardedAggregator, ShardedRoundSession, sharded_aggregator
 from .fpf import FPFTracker
 from . import client_stats
-from .client_stats import ADAM_DTYPES, DEFAULT_AHEAD, ClientStepStats, adam_form, adam_form_probe, client_train
+from .client_stats import (ADAM_DTYPES, DEFAULT_AHEAD, ClientStepStats, CohortResult, adam_form, adam_form_probe,
+                           client_train, cohort_train)
 
 __all__ = [
     "FedAvgLibraryError",
@@ -68,6 +69,8 @@ __all__ = [
     "client_stats",
     "ClientStepStats",
     "client_train",
+    "cohort_train",
+    "CohortResult",
     "ADAM_DTYPES",
     "adam_form",
     "adam_form_probe",

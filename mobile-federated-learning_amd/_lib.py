@@ -11,7 +11,7 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
+from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCOHORT_LIB_PATH, COHORT_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
                     CLIENTVEC_LIB_PATH, DESCRIBED, EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, LINEAR_BY_KEY, PROBE_LIB_PATH,
                     SEGVEC_LIB_PATH, STREAM_BY_KEY, NativeLib)
 
@@ -223,6 +223,15 @@ CLIENTSTREAM_SIGNATURES = {
     "fedavg_client_linear_stream_f32": CLIENTLINEAR_SIGNATURES["fedavg_client_linear_loop_f32"],
 }
 
+# libfedavg_amd_clientcohort.so (include/fedavg_amd_clientcohort.h)
+CLIENTCOHORT_SIGNATURES = {
+    "fedavg_clientcohort_abi_version": (_c_int, []),
+    "fedavg_clientcohort_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_cohort_limits": (None, [_vp, _vp, _vp, _vp]),
+    "fedavg_client_cohort_f32": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
+                                          ctypes.c_double, ctypes.c_double, _c_int, _vp, _vp, _vp]),
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
@@ -232,6 +241,7 @@ CLIENTADAM_ABI_VERSION = DESCRIBED["clientadam"].abi[1]
 CLIENTLOOP_ABI_VERSION = EXTRA_BY_KEY["clientloop"].abi[1]
 CLIENTLINEAR_ABI_VERSION = LINEAR_BY_KEY["clientlinear"].abi[1]
 CLIENTSTREAM_ABI_VERSION = STREAM_BY_KEY["clientstream"].abi[1]
+CLIENTCOHORT_ABI_VERSION = COHORT_BY_KEY["clientcohort"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -273,6 +283,11 @@ _STREAM_BINDING = {
     "clientstream": ((CLIENTSTREAM_SIGNATURES,), "CLIENTSTREAM_LIB_PATH", "_clientstream"),
 }
 
+# the same for the libraries of build.COHORT_BY_KEY (a new one goes here)
+_COHORT_BINDING = {
+    "clientcohort": ((CLIENTCOHORT_SIGNATURES,), "CLIENTCOHORT_LIB_PATH", "_clientcohort"),
+}
+
 _lock = threading.Lock()
 _lib = None
 _probe = None
@@ -284,6 +299,7 @@ _clientadam = None
 _clientloop = None
 _clientlinear = None
 _clientstream = None
+_clientcohort = None
 
 
 def library_path() -> Path:
@@ -293,13 +309,14 @@ def library_path() -> Path:
 def _load(d: NativeLib) -> ctypes.CDLL:
     """Load (once), type and version-check the library ``d`` describes.  No
     fallback: a missing, unloadable or stale library raises ``FedAvgLibraryError``."""
-    tables, path_name, slot = next(t[d.key] for t in (_BINDING, _EXTRA_BINDING, _LINEAR_BINDING, _STREAM_BINDING)
-                                   if d.key in t)
+    tables, path_name, slot = next(t[d.key] for t in (_BINDING, _EXTRA_BINDING, _LINEAR_BINDING, _STREAM_BINDING,
+                                                      _COHORT_BINDING) if d.key in t)
     g = globals()
     if g[slot] is not None:
         return g[slot]
     if d.needs:
-        _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY, STREAM_BY_KEY) if d.needs in t))
+        _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY, STREAM_BY_KEY, COHORT_BY_KEY)
+                   if d.needs in t))
     with _lock:
         if g[slot] is not None:
             return g[slot]
@@ -387,6 +404,11 @@ def load_clientstream() -> ctypes.CDLL:
     return _clientstream if _clientstream is not None else _load(STREAM_BY_KEY["clientstream"])
 
 
+def load_clientcohort() -> ctypes.CDLL:
+    """The one-launch cohort of linear softmax clients, fp32 (include/fedavg_amd_clientcohort.h)."""
+    return _clientcohort if _clientcohort is not None else _load(COHORT_BY_KEY["clientcohort"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
@@ -411,6 +433,11 @@ def check_clientlinear(rc: int, what: str) -> None:
 def check_clientstream(rc: int, what: str) -> None:
     """``_check`` for the streamed linear client loop library (its description read at call time)."""
     _check(STREAM_BY_KEY["clientstream"], rc, what)
+
+
+def check_clientcohort(rc: int, what: str) -> None:
+    """``_check`` for the client cohort library (its description read at call time)."""
+    _check(COHORT_BY_KEY["clientcohort"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

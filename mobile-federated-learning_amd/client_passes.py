@@ -2,7 +2,8 @@
 over a model's tensors and the reuse rule of its pinned key table
 (:class:`_KeyPass`), the fused SGD and Adam steps as its users, the statistics
 library per dtype, the host side of the :71 guard's arithmetic and the whole
-local loop of a linear softmax client as one launch (:class:`_LinearLoop`)."""
+local loop of a linear softmax client as one launch (:class:`_LinearLoop`), or of a
+round's whole cohort of them (:class:`_Cohort`)."""
 from __future__ import annotations
 
 import ctypes
@@ -295,3 +296,71 @@ class _LinearLoop:
         torch.autograd.graph.increment_version([self.w, self.b])  # the in-place update autograd did not see
         st.synchronize()
         return rec.tolist()
+
+
+# ------------------------------------------------------------------ a round's cohort of linear clients, one launch
+def cohort_limits():
+    """``(max K, max B, max D, max C)`` of ``fedavg_client_cohort_limits``."""
+    out = [ctypes.c_int64() for _ in range(4)]
+    _lib.load_clientcohort().fedavg_client_cohort_limits(*[ctypes.byref(v) for v in out])
+    return tuple(v.value for v in out)
+
+
+class _Cohort:
+    """One ``fedavg_client_cohort_f32`` call: every client of ``batches`` trained from the same model, client ``k``
+    into row ``k``.  The :class:`_LinearLoop` rules are checked once for the model (with the first batch) and per
+    client for the batch (``TypeError`` naming the rule, before anything runs).  The client table, the records and
+    Adam's coefficient table lie in pinned host memory kept per device; ``run`` returns only after the stream has
+    passed the launch, so the next call may reuse them."""
+
+    _pinned = {}  # device -> [client table [K, 4] int64, records [K, 8], coefficient table [rows, 7]]
+
+    def __init__(self, params, batches, criterion, form_of):
+        first = _LinearLoop(params, *batches[0], criterion, form_of)
+        self.w, self.b, self.form, self.D, self.C, self.device = first.w, first.b, first.form, first.D, first.C, first.device
+        max_k, max_b, _, _ = cohort_limits()
+        if len(batches) > max_k:
+            raise TypeError(f"a cohort of {len(batches)} clients exceeds {max_k}: {_LINEAR_RULE}")
+        self.x, self.labels = [first.x], [first.labels]
+        for k, (x, labels) in enumerate(batches[1:], 1):
+            B = x.shape[0] if x.dim() >= 2 else 0
+            if not (x.dtype == torch.float32 and 1 <= B <= max_b and x.flatten(1).shape[1] == self.D
+                    and labels.dtype == torch.int64 and labels.shape == (B,)
+                    and x.device == self.device and labels.device == self.device):
+                raise TypeError(f"client {k}: no fp32 batch of 1 to {max_b} rows of {self.D} columns with int64 labels "
+                                f"of its length on {self.device}: {_LINEAR_RULE}")
+            self.x.append(x.flatten(1).contiguous())
+            self.labels.append(labels.contiguous())
+        self.K, self.P = len(batches), self.C * self.D + self.C
+        self.B = [x.shape[0] for x in self.x]
+
+    def _buffers(self, iters):
+        held = self._pinned.get(self.device)
+        if held is None or held[0].shape[0] < self.K or held[2].shape[0] < iters:
+            with torch.cuda.device(self.device):
+                held = [torch.zeros(max(self.K, 16), 4, dtype=torch.int64, pin_memory=True),
+                        torch.zeros(max(self.K, 16), 8, dtype=torch.float64, pin_memory=True),
+                        torch.zeros(max(iters, 16), 7, dtype=torch.float64, pin_memory=True)]
+            self._pinned[self.device] = held
+        return held
+
+    def run(self, rows, iters, activation, lr, lr_ratio, adam=None):
+        """The launch on the current stream and the one host sync; returns the ``[K, 8]`` records as lists, record
+        ``k`` client ``k``'s.  ``rows``: the device ``[K, ld]`` fp32 buffer.  Entries go longest batch first (the
+        hardware starts workgroups in order), each with ``row`` = its client's position."""
+        table, rec, coef = self._buffers(iters if adam else 0)
+        order = sorted(range(self.K), key=lambda k: -self.B[k])
+        table.numpy()[:self.K] = [(self.x[k].data_ptr(), self.labels[k].data_ptr(), self.B[k], k) for k in order]
+        if adam:
+            for t in range(iters):
+                coef[t] = torch.from_numpy(adam_coef(lr, *adam, t + 1))
+        st = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device), torch.no_grad():
+            model = torch.cat([self.w.detach().reshape(-1), self.b.detach()])
+            rc = _lib.load_clientcohort().fedavg_client_cohort_f32(
+                model.data_ptr(), rows.data_ptr(), rows.stride(0), table.data_ptr(), self.K, self.D, self.C, iters,
+                activation, 1 if adam else 0, float(lr), float(lr_ratio), self.form,
+                coef.data_ptr() if adam else None, rec.data_ptr(), st.cuda_stream)
+        _lib.check_clientcohort(rc, "fedavg_client_cohort_f32")
+        st.synchronize()
+        return rec[:self.K].tolist()

@@ -68,7 +68,7 @@ import torch
 
 from . import _lib
 from .client_forms import _ADAM_PROBE, _mine_site_c, _probe_adam_form, _probe_sgd_form, _probe_values  # noqa: F401
-from .client_passes import (ADAM_SITES, FUSED_DTYPES, LINEAR_LOOPS, _RULE, _STEP_SUFFIX, _AdamPass,  # noqa: F401
+from .client_passes import (ADAM_SITES, FUSED_DTYPES, LINEAR_LOOPS, _RULE, _STEP_SUFFIX, _AdamPass, _Cohort,  # noqa: F401
                             _KeyPass, _LinearLoop, _STATS_LIBS, _StepPass, _fused_ok, _guard_bound, _norm_of, _round_to, adam_coef)
 
 # rec: one device record of doubles, read back in one D2H.  The device guard adds the previous loss, the gate and
@@ -599,6 +599,79 @@ def _linear_train(self, net, local_iteration, loop, keep_on_device, mod):
             logger.warning("grads too large than weights or meets nan with epoch {}".format(int(trip)))
         return sd, None, None, None, None, None
     return sd, loss, beta, rho, correct / plan.B, cycles
+
+
+class CohortResult:
+    """What :func:`cohort_train` leaves: ``rows``, the device ``[K, ld]`` fp32 tensor whose row ``k`` holds client
+    ``k``'s trained weight and bias in state_dict order (columns from ``P`` on are not written); ``P``;
+    ``results[k]``, the reference's ``(loss, beta, rho, acc)`` or four ``None`` after a tripped guard;
+    ``sample_numbers[k]``."""
+
+    def __init__(self, rows, P, results, sample_numbers, names, shape):
+        self.rows, self.P, self.results, self.sample_numbers = rows, P, results, sample_numbers
+        self._names, self._shape = names, shape
+
+    def state_dict(self, k, cpu=False):
+        """Client ``k``'s state_dict: views of row ``k``, or a ``.cpu()`` copy of them."""
+        C, D = self._shape
+        row = self.rows[k].cpu() if cpu else self.rows[k]
+        return {self._names[0]: row[:C * D].view(C, D), self._names[1]: row[C * D:self.P]}
+
+
+def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None):
+    """A round's clients (fedavg_trainer.py:172-199: each trained from the same global model ``net``) under
+    ``loop="linear"`` / ``"linear_sigmoid"`` as ONE launch of ``fedavg_client_cohort_f32``, one workgroup per client,
+    one host sync and one read of the ``[K, 8]`` records.  ``clients`` are reference ``Client`` objects that share
+    ``args``; each one's batch is drawn as client.py:48-49 draws it.  ``net`` is not modified: client ``k``'s trained
+    parameters go to row ``k`` of ``rows`` (device fp32 ``[K, ld]``, allocated with ``ld`` rounded up to
+    ``ALIGN_ELEMS`` unless passed), the packed layout the reduce reads, so the round's aggregate is
+    ``reduce_with_sqdist(res.rows, weights_tensor(sample_weights(res.sample_numbers), torch.float32, device), res.P)``.
+    The rules of ``client_train(loop="linear")`` hold for the model and for every batch (``TypeError`` before anything
+    runs); a label outside ``[0, C)`` raises ``IndexError`` naming the client's position after the launch, with
+    ``net`` untouched.  Returns a :class:`CohortResult`."""
+    from .reduce import ALIGN_ELEMS
+
+    if loop not in LINEAR_LOOPS:
+        raise ValueError(f"loop must be 'linear' or 'linear_sigmoid', not {loop!r}")
+    if local_iteration <= 0:
+        raise ValueError("cohort_train needs local_iteration >= 1")
+    clients = list(clients)
+    if not clients:
+        raise ValueError("cohort_train needs at least one client")
+    args = clients[0].args
+    key = lambda a: (a.client_optimizer, a.lr, a.wd)  # noqa: E731
+    if any(key(c.args) != key(args) for c in clients):
+        raise ValueError("the clients of a cohort share client_optimizer, lr and wd")
+    mod = sys.modules[type(clients[0]).__module__]
+    sgd = args.client_optimizer == "sgd"
+    batches = []
+    for c in clients:
+        x, labels = next(iter(c.local_training_data))
+        batches.append((x.to(c.device), labels.to(c.device)))
+    form_of = (lambda dev: sgd_form(dev, torch.float32)) if sgd else (lambda dev: adam_form(dev, torch.float32))
+    names = [n for n, _ in net.named_parameters()]
+    plan = _Cohort(net.parameters(), batches, clients[0].criterion, form_of)  # refused, if it is, before anything runs
+    ld = -(-plan.P // ALIGN_ELEMS) * ALIGN_ELEMS
+    if rows is None:
+        rows = torch.empty(plan.K, ld, dtype=torch.float32, device=plan.device)
+    elif not (rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[0] == plan.K and rows.shape[1] >= plan.P
+              and rows.stride(1) == 1 and rows.stride(0) >= rows.shape[1] and rows.device == plan.device):
+        raise TypeError(f"rows is no fp32 [{plan.K}, >= {plan.P}] tensor with contiguous rows on {plan.device}")
+    recs = plan.run(rows, local_iteration, LINEAR_LOOPS[loop], args.lr, args.lr * mod.THRESHOLD_GRADS_RATIO,
+                    None if sgd else (0.9, 0.999, 1e-8, args.wd))
+    bad = [k for k, rec in enumerate(recs) if rec[5]]
+    if bad:
+        raise IndexError(f"client {bad[0]}: a label lies outside [0, {plan.C}): the kernel refused the batch and "
+                         "left the model untouched")
+    results = []
+    for k, (trip, loss, beta, rho, correct, *_) in enumerate(recs):
+        if trip >= 0:
+            logger = getattr(mod, "logger", None)
+            if logger is not None:
+                logger.warning("grads too large than weights or meets nan with epoch {}".format(int(trip)))
+        results.append((None,) * 4 if trip >= 0 else (loss, beta, rho, correct / plan.B[k]))
+    return CohortResult(rows, plan.P, results, [getattr(c, "local_sample_number", B) for c, B in zip(clients, plan.B)],
+                        names, (plan.C, plan.D))
 
 
 def client_train(self, net, local_iteration, *, keep_on_device=False, stats="auto", trace=None, step="torch",
