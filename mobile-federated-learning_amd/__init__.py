@@ -16,7 +16,8 @@ Layers:
   fpf                      FPF2 bookkeeping (local_w_diffs / A_mat / G_mat) in HBM
   client_stats             Client.train's rho / beta / guard statistics, one fused pass per step
   client_passes            its native calls' buffers and the reuse rule of their pinned key tables; the whole
-                           local loop of a linear softmax client as one launch (client_train(loop="linear"))
+                           local loop of a linear softmax client as one launch (client_train(loop="linear")); the
+                           evaluation of a linear model on every client's dataset as one call (local_test_all)
   client_forms             the probes behind sgd_form / adam_form, once per (device, dtype)
 """
 from ._lib import FedAvgLibraryError, library_path
@@ -37,8 +38,8 @@ from .session import RoundSession
 from .multi import ShardedAggregator, ShardedRoundSession, sharded_aggregator
 from .fpf import FPFTracker
 from . import client_stats
-from .client_stats import (ADAM_DTYPES, DEFAULT_AHEAD, ClientStepStats, CohortResult, adam_form, adam_form_probe,
-                           client_train, cohort_train)
+from .client_stats import (ADAM_DTYPES, DEFAULT_AHEAD, ClientStepStats, CohortResult, EvalSet, adam_form,
+                           adam_form_probe, client_train, cohort_test, cohort_train, local_test_all)
 
 __all__ = [
     "FedAvgLibraryError",
@@ -71,6 +72,9 @@ __all__ = [
     "client_train",
     "cohort_train",
     "CohortResult",
+    "EvalSet",
+    "cohort_test",
+    "local_test_all",
     "ADAM_DTYPES",
     "adam_form",
     "adam_form_probe",

@@ -11,7 +11,7 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCOHORT_LIB_PATH, COHORT_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
+from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCOHORT_LIB_PATH, CLIENTEVAL_LIB_PATH, COHORT_BY_KEY, EVAL_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
                     CLIENTVEC_LIB_PATH, DESCRIBED, EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, LINEAR_BY_KEY, PROBE_LIB_PATH,
                     SEGVEC_LIB_PATH, STREAM_BY_KEY, NativeLib)
 
@@ -232,6 +232,15 @@ CLIENTCOHORT_SIGNATURES = {
                                           ctypes.c_double, ctypes.c_double, _c_int, _vp, _vp, _vp]),
 }
 
+# libfedavg_amd_clienteval.so (include/fedavg_amd_clienteval.h)
+CLIENTEVAL_SIGNATURES = {
+    "fedavg_clienteval_abi_version": (_c_int, []),
+    "fedavg_clienteval_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_eval_limits": (None, [_vp, _vp, _vp, _vp]),
+    "fedavg_client_eval_workspace_bytes": (_c_i64, [_vp, _c_i64, _c_i64]),
+    "fedavg_client_eval_f32": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _vp]),
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
@@ -242,6 +251,7 @@ CLIENTLOOP_ABI_VERSION = EXTRA_BY_KEY["clientloop"].abi[1]
 CLIENTLINEAR_ABI_VERSION = LINEAR_BY_KEY["clientlinear"].abi[1]
 CLIENTSTREAM_ABI_VERSION = STREAM_BY_KEY["clientstream"].abi[1]
 CLIENTCOHORT_ABI_VERSION = COHORT_BY_KEY["clientcohort"].abi[1]
+CLIENTEVAL_ABI_VERSION = EVAL_BY_KEY["clienteval"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -287,6 +297,10 @@ _STREAM_BINDING = {
 _COHORT_BINDING = {
     "clientcohort": ((CLIENTCOHORT_SIGNATURES,), "CLIENTCOHORT_LIB_PATH", "_clientcohort"),
 }
+# the same for the libraries of build.EVAL_BY_KEY (a new one goes here)
+_EVAL_BINDING = {
+    "clienteval": ((CLIENTEVAL_SIGNATURES,), "CLIENTEVAL_LIB_PATH", "_clienteval"),
+}
 
 _lock = threading.Lock()
 _lib = None
@@ -300,6 +314,7 @@ _clientloop = None
 _clientlinear = None
 _clientstream = None
 _clientcohort = None
+_clienteval = None
 
 
 def library_path() -> Path:
@@ -310,12 +325,12 @@ def _load(d: NativeLib) -> ctypes.CDLL:
     """Load (once), type and version-check the library ``d`` describes.  No
     fallback: a missing, unloadable or stale library raises ``FedAvgLibraryError``."""
     tables, path_name, slot = next(t[d.key] for t in (_BINDING, _EXTRA_BINDING, _LINEAR_BINDING, _STREAM_BINDING,
-                                                      _COHORT_BINDING) if d.key in t)
+                                                      _COHORT_BINDING, _EVAL_BINDING) if d.key in t)
     g = globals()
     if g[slot] is not None:
         return g[slot]
     if d.needs:
-        _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY, STREAM_BY_KEY, COHORT_BY_KEY)
+        _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY, STREAM_BY_KEY, COHORT_BY_KEY, EVAL_BY_KEY)
                    if d.needs in t))
     with _lock:
         if g[slot] is not None:
@@ -409,6 +424,11 @@ def load_clientcohort() -> ctypes.CDLL:
     return _clientcohort if _clientcohort is not None else _load(COHORT_BY_KEY["clientcohort"])
 
 
+def load_clienteval() -> ctypes.CDLL:
+    """The one-call evaluation of linear softmax clients, fp32 (include/fedavg_amd_clienteval.h)."""
+    return _clienteval if _clienteval is not None else _load(EVAL_BY_KEY["clienteval"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
@@ -438,6 +458,11 @@ def check_clientstream(rc: int, what: str) -> None:
 def check_clientcohort(rc: int, what: str) -> None:
     """``_check`` for the client cohort library (its description read at call time)."""
     _check(COHORT_BY_KEY["clientcohort"], rc, what)
+
+
+def check_clienteval(rc: int, what: str) -> None:
+    """``_check`` for the client evaluation library (its description read at call time)."""
+    _check(EVAL_BY_KEY["clienteval"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

@@ -3,7 +3,8 @@ over a model's tensors and the reuse rule of its pinned key table
 (:class:`_KeyPass`), the fused SGD and Adam steps as its users, the statistics
 library per dtype, the host side of the :71 guard's arithmetic and the whole
 local loop of a linear softmax client as one launch (:class:`_LinearLoop`), or of a
-round's whole cohort of them (:class:`_Cohort`)."""
+round's whole cohort of them (:class:`_Cohort`), and the evaluation of a linear
+model on every client's dataset as one call (:class:`EvalSet`)."""
 from __future__ import annotations
 
 import ctypes
@@ -364,3 +365,91 @@ class _Cohort:
         _lib.check_clientcohort(rc, "fedavg_client_cohort_f32")
         st.synchronize()
         return rec[:self.K].tolist()
+
+
+# ------------------------------------------------------------------ every client's evaluation, one call
+EVAL_CHUNK_ROWS = 256  # the kernel's unit of work: a run of at most this many rows of one client
+_EVAL_RULE = ("the one-call evaluation needs a model of exactly two parameters, a contiguous fp32 [C, D] weight and a "
+              "[C] bias on the set's GPU; per client one batch whose x.flatten(1) is fp32 with D columns and whose "
+              "labels are int64 of its length; a default nn.CrossEntropyLoss; sizes inside fedavg_client_eval_limits")
+
+
+def eval_limits():
+    """``(max K, max B, max D, max C)`` of ``fedavg_client_eval_limits``."""
+    out = [ctypes.c_int64() for _ in range(4)]
+    _lib.load_clienteval().fedavg_client_eval_limits(*[ctypes.byref(v) for v in out])
+    return tuple(v.value for v in out)
+
+
+class EvalSet:
+    """The datasets one ``fedavg_client_eval_f32`` call evaluates a model on: each loader's one batch, drawn as
+    client.py:108-109 draws it (the batch is the client's whole dataset, main_fedavg.py:232), flattened and uploaded
+    to ``device``; the pinned client table, longest batch first, each entry's ``slot`` its position among the loaders
+    that are not ``None`` (those are skipped, as fedavg_trainer.py:483 skips them); the workspace and the pinned
+    records.  Built once and reused for every later evaluation.  The batch rules are checked here and the model's in
+    :meth:`run` (``TypeError`` naming the rule, before anything runs)."""
+
+    def __init__(self, loaders, device, criterion=None):
+        def refuse(why):
+            raise TypeError(f"{why}: {_EVAL_RULE}")
+
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            refuse(f"{self.device} is no GPU")
+        if criterion is not None and not (
+                type(criterion) is torch.nn.CrossEntropyLoss and criterion.reduction == "mean" and criterion.weight is None
+                and criterion.label_smoothing == 0.0 and criterion.ignore_index == -100):
+            refuse("the criterion is no default nn.CrossEntropyLoss")
+        max_k, max_b, max_d, _ = eval_limits()
+        loaders = list(loaders)
+        self.n, self.positions, self.x, self.labels, self.D = len(loaders), [], [], [], None
+        for pos, loader in enumerate(loaders):
+            if loader is None:
+                continue
+            x, labels = next(iter(loader))
+            B = x.shape[0] if x.dim() >= 2 else 0
+            if self.D is None and B:
+                self.D = x.flatten(1).shape[1]
+            if not (x.dtype == torch.float32 and 1 <= B <= max_b and 1 <= self.D <= max_d
+                    and x.flatten(1).shape[1] == self.D and labels.dtype == torch.int64 and labels.shape == (B,)):
+                refuse(f"client {pos}: no fp32 batch of 1 to {max_b} rows of {self.D} (at most {max_d}) columns with "
+                       "int64 labels of its length")
+            self.positions.append(pos)
+            self.x.append(x.to(self.device).flatten(1).contiguous())
+            self.labels.append(labels.to(self.device).contiguous())
+        self.K = len(self.x)
+        if not 1 <= self.K <= max_k:
+            refuse(f"{self.K} clients with data lie outside 1 to {max_k}")
+        self.B = [x.shape[0] for x in self.x]
+        order = sorted(range(self.K), key=lambda k: -self.B[k])
+        with torch.cuda.device(self.device):
+            self.table = torch.zeros(self.K, 4, dtype=torch.int64, pin_memory=True)
+            self.rec = torch.zeros(self.K, 4, dtype=torch.float64, pin_memory=True)
+        self.table.numpy()[:] = [(self.x[k].data_ptr(), self.labels[k].data_ptr(), self.B[k], k) for k in order]
+        need = _lib.load_clienteval().fedavg_client_eval_workspace_bytes(self.table.data_ptr(), self.K, self.D)
+        if need < 0:
+            _lib.check_clienteval(int(need), "fedavg_client_eval_workspace_bytes")
+        self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    def run(self, params, activation):
+        """One call on the current stream and the one host sync; returns ``(C, records)``, record ``k`` =
+        ``[loss sum, correct count, label flag, B]`` of the ``k``-th loader that is not ``None``."""
+        params = list(params)
+        if len(params) != 2:
+            raise TypeError(f"the model has {len(params)} parameters, not two: {_EVAL_RULE}")
+        w, b = params
+        _, _, _, max_c = eval_limits()
+        if not (w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and w.shape[1] == self.D
+                and 2 <= w.shape[0] <= max_c and b.dtype == torch.float32 and b.shape == (w.shape[0],)
+                and b.is_contiguous() and w.device == self.device and b.device == self.device):
+            raise TypeError(f"the parameters are no contiguous fp32 [C, {self.D}] weight and [C] bias with "
+                            f"2 <= C <= {max_c} on {self.device}: {_EVAL_RULE}")
+        st = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device), torch.no_grad():
+            model = torch.cat([w.detach().reshape(-1), b.detach()])
+            rc = _lib.load_clienteval().fedavg_client_eval_f32(
+                model.data_ptr(), self.table.data_ptr(), self.K, self.D, w.shape[0], activation, self.rec.data_ptr(),
+                self.workspace.data_ptr(), self.workspace.numel(), st.cuda_stream)
+        _lib.check_clienteval(rc, "fedavg_client_eval_f32")
+        st.synchronize()
+        return w.shape[0], self.rec.tolist()

@@ -68,7 +68,7 @@ import torch
 
 from . import _lib
 from .client_forms import _ADAM_PROBE, _mine_site_c, _probe_adam_form, _probe_sgd_form, _probe_values  # noqa: F401
-from .client_passes import (ADAM_SITES, FUSED_DTYPES, LINEAR_LOOPS, _RULE, _STEP_SUFFIX, _AdamPass, _Cohort,  # noqa: F401
+from .client_passes import (ADAM_SITES, FUSED_DTYPES, LINEAR_LOOPS, _RULE, _STEP_SUFFIX, EvalSet, _AdamPass, _Cohort,  # noqa: F401
                             _KeyPass, _LinearLoop, _STATS_LIBS, _StepPass, _fused_ok, _guard_bound, _norm_of, _round_to, adam_coef)
 
 # rec: one device record of doubles, read back in one D2H.  The device guard adds the previous loss, the gate and
@@ -672,6 +672,69 @@ def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None):
         results.append((None,) * 4 if trip >= 0 else (loss, beta, rho, correct / plan.B[k]))
     return CohortResult(rows, plan.P, results, [getattr(c, "local_sample_number", B) for c, B in zip(clients, plan.B)],
                         names, (plan.C, plan.D))
+
+
+def cohort_test(net, evalset, *, loop="linear"):
+    """``Client.local_test`` (client.py:99-120) of ``net`` on every dataset of ``evalset`` (an :class:`EvalSet`) as ONE
+    call of ``fedavg_client_eval_f32`` and one host sync.  ``net.eval()`` is called, as :100 calls it, and the
+    parameters are only read.  Returns one entry per loader the set was built from: the reference's
+    ``{'test_correct': int, 'test_loss': float, 'test_total': int}`` (the loss is the SUM over the client's samples,
+    ``loss.item() * B`` there), or ``None`` where the loader was ``None``.  The model rules are those of
+    ``client_train(loop="linear")`` without the step's (``TypeError`` before anything runs); a label outside
+    ``[0, C)`` raises ``IndexError`` naming the client's position."""
+    if loop not in LINEAR_LOOPS:
+        raise ValueError(f"loop must be 'linear' or 'linear_sigmoid', not {loop!r}")
+    net.eval()
+    C, recs = evalset.run(net.parameters(), LINEAR_LOOPS[loop])
+    out = [None] * evalset.n
+    for pos, (loss, correct, bad_label, total) in zip(evalset.positions, recs):
+        if bad_label:
+            raise IndexError(f"client {pos}: a label lies outside [0, {C}): the sample was left out of the sums")
+        out[pos] = {"test_correct": int(correct), "test_loss": float(loss), "test_total": int(total)}
+    return out
+
+
+def local_test_all(trainer, model_global, round_idx, eval_on_train=False, if_log=True, *, loop="linear", sets=None):
+    """``FedAvgTrainer.local_test_on_all_clients`` (fedavg_trainer.py:461-529) on :func:`cohort_test`: one call per
+    set instead of one torch forward and two host syncs per client and set.  The clients are
+    ``range(min(client_num_in_total, trainer.client_num))`` without those whose test loader is ``None`` or that are in
+    ``trainer.invalid_datasets`` (:483); ``client_num_in_total``, ``logger`` and ``wandb`` are those of the module
+    that defines the trainer's class.  ``sets``: ``{"test": EvalSet, "train": EvalSet}`` over exactly those clients;
+    when not passed they are built on first use (on ``trainer.device`` if it has one, else the model's) and kept on
+    the trainer as ``_mfl_eval_sets``, since a client's batch is its whole dataset.  Returns the reference's
+    ``(test_acc, per-client train accuracies or None)`` and logs the same ``stats``."""
+    mod = sys.modules[type(trainer).__module__]
+    logger, wandb = getattr(mod, "logger", None), getattr(mod, "wandb", None)
+    if logger is not None:
+        logger.info("################local_test_on_all_clients : {}".format(round_idx))
+    device = getattr(trainer, "device", None) or next(model_global.parameters()).device
+    model_global.to(device)
+    if sets is None:
+        sets = trainer.__dict__.setdefault("_mfl_eval_sets", {})
+    clients = [i for i in range(min(int(mod.client_num_in_total), trainer.client_num))
+               if trainer.test_data_local_dict[i] is not None and i not in trainer.invalid_datasets.keys()]
+
+    def metrics(which, data):
+        if which not in sets:
+            sets[which] = EvalSet([data[i] for i in clients], device)
+        res = cohort_test(model_global, sets[which], loop=loop)
+        return [m["test_total"] for m in res], [m["test_correct"] for m in res], [m["test_loss"] for m in res]
+
+    samples, correct, losses = metrics("test", trainer.test_data_local_dict)
+    test_acc = sum(correct) / sum(samples)
+    stats = {"Test/Acc": test_acc, "Test/Loss": sum(losses) / sum(samples), "round": round_idx,
+             "cum_time": trainer.time_counter + trainer.cycle_num * 59361}
+    train_acc = None
+    if eval_on_train:
+        samples, correct, losses = metrics("train", trainer.train_data_local_dict)
+        stats.update({"Train/Acc": sum(correct) / sum(samples), "Train/Loss": sum(losses) / sum(samples)})
+        train_acc = np.array(correct) / np.array(samples)
+    if if_log:
+        if logger is not None:
+            logger.info(stats)
+        if wandb is not None:
+            wandb.log(stats)
+    return test_acc, train_acc
 
 
 def client_train(self, net, local_iteration, *, keep_on_device=False, stats="auto", trace=None, step="torch",
