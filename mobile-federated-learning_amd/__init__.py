@@ -17,7 +17,8 @@ Layers:
   client_stats             Client.train's rho / beta / guard statistics, one fused pass per step
   client_passes            its native calls' buffers and the reuse rule of their pinned key tables; the whole
                            local loop of a linear softmax client as one launch (client_train(loop="linear")); the
-                           evaluation of a linear model on every client's dataset as one call (local_test_all)
+                           evaluation of a linear model on every client's dataset as one call (local_test_all);
+                           central_train's chain of steps over all clients' batches as one launch (chain_train)
   client_forms             the probes behind sgd_form / adam_form, once per (device, dtype)
 """
 from ._lib import FedAvgLibraryError, library_path
@@ -39,7 +40,8 @@ from .multi import ShardedAggregator, ShardedRoundSession, sharded_aggregator
 from .fpf import FPFTracker
 from . import client_stats
 from .client_stats import (ADAM_DTYPES, DEFAULT_AHEAD, ClientStepStats, CohortResult, EvalSet, adam_form,
-                           adam_form_probe, client_train, cohort_test, cohort_train, local_test_all)
+                           adam_form_probe, central_train, chain_train, client_train, cohort_test, cohort_train,
+                           local_test_all)
 
 __all__ = [
     "FedAvgLibraryError",
@@ -75,6 +77,8 @@ __all__ = [
     "EvalSet",
     "cohort_test",
     "local_test_all",
+    "chain_train",
+    "central_train",
     "ADAM_DTYPES",
     "adam_form",
     "adam_form_probe",

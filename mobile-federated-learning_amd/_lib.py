@@ -11,7 +11,7 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import (BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCOHORT_LIB_PATH, CLIENTEVAL_LIB_PATH, COHORT_BY_KEY, EVAL_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
+from .build import (BY_KEY, CHAIN_BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCHAIN_LIB_PATH, CLIENTCOHORT_LIB_PATH, CLIENTEVAL_LIB_PATH, COHORT_BY_KEY, EVAL_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
                     CLIENTVEC_LIB_PATH, DESCRIBED, EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, LINEAR_BY_KEY, PROBE_LIB_PATH,
                     SEGVEC_LIB_PATH, STREAM_BY_KEY, NativeLib)
 
@@ -241,6 +241,15 @@ CLIENTEVAL_SIGNATURES = {
     "fedavg_client_eval_f32": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _vp, _vp, _c_i64, _vp]),
 }
 
+# libfedavg_amd_clientchain.so (include/fedavg_amd_clientchain.h)
+CLIENTCHAIN_SIGNATURES = {
+    "fedavg_clientchain_abi_version": (_c_int, []),
+    "fedavg_clientchain_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_chain_limits": (None, [_vp, _vp, _vp, _vp]),
+    "fedavg_client_chain_f32": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int,
+                                         ctypes.c_double, _c_int, _vp, _vp, _vp, _vp]),
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
@@ -252,6 +261,7 @@ CLIENTLINEAR_ABI_VERSION = LINEAR_BY_KEY["clientlinear"].abi[1]
 CLIENTSTREAM_ABI_VERSION = STREAM_BY_KEY["clientstream"].abi[1]
 CLIENTCOHORT_ABI_VERSION = COHORT_BY_KEY["clientcohort"].abi[1]
 CLIENTEVAL_ABI_VERSION = EVAL_BY_KEY["clienteval"].abi[1]
+CLIENTCHAIN_ABI_VERSION = CHAIN_BY_KEY["clientchain"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -301,6 +311,10 @@ _COHORT_BINDING = {
 _EVAL_BINDING = {
     "clienteval": ((CLIENTEVAL_SIGNATURES,), "CLIENTEVAL_LIB_PATH", "_clienteval"),
 }
+# the same for the libraries of build.CHAIN_BY_KEY (a new one goes here)
+_CHAIN_BINDING = {
+    "clientchain": ((CLIENTCHAIN_SIGNATURES,), "CLIENTCHAIN_LIB_PATH", "_clientchain"),
+}
 
 _lock = threading.Lock()
 _lib = None
@@ -315,6 +329,7 @@ _clientlinear = None
 _clientstream = None
 _clientcohort = None
 _clienteval = None
+_clientchain = None
 
 
 def library_path() -> Path:
@@ -325,13 +340,13 @@ def _load(d: NativeLib) -> ctypes.CDLL:
     """Load (once), type and version-check the library ``d`` describes.  No
     fallback: a missing, unloadable or stale library raises ``FedAvgLibraryError``."""
     tables, path_name, slot = next(t[d.key] for t in (_BINDING, _EXTRA_BINDING, _LINEAR_BINDING, _STREAM_BINDING,
-                                                      _COHORT_BINDING, _EVAL_BINDING) if d.key in t)
+                                                      _COHORT_BINDING, _EVAL_BINDING, _CHAIN_BINDING) if d.key in t)
     g = globals()
     if g[slot] is not None:
         return g[slot]
     if d.needs:
-        _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY, STREAM_BY_KEY, COHORT_BY_KEY, EVAL_BY_KEY)
-                   if d.needs in t))
+        _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY, STREAM_BY_KEY, COHORT_BY_KEY, EVAL_BY_KEY,
+                                          CHAIN_BY_KEY) if d.needs in t))
     with _lock:
         if g[slot] is not None:
             return g[slot]
@@ -429,6 +444,11 @@ def load_clienteval() -> ctypes.CDLL:
     return _clienteval if _clienteval is not None else _load(EVAL_BY_KEY["clienteval"])
 
 
+def load_clientchain() -> ctypes.CDLL:
+    """The one-launch chain of central training steps of a linear model, fp32 (include/fedavg_amd_clientchain.h)."""
+    return _clientchain if _clientchain is not None else _load(CHAIN_BY_KEY["clientchain"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
@@ -463,6 +483,11 @@ def check_clientcohort(rc: int, what: str) -> None:
 def check_clienteval(rc: int, what: str) -> None:
     """``_check`` for the client evaluation library (its description read at call time)."""
     _check(EVAL_BY_KEY["clienteval"], rc, what)
+
+
+def check_clientchain(rc: int, what: str) -> None:
+    """``_check`` for the central training chain library (its description read at call time)."""
+    _check(CHAIN_BY_KEY["clientchain"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

@@ -16,10 +16,12 @@ pins to that one key.  The tenth, and any after it, is described in
 ``STREAM_LIBS`` / ``STREAM_BY_KEY``, which tests/test_clientstream_abi.py pins
 to that one key.  The eleventh, and any after it, is described in
 ``COHORT_LIBS`` / ``COHORT_BY_KEY``, which tests/test_clientcohort_abi.py pins
-to that one key.  The twelfth, and any after it, is described in ``EVAL_LIBS``
-/ ``EVAL_BY_KEY`` (a new one goes there);
-``BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS`` is what ``sources()``,
-the up-to-date rule and ``build()`` cover, and ``_lib`` loads a library from
+to that one key.  The twelfth is described in ``EVAL_LIBS`` / ``EVAL_BY_KEY``,
+which tests/test_clienteval_abi.py pins to that one key.  The thirteenth, and
+any after it, is described in ``CHAIN_LIBS`` / ``CHAIN_BY_KEY``, which no test
+pins to one key (a new one goes there);
+``BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS + CHAIN_LIBS``
+(``described_libs()``) is what ``sources()``, the up-to-date rule and ``build()`` cover, and ``_lib`` loads a library from
 the by-key table that holds it.
 
 Every translation unit of ``BUILT_LIBS`` is compiled in parallel with hipcc for
@@ -190,6 +192,24 @@ EVAL_LIBS = (
 )
 EVAL_BY_KEY = {lib.key: lib for lib in EVAL_LIBS}
 CLIENTEVAL_LIB_PATH = EVAL_BY_KEY["clienteval"].path
+# libraries added after those twelve (a new one goes here: see the module docstring)
+CHAIN_LIBS = (
+    # central_train's chain of steps for a linear model in one launch: one persistent workgroup, the clients' batches
+    # streamed through LDS one after another, the model and the optimizer state in registers, fp32; calls no other
+    # library.  Compiled without packed fp32 instructions.
+    NativeLib("clientchain", "libfedavg_amd_clientchain.so", "fedavg_amd_clientchain.h",
+              ("fedavg_client_chain.hip",), abi=("fedavg_clientchain_abi_version", 1),
+              last_error="fedavg_clientchain_last_error",
+              no_fallback="; there is no fallback for the one-launch chain of central training steps",
+              defines=("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")),
+)
+CHAIN_BY_KEY = {lib.key: lib for lib in CHAIN_LIBS}
+CLIENTCHAIN_LIB_PATH = CHAIN_BY_KEY["clientchain"].path
+
+
+def described_libs():
+    """Every described library, in link order (the tuples are read when called, so a test that patches one is served)."""
+    return BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS + CHAIN_LIBS
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",
@@ -217,8 +237,7 @@ def hipcc_path() -> str:
 def sources():
     """Everything a library can depend on: every translation unit, every
     header in csrc/ and include/ (found, not listed) and this recipe."""
-    units = dict.fromkeys(src for lib in BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS
-                          for src in lib.sources)
+    units = dict.fromkeys(src for lib in described_libs() for src in lib.sources)
     return [*units, *sorted(CSRC_DIR.glob("*.hpp")), *sorted(INCLUDE.glob("*.h")), Path(__file__)]
 
 
@@ -229,10 +248,11 @@ def up_to_date() -> bool:
 
 def later_up_to_date() -> bool:
     """The same rule for ``LATER_LIBS``, ``NEWER_LIBS``, ``EXTRA_LIBS``, ``LINEAR_LIBS``, ``STREAM_LIBS``,
-    ``COHORT_LIBS`` and ``EVAL_LIBS``: each built and no older than the newest source."""
+    ``COHORT_LIBS``, ``EVAL_LIBS`` and ``CHAIN_LIBS``: each built and no older than the newest source."""
     newest = max(p.stat().st_mtime for p in sources())
     return all(lib.path.exists() and lib.path.stat().st_mtime >= newest
-               for lib in LATER_LIBS + NEWER_LIBS + EXTRA_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS)
+               for lib in LATER_LIBS + NEWER_LIBS + EXTRA_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS
+               + CHAIN_LIBS)
 
 
 def collect_ext_path() -> Path:
@@ -287,14 +307,15 @@ def _link(objs, lib_path, verbose, extra=()):
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Build every library of ``BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS``; returns the product library's path."""
+    """Build every library of ``described_libs()``; returns the product library's path."""
     if not force and up_to_date() and later_up_to_date():
         return LIB_PATH
-    libs = BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS
+    libs = described_libs()
     for lib in libs:
         (LIB_DIR / lib.obj_dir).mkdir(parents=True, exist_ok=True)
     _compile_all([(CSRC_DIR / u, lib.obj(u), list(lib.defines)) for lib in libs for u in lib.units], verbose)
-    by_key = {**DESCRIBED, **EXTRA_BY_KEY, **LINEAR_BY_KEY, **STREAM_BY_KEY, **COHORT_BY_KEY, **EVAL_BY_KEY}
+    by_key = {**DESCRIBED, **EXTRA_BY_KEY, **LINEAR_BY_KEY, **STREAM_BY_KEY, **COHORT_BY_KEY, **EVAL_BY_KEY,
+              **CHAIN_BY_KEY}
     for lib in libs:  # in order: a library links after the one its link arguments name
         objs = [lib.obj(u) for u in lib.units] + [by_key[key].obj(u) for key, u in lib.reuse]
         _link(objs, lib.path, verbose, extra=lib.link)

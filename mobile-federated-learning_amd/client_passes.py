@@ -3,8 +3,9 @@ over a model's tensors and the reuse rule of its pinned key table
 (:class:`_KeyPass`), the fused SGD and Adam steps as its users, the statistics
 library per dtype, the host side of the :71 guard's arithmetic and the whole
 local loop of a linear softmax client as one launch (:class:`_LinearLoop`), or of a
-round's whole cohort of them (:class:`_Cohort`), and the evaluation of a linear
-model on every client's dataset as one call (:class:`EvalSet`)."""
+round's whole cohort of them (:class:`_Cohort`), the evaluation of a linear
+model on every client's dataset as one call (:class:`EvalSet`), and central
+training's chain of steps over every client's batch (:class:`_Chain`)."""
 from __future__ import annotations
 
 import ctypes
@@ -365,6 +366,84 @@ class _Cohort:
         _lib.check_clientcohort(rc, "fedavg_client_cohort_f32")
         st.synchronize()
         return rec[:self.K].tolist()
+
+
+# ------------------------------------------------------------------ central_train's chain of steps, one launch
+def chain_limits():
+    """``(max K, max B, max D, max C)`` of ``fedavg_client_chain_limits``."""
+    out = [ctypes.c_int64() for _ in range(4)]
+    _lib.load_clientchain().fedavg_client_chain_limits(*[ctypes.byref(v) for v in out])
+    return tuple(v.value for v in out)
+
+
+def adam_coef_rows(lr, beta1, beta2, eps, weight_decay, first, n):
+    """Rows ``[n, 7]`` of :func:`adam_coef` for the steps ``first .. first + n - 1`` (from 1): the constant columns
+    filled at once, the three powers of a row in Python floats exactly as torch/optim/adam.py forms them."""
+    rows = np.empty((n, 7), dtype=np.float64)
+    rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], rows[:, 5] = weight_decay, 1 - beta1, beta2, 1 - beta2, eps
+    ts = [float(t) for t in range(first, first + n)]
+    rows[:, 4] = [(1 - beta2 ** t) ** 0.5 for t in ts]
+    rows[:, 6] = [(lr / (1 - beta1 ** t)) * -1 for t in ts]
+    return rows
+
+
+class _Chain:
+    """The ``fedavg_client_chain_f32`` calls of one chain: one model stepped on every batch of ``batches`` in their
+    order, round after round.  The :class:`_LinearLoop` rules are checked once for the model (with the first batch)
+    and per client for the batch (``TypeError`` naming the rule, before anything runs).  The plan keeps the pinned
+    client table in client order, the pinned losses and record, and on the device Adam's coefficient rows and its
+    ``m, v, vmax``."""
+
+    def __init__(self, params, batches, form_of):
+        first = _LinearLoop(params, *batches[0], torch.nn.CrossEntropyLoss(), form_of)
+        self.w, self.b, self.form, self.D, self.C, self.device = first.w, first.b, first.form, first.D, first.C, first.device
+        max_k, max_b, _, _ = chain_limits()
+        if len(batches) > max_k:
+            raise TypeError(f"a chain over {len(batches)} clients exceeds {max_k}: {_LINEAR_RULE}")
+        self.x, self.labels = [first.x], [first.labels]
+        for k, (x, labels) in enumerate(batches[1:], 1):
+            B = x.shape[0] if x.dim() >= 2 else 0
+            if not (x.dtype == torch.float32 and 1 <= B <= max_b and x.flatten(1).shape[1] == self.D
+                    and labels.dtype == torch.int64 and labels.shape == (B,)
+                    and x.device == self.device and labels.device == self.device):
+                raise TypeError(f"client {k}: no fp32 batch of 1 to {max_b} rows of {self.D} columns with int64 labels "
+                                f"of its length on {self.device}: {_LINEAR_RULE}")
+            self.x.append(x.flatten(1).contiguous())
+            self.labels.append(labels.contiguous())
+        self.K, self.P = len(batches), self.C * self.D + self.C
+        with torch.cuda.device(self.device):
+            self.table = torch.zeros(self.K, 4, dtype=torch.int64, pin_memory=True)
+            self.rec = torch.zeros(8, dtype=torch.float64, pin_memory=True)
+        self.table.numpy()[:] = [(x.data_ptr(), y.data_ptr(), x.shape[0], 0) for x, y in zip(self.x, self.labels)]
+
+    def run(self, rounds, per_launch, activation, lr, adam=None):
+        """``rounds`` rounds in launches of ``per_launch`` rounds on the current stream, one host sync per launch,
+        ``state`` and ``step0`` carried from launch to launch; the parameters are updated in place after the last one.
+        Returns ``(losses, None)``, or ``(None, k)`` when client ``k`` has a label outside ``[0, C)`` (nothing was
+        stepped then).  ``adam``: ``(beta1, beta2, eps, weight_decay)`` of the reference's Adam, else plain SGD."""
+        st = torch.cuda.current_stream(self.device)
+        lib = _lib.load_clientchain()
+        with torch.cuda.device(self.device), torch.no_grad():
+            losses = torch.zeros(rounds, dtype=torch.float64, pin_memory=True)
+            model = torch.cat([self.w.detach().reshape(-1), self.b.detach()])
+            state = coef = None
+            if adam:
+                state = torch.zeros(3 * self.P, dtype=torch.float32, device=self.device)
+                coef = torch.from_numpy(adam_coef_rows(lr, *adam, 1, rounds * self.K)).to(self.device)
+            for r0 in range(0, rounds, per_launch):
+                n = min(per_launch, rounds - r0)
+                rc = lib.fedavg_client_chain_f32(
+                    model.data_ptr(), state.data_ptr() if adam else None, self.table.data_ptr(), self.K, self.D,
+                    self.C, n, r0 * self.K, activation, 1 if adam else 0, float(lr), self.form,
+                    coef[r0 * self.K:].data_ptr() if adam else None, losses[r0:].data_ptr(), self.rec.data_ptr(),
+                    st.cuda_stream)
+                _lib.check_clientchain(rc, "fedavg_client_chain_f32")
+                st.synchronize()
+                if self.rec[0]:
+                    return None, int(self.rec[1])
+            self.w.copy_(model[:self.C * self.D].view(self.C, self.D))
+            self.b.copy_(model[self.C * self.D:])
+        return losses.tolist(), None
 
 
 # ------------------------------------------------------------------ every client's evaluation, one call

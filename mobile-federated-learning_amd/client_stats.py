@@ -68,7 +68,7 @@ import torch
 
 from . import _lib
 from .client_forms import _ADAM_PROBE, _mine_site_c, _probe_adam_form, _probe_sgd_form, _probe_values  # noqa: F401
-from .client_passes import (ADAM_SITES, FUSED_DTYPES, LINEAR_LOOPS, _RULE, _STEP_SUFFIX, EvalSet, _AdamPass, _Cohort,  # noqa: F401
+from .client_passes import (ADAM_SITES, FUSED_DTYPES, LINEAR_LOOPS, _RULE, _STEP_SUFFIX, EvalSet, _AdamPass, _Chain, _Cohort,  # noqa: F401
                             _KeyPass, _LinearLoop, _STATS_LIBS, _StepPass, _fused_ok, _guard_bound, _norm_of, _round_to, adam_coef)
 
 # rec: one device record of doubles, read back in one D2H.  The device guard adds the previous loss, the gate and
@@ -735,6 +735,74 @@ def local_test_all(trainer, model_global, round_idx, eval_on_train=False, if_log
         if wandb is not None:
             wandb.log(stats)
     return test_acc, train_acc
+
+
+def chain_train(net, batches, rounds, *, optimizer, lr, wd=0.0, loop="linear", per_launch=None):
+    """The loop of ``FedAvgTrainer.central_train`` (fedavg_trainer.py:361-371) on ``fedavg_client_chain_f32``: ``rounds``
+    rounds of one optimizer step of ``net`` on each batch of ``batches``, in their order, the optimizer state carried
+    through all of them.  ``batches``: a list of ``(x, labels)`` on the model's GPU, or an :class:`EvalSet`, whose
+    resident batches are taken in position order (not in its sorted table's).  ``optimizer="sgd"`` is
+    ``torch.optim.SGD(lr)``, anything else the reference's ``Adam(lr, weight_decay=wd, amsgrad=True)``.  The work is cut
+    into launches of ``per_launch`` rounds (default ``max(1, 1024 // K)``, which bounds one kernel's run time), one
+    host sync each; the result does not depend on the cut, to the bit.  The rules of ``client_train(loop="linear")``
+    hold for the model and every batch (``TypeError`` before anything runs).  ``net``'s two parameters are updated in
+    place; a label outside ``[0, C)`` raises ``IndexError`` naming the client, with ``net`` untouched.  Returns the
+    ``rounds`` losses that :372 logs: each round's last batch's, from before its step."""
+    if loop not in LINEAR_LOOPS:
+        raise ValueError(f"loop must be 'linear' or 'linear_sigmoid', not {loop!r}")
+    if rounds < 1:
+        raise ValueError("chain_train needs rounds >= 1")
+    if isinstance(batches, EvalSet):
+        batches = list(zip(batches.x, batches.labels))
+    batches = list(batches)
+    if not batches:
+        raise ValueError("chain_train needs at least one batch")
+    if per_launch is None:
+        per_launch = max(1, 1024 // len(batches))
+    if per_launch < 1:
+        raise ValueError("per_launch must be at least 1")
+    sgd = optimizer == "sgd"
+    form_of = (lambda dev: sgd_form(dev, torch.float32)) if sgd else (lambda dev: adam_form(dev, torch.float32))
+    plan = _Chain(net.parameters(), batches, form_of)  # refused, if it is, before anything runs
+    losses, bad = plan.run(rounds, per_launch, LINEAR_LOOPS[loop], lr, None if sgd else (0.9, 0.999, 1e-8, wd))
+    if bad is not None:
+        raise IndexError(f"client {bad}: a label lies outside [0, {plan.C}): the kernel took no step and the model is "
+                         "untouched")
+    torch.autograd.graph.increment_version([plan.w, plan.b])  # the in-place update autograd did not see
+    return losses
+
+
+def central_train(trainer, *, loop="linear", sets=None):
+    """``FedAvgTrainer.central_train`` (fedavg_trainer.py:351-375) on :func:`chain_train`: the model built as :353
+    builds it and moved to ``trainer.device``, ``args.central_round`` rounds over the clients
+    ``range(trainer.client_num)`` with ``args.client_optimizer``, ``args.lr`` and ``args.wd``, one
+    ``wandb.log({"central_training/loss": loss})`` per round (``logger`` and ``wandb`` are those of the module that
+    defines the trainer's class, if it has them).  ``sets``: ``{"train": EvalSet}`` over exactly those clients; when
+    not passed, the set :func:`local_test_all` kept on the trainer is used if it covers exactly those clients, else one
+    is built.  Returns the reference's ``(w_optimal, loss_optimal)``."""
+    mod = sys.modules[type(trainer).__module__]
+    logger, wandb = getattr(mod, "logger", None), getattr(mod, "wandb", None)
+    if logger is not None:
+        logger.info("################global optimal weights calculation")
+    args, device = trainer.args, torch.device(trainer.device)
+    model = trainer.model(args, model_name=args.model, output_dim=trainer.class_num)
+    model.to(device)
+    n = trainer.client_num
+    train = (sets if sets is not None else trainer.__dict__.get("_mfl_eval_sets", {})).get("train")
+    if sets is None and train is not None:
+        # the kept set is local_test_all's: over the clients that function does not leave out
+        kept = [i for i in range(min(int(getattr(mod, "client_num_in_total", n)), n))
+                if trainer.test_data_local_dict[i] is not None and i not in trainer.invalid_datasets.keys()]
+        if kept != list(range(n)):
+            train = None
+    if train is None or not (train.n == train.K == n and train.device == device):
+        train = EvalSet([trainer.train_data_local_dict[i] for i in range(n)], device)
+    losses = chain_train(model, train, args.central_round, optimizer=args.client_optimizer, lr=args.lr, wd=args.wd,
+                         loop=loop)
+    if wandb is not None:
+        for loss in losses:
+            wandb.log({"central_training/loss": loss})
+    return torch.cat([param.view(-1) for param in model.parameters()]), losses[-1]
 
 
 def client_train(self, net, local_iteration, *, keep_on_device=False, stats="auto", trace=None, step="torch",
