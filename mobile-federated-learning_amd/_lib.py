@@ -11,7 +11,7 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import (BY_KEY, CHAIN_BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCHAIN_LIB_PATH, CLIENTCOHORT_LIB_PATH, CLIENTEVAL_LIB_PATH, COHORT_BY_KEY, EVAL_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
+from .build import (BY_KEY, CHAIN_BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCHAIN_LIB_PATH, CLIENTCOHORT_LIB_PATH, CLIENTEVAL_LIB_PATH, CLIENTSPLIT_LIB_PATH, COHORT_BY_KEY, EVAL_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
                     CLIENTVEC_LIB_PATH, DESCRIBED, EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, LINEAR_BY_KEY, PROBE_LIB_PATH,
                     SEGVEC_LIB_PATH, STREAM_BY_KEY, NativeLib)
 
@@ -250,6 +250,16 @@ CLIENTCHAIN_SIGNATURES = {
                                          ctypes.c_double, _c_int, _vp, _vp, _vp, _vp]),
 }
 
+# libfedavg_amd_clientsplit.so (include/fedavg_amd_clientsplit.h): the chain's arguments, then the workspace
+CLIENTSPLIT_SIGNATURES = {
+    "fedavg_clientsplit_abi_version": (_c_int, []),
+    "fedavg_clientsplit_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_split_slice_rows": (_c_i64, [_c_i64]),
+    "fedavg_client_split_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "fedavg_client_chain_split_f32": (_c_int, CLIENTCHAIN_SIGNATURES["fedavg_client_chain_f32"][1][:-1]
+                                      + [_vp, _c_i64, _vp]),
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
@@ -262,6 +272,7 @@ CLIENTSTREAM_ABI_VERSION = STREAM_BY_KEY["clientstream"].abi[1]
 CLIENTCOHORT_ABI_VERSION = COHORT_BY_KEY["clientcohort"].abi[1]
 CLIENTEVAL_ABI_VERSION = EVAL_BY_KEY["clienteval"].abi[1]
 CLIENTCHAIN_ABI_VERSION = CHAIN_BY_KEY["clientchain"].abi[1]
+CLIENTSPLIT_ABI_VERSION = CHAIN_BY_KEY["clientsplit"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -314,6 +325,7 @@ _EVAL_BINDING = {
 # the same for the libraries of build.CHAIN_BY_KEY (a new one goes here)
 _CHAIN_BINDING = {
     "clientchain": ((CLIENTCHAIN_SIGNATURES,), "CLIENTCHAIN_LIB_PATH", "_clientchain"),
+    "clientsplit": ((CLIENTSPLIT_SIGNATURES,), "CLIENTSPLIT_LIB_PATH", "_clientsplit"),
 }
 
 _lock = threading.Lock()
@@ -330,6 +342,7 @@ _clientstream = None
 _clientcohort = None
 _clienteval = None
 _clientchain = None
+_clientsplit = None
 
 
 def library_path() -> Path:
@@ -449,6 +462,11 @@ def load_clientchain() -> ctypes.CDLL:
     return _clientchain if _clientchain is not None else _load(CHAIN_BY_KEY["clientchain"])
 
 
+def load_clientsplit() -> ctypes.CDLL:
+    """The batch-split chain of central training steps of a linear model, fp32 (include/fedavg_amd_clientsplit.h)."""
+    return _clientsplit if _clientsplit is not None else _load(CHAIN_BY_KEY["clientsplit"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
@@ -488,6 +506,11 @@ def check_clienteval(rc: int, what: str) -> None:
 def check_clientchain(rc: int, what: str) -> None:
     """``_check`` for the central training chain library (its description read at call time)."""
     _check(CHAIN_BY_KEY["clientchain"], rc, what)
+
+
+def check_clientsplit(rc: int, what: str) -> None:
+    """``_check`` for the batch-split chain library (its description read at call time)."""
+    _check(CHAIN_BY_KEY["clientsplit"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

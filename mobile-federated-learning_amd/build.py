@@ -18,8 +18,8 @@ to that one key.  The eleventh, and any after it, is described in
 ``COHORT_LIBS`` / ``COHORT_BY_KEY``, which tests/test_clientcohort_abi.py pins
 to that one key.  The twelfth is described in ``EVAL_LIBS`` / ``EVAL_BY_KEY``,
 which tests/test_clienteval_abi.py pins to that one key.  The thirteenth, and
-any after it, is described in ``CHAIN_LIBS`` / ``CHAIN_BY_KEY``, which no test
-pins to one key (a new one goes there);
+any after it (the fourteenth, ``clientsplit``), is described in ``CHAIN_LIBS`` /
+``CHAIN_BY_KEY``, which no test pins to one key (a new one goes there);
 ``BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS + CHAIN_LIBS``
 (``described_libs()``) is what ``sources()``, the up-to-date rule and ``build()`` cover, and ``_lib`` loads a library from
 the by-key table that holds it.
@@ -202,9 +202,18 @@ CHAIN_LIBS = (
               last_error="fedavg_clientchain_last_error",
               no_fallback="; there is no fallback for the one-launch chain of central training steps",
               defines=("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")),
+    # the same chain with each step's batch split across workgroups: per step a gradient launch of one workgroup per
+    # slice of rows and a step launch that sums the slices' partial gradients in slot order, fp32; calls no other
+    # library.  Compiled without packed fp32 instructions.
+    NativeLib("clientsplit", "libfedavg_amd_clientsplit.so", "fedavg_amd_clientsplit.h",
+              ("fedavg_client_split.hip",), abi=("fedavg_clientsplit_abi_version", 1),
+              last_error="fedavg_clientsplit_last_error",
+              no_fallback="; there is no fallback for the batch-split chain of central training steps",
+              defines=("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")),
 )
 CHAIN_BY_KEY = {lib.key: lib for lib in CHAIN_LIBS}
 CLIENTCHAIN_LIB_PATH = CHAIN_BY_KEY["clientchain"].path
+CLIENTSPLIT_LIB_PATH = CHAIN_BY_KEY["clientsplit"].path
 
 
 def described_libs():

@@ -376,6 +376,16 @@ def chain_limits():
     return tuple(v.value for v in out)
 
 
+def split_limits():
+    """``(max K, max B, max D, max C)`` of the batch-split chain: the chain's, which its entry checks first."""
+    return chain_limits()
+
+
+def split_slice_rows(D):
+    """The rows of one slice of ``fedavg_client_chain_split_f32`` at ``D`` columns (0 outside its range)."""
+    return _lib.load_clientsplit().fedavg_client_split_slice_rows(D)
+
+
 def adam_coef_rows(lr, beta1, beta2, eps, weight_decay, first, n):
     """Rows ``[n, 7]`` of :func:`adam_coef` for the steps ``first .. first + n - 1`` (from 1): the constant columns
     filled at once, the three powers of a row in Python floats exactly as torch/optim/adam.py forms them."""
@@ -392,9 +402,10 @@ class _Chain:
     order, round after round.  The :class:`_LinearLoop` rules are checked once for the model (with the first batch)
     and per client for the batch (``TypeError`` naming the rule, before anything runs).  The plan keeps the pinned
     client table in client order, the pinned losses and record, and on the device Adam's coefficient rows and its
-    ``m, v, vmax``."""
+    ``m, v, vmax``.  ``split``: the calls are ``fedavg_client_chain_split_f32``'s, each step's batch split across
+    workgroups, and the plan also keeps that entry's workspace, sized from the table's largest batch."""
 
-    def __init__(self, params, batches, form_of):
+    def __init__(self, params, batches, form_of, split=False):
         first = _LinearLoop(params, *batches[0], torch.nn.CrossEntropyLoss(), form_of)
         self.w, self.b, self.form, self.D, self.C, self.device = first.w, first.b, first.form, first.D, first.C, first.device
         max_k, max_b, _, _ = chain_limits()
@@ -415,6 +426,21 @@ class _Chain:
             self.table = torch.zeros(self.K, 4, dtype=torch.int64, pin_memory=True)
             self.rec = torch.zeros(8, dtype=torch.float64, pin_memory=True)
         self.table.numpy()[:] = [(x.data_ptr(), y.data_ptr(), x.shape[0], 0) for x, y in zip(self.x, self.labels)]
+        self.workspace = None
+        if split:
+            nbytes = _lib.load_clientsplit().fedavg_client_split_workspace_bytes(
+                max(x.shape[0] for x in self.x), self.D, self.C)
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _call(self, *args, stream):
+        """One call of the plan's entry: the chain's arguments, and for the split entry its workspace after them."""
+        if self.workspace is None:
+            _lib.check_clientchain(_lib.load_clientchain().fedavg_client_chain_f32(*args, stream),
+                                   "fedavg_client_chain_f32")
+        else:
+            rc = _lib.load_clientsplit().fedavg_client_chain_split_f32(*args, self.workspace.data_ptr(),
+                                                                       self.workspace.numel(), stream)
+            _lib.check_clientsplit(rc, "fedavg_client_chain_split_f32")
 
     def run(self, rounds, per_launch, activation, lr, adam=None):
         """``rounds`` rounds in launches of ``per_launch`` rounds on the current stream, one host sync per launch,
@@ -422,7 +448,6 @@ class _Chain:
         Returns ``(losses, None)``, or ``(None, k)`` when client ``k`` has a label outside ``[0, C)`` (nothing was
         stepped then).  ``adam``: ``(beta1, beta2, eps, weight_decay)`` of the reference's Adam, else plain SGD."""
         st = torch.cuda.current_stream(self.device)
-        lib = _lib.load_clientchain()
         with torch.cuda.device(self.device), torch.no_grad():
             losses = torch.zeros(rounds, dtype=torch.float64, pin_memory=True)
             model = torch.cat([self.w.detach().reshape(-1), self.b.detach()])
@@ -432,12 +457,11 @@ class _Chain:
                 coef = torch.from_numpy(adam_coef_rows(lr, *adam, 1, rounds * self.K)).to(self.device)
             for r0 in range(0, rounds, per_launch):
                 n = min(per_launch, rounds - r0)
-                rc = lib.fedavg_client_chain_f32(
+                self._call(
                     model.data_ptr(), state.data_ptr() if adam else None, self.table.data_ptr(), self.K, self.D,
                     self.C, n, r0 * self.K, activation, 1 if adam else 0, float(lr), self.form,
                     coef[r0 * self.K:].data_ptr() if adam else None, losses[r0:].data_ptr(), self.rec.data_ptr(),
-                    st.cuda_stream)
-                _lib.check_clientchain(rc, "fedavg_client_chain_f32")
+                    stream=st.cuda_stream)
                 st.synchronize()
                 if self.rec[0]:
                     return None, int(self.rec[1])

@@ -737,7 +737,7 @@ def local_test_all(trainer, model_global, round_idx, eval_on_train=False, if_log
     return test_acc, train_acc
 
 
-def chain_train(net, batches, rounds, *, optimizer, lr, wd=0.0, loop="linear", per_launch=None):
+def chain_train(net, batches, rounds, *, optimizer, lr, wd=0.0, loop="linear", per_launch=None, split=False):
     """The loop of ``FedAvgTrainer.central_train`` (fedavg_trainer.py:361-371) on ``fedavg_client_chain_f32``: ``rounds``
     rounds of one optimizer step of ``net`` on each batch of ``batches``, in their order, the optimizer state carried
     through all of them.  ``batches``: a list of ``(x, labels)`` on the model's GPU, or an :class:`EvalSet`, whose
@@ -747,7 +747,13 @@ def chain_train(net, batches, rounds, *, optimizer, lr, wd=0.0, loop="linear", p
     host sync each; the result does not depend on the cut, to the bit.  The rules of ``client_train(loop="linear")``
     hold for the model and every batch (``TypeError`` before anything runs).  ``net``'s two parameters are updated in
     place; a label outside ``[0, C)`` raises ``IndexError`` naming the client, with ``net`` untouched.  Returns the
-    ``rounds`` losses that :372 logs: each round's last batch's, from before its step."""
+    ``rounds`` losses that :372 logs: each round's last batch's, from before its step.
+
+    ``split=True`` runs ``fedavg_client_chain_split_f32`` instead (``libfedavg_amd_clientsplit.so``): every step's batch
+    is split across workgroups, a gradient launch and a step launch per step, the same checks, the same ``IndexError``
+    and the same cut into calls, whose result does not depend on the cut either.  It has the same reference and bound
+    but not the one-launch chain's bits (a step's gradient is summed slice by slice).  Nothing chooses between the two:
+    README.md says from measurement at which batch sizes to pass it."""
     if loop not in LINEAR_LOOPS:
         raise ValueError(f"loop must be 'linear' or 'linear_sigmoid', not {loop!r}")
     if rounds < 1:
@@ -763,7 +769,7 @@ def chain_train(net, batches, rounds, *, optimizer, lr, wd=0.0, loop="linear", p
         raise ValueError("per_launch must be at least 1")
     sgd = optimizer == "sgd"
     form_of = (lambda dev: sgd_form(dev, torch.float32)) if sgd else (lambda dev: adam_form(dev, torch.float32))
-    plan = _Chain(net.parameters(), batches, form_of)  # refused, if it is, before anything runs
+    plan = _Chain(net.parameters(), batches, form_of, split=split)  # refused, if it is, before anything runs
     losses, bad = plan.run(rounds, per_launch, LINEAR_LOOPS[loop], lr, None if sgd else (0.9, 0.999, 1e-8, wd))
     if bad is not None:
         raise IndexError(f"client {bad}: a label lies outside [0, {plan.C}): the kernel took no step and the model is "
@@ -772,14 +778,14 @@ def chain_train(net, batches, rounds, *, optimizer, lr, wd=0.0, loop="linear", p
     return losses
 
 
-def central_train(trainer, *, loop="linear", sets=None):
+def central_train(trainer, *, loop="linear", sets=None, split=False):
     """``FedAvgTrainer.central_train`` (fedavg_trainer.py:351-375) on :func:`chain_train`: the model built as :353
     builds it and moved to ``trainer.device``, ``args.central_round`` rounds over the clients
     ``range(trainer.client_num)`` with ``args.client_optimizer``, ``args.lr`` and ``args.wd``, one
     ``wandb.log({"central_training/loss": loss})`` per round (``logger`` and ``wandb`` are those of the module that
     defines the trainer's class, if it has them).  ``sets``: ``{"train": EvalSet}`` over exactly those clients; when
     not passed, the set :func:`local_test_all` kept on the trainer is used if it covers exactly those clients, else one
-    is built.  Returns the reference's ``(w_optimal, loss_optimal)``."""
+    is built.  ``split``: :func:`chain_train`'s.  Returns the reference's ``(w_optimal, loss_optimal)``."""
     mod = sys.modules[type(trainer).__module__]
     logger, wandb = getattr(mod, "logger", None), getattr(mod, "wandb", None)
     if logger is not None:
@@ -798,7 +804,7 @@ def central_train(trainer, *, loop="linear", sets=None):
     if train is None or not (train.n == train.K == n and train.device == device):
         train = EvalSet([trainer.train_data_local_dict[i] for i in range(n)], device)
     losses = chain_train(model, train, args.central_round, optimizer=args.client_optimizer, lr=args.lr, wd=args.wd,
-                         loop=loop)
+                         loop=loop, split=split)
     if wandb is not None:
         for loss in losses:
             wandb.log({"central_training/loss": loss})

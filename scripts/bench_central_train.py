@@ -1,19 +1,22 @@
-"""central_train for a linear model: one ``chain_train`` call against the torch loop of fedavg_trainer.py:361-371.
+"""central_train for a linear model: ``chain_train``, one launch and batch-split, against the torch loop of fedavg_trainer.py:361-371.
 
     python scripts/bench_central_train.py                   # every configuration, one child process each
     python scripts/bench_central_train.py --one 64 sgd 1000 # one configuration, one JSON line
 
 Workload: MNIST-LR shapes (D = 784, C = 10), K in 100, 1000 clients of B = 64 and B = 600 samples, SGD and Adam,
-3 central rounds: 3 K optimizer steps of one model.  Both arms run in the same process on batches that are resident
-on the GPU, alternated (loop, chain, loop, ...), 3 warm-up pairs and then 30 timed pairs.  The loop arm is the
+3 central rounds: 3 K optimizer steps of one model.  The three arms (the torch loop, ``chain_train``, and
+``chain_train(split=True)``) run in the same process on batches that are resident on the GPU, rotated (loop, chain,
+split, loop, ...), 3 warm-up rounds of arms and then 30 timed ones.  The loop arm is the
 reference's: per step ``zero_grad``, forward, ``CrossEntropyLoss``, backward, ``loss.item()`` and ``optimizer.step()``,
 with a fresh optimizer per run as central_train makes one.  A time is host wall clock around the arm including its
-host syncs; the line holds the medians, the extremes and whether the chain was below the loop in EVERY pair
-(``all_below``; without it nothing is called faster).  ``x_gbps`` is the bytes of x the chain reads (every batch once
+host syncs; the line holds the three medians, the extremes and whether one arm was below another in EVERY round of
+arms (``all_below``: chain below loop; ``split_below_loop_every_pair``; ``split_below_chain_every_pair``; without the
+flag nothing is called faster).  ``x_gbps`` is the bytes of x the chain reads (every batch once
 per round) over the chain's median time: a rate over the whole call, host time included, not a counter reading.
 
 The driver runs each configuration as a child process under its own time limit and stops at the first that fails;
-lines go to profiles/central_train/mi355x_central_train.jsonl.
+lines go to profiles/central_train/mi355x_central_split.jsonl (mi355x_central_train.jsonl beside it is the two-arm
+run from before the split arm existed).
 """
 import argparse
 import json
@@ -25,7 +28,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path[:0] = [str(ROOT)]
-OUT = ROOT / "profiles" / "central_train" / "mi355x_central_train.jsonl"
+OUT = ROOT / "profiles" / "central_train" / "mi355x_central_split.jsonl"
 D, C, ROUNDS, WARMUP, REPEATS = 784, 10, 3, 3, 30
 KS, BS, OPTIMIZERS = (100, 1000), (64, 600), ("sgd", "adam")
 HYPER = {"sgd": dict(lr=0.05, wd=0.0), "adam": dict(lr=0.001, wd=0.001)}
@@ -66,6 +69,9 @@ def one(B, optimizer, K):
     def chain():
         return mfl_amd.chain_train(net, batches, ROUNDS, optimizer=optimizer, **h)[-1]
 
+    def split():
+        return mfl_amd.chain_train(net, batches, ROUNDS, optimizer=optimizer, split=True, **h)[-1]
+
     def timed(fn):
         restore()
         torch.cuda.synchronize()
@@ -74,14 +80,17 @@ def one(B, optimizer, K):
         torch.cuda.synchronize()
         return (time.perf_counter() - t) * 1e3, loss
 
-    runs = [(timed(loop), timed(chain)) for _ in range(WARMUP + REPEATS)][WARMUP:]
-    lo, ch = [r[0][0] for r in runs], [r[1][0] for r in runs]
+    runs = [(timed(loop), timed(chain), timed(split)) for _ in range(WARMUP + REPEATS)][WARMUP:]
+    lo, ch, sp = ([r[arm][0] for r in runs] for arm in range(3))
     line = dict(workload="mnist_lr_central_train", B=B, D=D, C=C, rounds=ROUNDS, optimizer=optimizer, K=K,
                 repeats=REPEATS, device=torch.cuda.get_device_name(0), torch=torch.__version__,
-                loop_ms=statistics.median(lo), chain_ms=statistics.median(ch), loop_min_max=[min(lo), max(lo)],
-                chain_min_max=[min(ch), max(ch)], all_below=all(c < s for s, c in zip(lo, ch)),
+                loop_ms=statistics.median(lo), chain_ms=statistics.median(ch), split_ms=statistics.median(sp),
+                loop_min_max=[min(lo), max(lo)], chain_min_max=[min(ch), max(ch)], split_min_max=[min(sp), max(sp)],
+                all_below=all(c < s for s, c in zip(lo, ch)),
+                split_below_loop_every_pair=all(p < s for s, p in zip(lo, sp)),
+                split_below_chain_every_pair=all(p < c for c, p in zip(ch, sp)),
                 x_gbps=ROUNDS * K * B * D * 4 / (statistics.median(ch) * 1e-3) / 1e9,
-                last_loss=dict(loop=runs[-1][0][1], chain=runs[-1][1][1]))
+                last_loss=dict(loop=runs[-1][0][1], chain=runs[-1][1][1], split=runs[-1][2][1]))
     print(json.dumps(line), flush=True)
 
 
