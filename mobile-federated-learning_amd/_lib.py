@@ -11,7 +11,8 @@ import functools
 import threading
 from pathlib import Path
 
-from .build import (BY_KEY, CHAIN_BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCHAIN_LIB_PATH, CLIENTCOHORT_LIB_PATH, CLIENTEVAL_LIB_PATH, CLIENTSPLIT_LIB_PATH, COHORT_BY_KEY, EVAL_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
+from .build import (BY_KEY, CHAIN_BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCHAIN_LIB_PATH, CLIENTCOHORT_LIB_PATH,
+                    CLIENTCOSPLIT_LIB_PATH, COSPLIT_BY_KEY, CLIENTEVAL_LIB_PATH, CLIENTSPLIT_LIB_PATH, COHORT_BY_KEY, EVAL_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
                     CLIENTVEC_LIB_PATH, DESCRIBED, EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, LINEAR_BY_KEY, PROBE_LIB_PATH,
                     SEGVEC_LIB_PATH, STREAM_BY_KEY, NativeLib)
 
@@ -260,6 +261,16 @@ CLIENTSPLIT_SIGNATURES = {
                                       + [_vp, _c_i64, _vp]),
 }
 
+# libfedavg_amd_clientcosplit.so (include/fedavg_amd_clientcosplit.h): the cohort's arguments, then slices_per_group and
+# the workspace
+CLIENTCOSPLIT_SIGNATURES = {
+    "fedavg_clientcosplit_abi_version": (_c_int, []),
+    "fedavg_clientcosplit_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_cosplit_workspace_bytes": (_c_i64, [_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
+    "fedavg_client_cohort_split_f32": (_c_int, CLIENTCOHORT_SIGNATURES["fedavg_client_cohort_f32"][1][:-1]
+                                       + [_c_i64, _vp, _c_i64, _vp]),
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
@@ -273,6 +284,7 @@ CLIENTCOHORT_ABI_VERSION = COHORT_BY_KEY["clientcohort"].abi[1]
 CLIENTEVAL_ABI_VERSION = EVAL_BY_KEY["clienteval"].abi[1]
 CLIENTCHAIN_ABI_VERSION = CHAIN_BY_KEY["clientchain"].abi[1]
 CLIENTSPLIT_ABI_VERSION = CHAIN_BY_KEY["clientsplit"].abi[1]
+CLIENTCOSPLIT_ABI_VERSION = COSPLIT_BY_KEY["clientcosplit"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -327,6 +339,10 @@ _CHAIN_BINDING = {
     "clientchain": ((CLIENTCHAIN_SIGNATURES,), "CLIENTCHAIN_LIB_PATH", "_clientchain"),
     "clientsplit": ((CLIENTSPLIT_SIGNATURES,), "CLIENTSPLIT_LIB_PATH", "_clientsplit"),
 }
+# the same for the libraries of build.COSPLIT_BY_KEY (a new one goes here)
+_COSPLIT_BINDING = {
+    "clientcosplit": ((CLIENTCOSPLIT_SIGNATURES,), "CLIENTCOSPLIT_LIB_PATH", "_clientcosplit"),
+}
 
 _lock = threading.Lock()
 _lib = None
@@ -343,6 +359,7 @@ _clientcohort = None
 _clienteval = None
 _clientchain = None
 _clientsplit = None
+_clientcosplit = None
 
 
 def library_path() -> Path:
@@ -353,13 +370,14 @@ def _load(d: NativeLib) -> ctypes.CDLL:
     """Load (once), type and version-check the library ``d`` describes.  No
     fallback: a missing, unloadable or stale library raises ``FedAvgLibraryError``."""
     tables, path_name, slot = next(t[d.key] for t in (_BINDING, _EXTRA_BINDING, _LINEAR_BINDING, _STREAM_BINDING,
-                                                      _COHORT_BINDING, _EVAL_BINDING, _CHAIN_BINDING) if d.key in t)
+                                                      _COHORT_BINDING, _EVAL_BINDING, _CHAIN_BINDING, _COSPLIT_BINDING)
+                                   if d.key in t)
     g = globals()
     if g[slot] is not None:
         return g[slot]
     if d.needs:
         _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY, STREAM_BY_KEY, COHORT_BY_KEY, EVAL_BY_KEY,
-                                          CHAIN_BY_KEY) if d.needs in t))
+                                          CHAIN_BY_KEY, COSPLIT_BY_KEY) if d.needs in t))
     with _lock:
         if g[slot] is not None:
             return g[slot]
@@ -467,6 +485,11 @@ def load_clientsplit() -> ctypes.CDLL:
     return _clientsplit if _clientsplit is not None else _load(CHAIN_BY_KEY["clientsplit"])
 
 
+def load_clientcosplit() -> ctypes.CDLL:
+    """The batch-split cohort of linear softmax clients, fp32 (include/fedavg_amd_clientcosplit.h)."""
+    return _clientcosplit if _clientcosplit is not None else _load(COSPLIT_BY_KEY["clientcosplit"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
@@ -511,6 +534,11 @@ def check_clientchain(rc: int, what: str) -> None:
 def check_clientsplit(rc: int, what: str) -> None:
     """``_check`` for the batch-split chain library (its description read at call time)."""
     _check(CHAIN_BY_KEY["clientsplit"], rc, what)
+
+
+def check_clientcosplit(rc: int, what: str) -> None:
+    """``_check`` for the batch-split cohort library (its description read at call time)."""
+    _check(COSPLIT_BY_KEY["clientcosplit"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

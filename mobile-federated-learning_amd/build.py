@@ -19,8 +19,10 @@ to that one key.  The eleventh, and any after it, is described in
 to that one key.  The twelfth is described in ``EVAL_LIBS`` / ``EVAL_BY_KEY``,
 which tests/test_clienteval_abi.py pins to that one key.  The thirteenth, and
 any after it (the fourteenth, ``clientsplit``), is described in ``CHAIN_LIBS`` /
-``CHAIN_BY_KEY``, which no test pins to one key (a new one goes there);
-``BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS + CHAIN_LIBS``
+``CHAIN_BY_KEY``, which tests/test_clientsplit_abi.py pins to those two keys.
+The fifteenth, and any after it, is described in ``COSPLIT_LIBS`` /
+``COSPLIT_BY_KEY``, which tests/test_clientcosplit_abi.py pins to that one key;
+``BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS + CHAIN_LIBS + COSPLIT_LIBS``
 (``described_libs()``) is what ``sources()``, the up-to-date rule and ``build()`` cover, and ``_lib`` loads a library from
 the by-key table that holds it.
 
@@ -214,11 +216,24 @@ CHAIN_LIBS = (
 CHAIN_BY_KEY = {lib.key: lib for lib in CHAIN_LIBS}
 CLIENTCHAIN_LIB_PATH = CHAIN_BY_KEY["clientchain"].path
 CLIENTSPLIT_LIB_PATH = CHAIN_BY_KEY["clientsplit"].path
+# libraries added after those fourteen (a new one goes here: see the module docstring)
+COSPLIT_LIBS = (
+    # the cohort with each client's batch split across workgroups: per local iteration a gradient launch over every
+    # client's slices of rows and a step launch of one workgroup per client that sums its slots in slot order, decides
+    # the guard and steps the client's row, fp32; calls no other library.  Compiled without packed fp32 instructions.
+    NativeLib("clientcosplit", "libfedavg_amd_clientcosplit.so", "fedavg_amd_clientcosplit.h",
+              ("fedavg_client_cosplit.hip",), abi=("fedavg_clientcosplit_abi_version", 1),
+              last_error="fedavg_clientcosplit_last_error",
+              no_fallback="; there is no fallback for the batch-split cohort of linear clients",
+              defines=("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")),
+)
+COSPLIT_BY_KEY = {lib.key: lib for lib in COSPLIT_LIBS}
+CLIENTCOSPLIT_LIB_PATH = COSPLIT_BY_KEY["clientcosplit"].path
 
 
 def described_libs():
     """Every described library, in link order (the tuples are read when called, so a test that patches one is served)."""
-    return BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS + CHAIN_LIBS
+    return BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS + CHAIN_LIBS + COSPLIT_LIBS
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",
@@ -257,11 +272,11 @@ def up_to_date() -> bool:
 
 def later_up_to_date() -> bool:
     """The same rule for ``LATER_LIBS``, ``NEWER_LIBS``, ``EXTRA_LIBS``, ``LINEAR_LIBS``, ``STREAM_LIBS``,
-    ``COHORT_LIBS``, ``EVAL_LIBS`` and ``CHAIN_LIBS``: each built and no older than the newest source."""
+    ``COHORT_LIBS``, ``EVAL_LIBS``, ``CHAIN_LIBS`` and ``COSPLIT_LIBS``: each built and no older than the newest source."""
     newest = max(p.stat().st_mtime for p in sources())
     return all(lib.path.exists() and lib.path.stat().st_mtime >= newest
                for lib in LATER_LIBS + NEWER_LIBS + EXTRA_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS
-               + CHAIN_LIBS)
+               + CHAIN_LIBS + COSPLIT_LIBS)
 
 
 def collect_ext_path() -> Path:
@@ -324,7 +339,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         (LIB_DIR / lib.obj_dir).mkdir(parents=True, exist_ok=True)
     _compile_all([(CSRC_DIR / u, lib.obj(u), list(lib.defines)) for lib in libs for u in lib.units], verbose)
     by_key = {**DESCRIBED, **EXTRA_BY_KEY, **LINEAR_BY_KEY, **STREAM_BY_KEY, **COHORT_BY_KEY, **EVAL_BY_KEY,
-              **CHAIN_BY_KEY}
+              **CHAIN_BY_KEY, **COSPLIT_BY_KEY}
     for lib in libs:  # in order: a library links after the one its link arguments name
         objs = [lib.obj(u) for u in lib.units] + [by_key[key].obj(u) for key, u in lib.reuse]
         _link(objs, lib.path, verbose, extra=lib.link)

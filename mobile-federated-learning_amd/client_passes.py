@@ -313,11 +313,14 @@ class _Cohort:
     into row ``k``.  The :class:`_LinearLoop` rules are checked once for the model (with the first batch) and per
     client for the batch (``TypeError`` naming the rule, before anything runs).  The client table, the records and
     Adam's coefficient table lie in pinned host memory kept per device; ``run`` returns only after the stream has
-    passed the launch, so the next call may reuse them."""
+    passed the launch, so the next call may reuse them.  ``split``: the call is ``fedavg_client_cohort_split_f32``'s,
+    each client's batch split across workgroups that walk ``slices_per_group`` slices each (``None``:
+    :func:`cosplit_default_slices`), and the plan owns that entry's workspace, allocated by ``run`` after
+    :func:`_fits` has let its size pass."""
 
     _pinned = {}  # device -> [client table [K, 4] int64, records [K, 8], coefficient table [rows, 7]]
 
-    def __init__(self, params, batches, criterion, form_of):
+    def __init__(self, params, batches, criterion, form_of, split=False, slices_per_group=None):
         first = _LinearLoop(params, *batches[0], criterion, form_of)
         self.w, self.b, self.form, self.D, self.C, self.device = first.w, first.b, first.form, first.D, first.C, first.device
         max_k, max_b, _, _ = cohort_limits()
@@ -335,6 +338,13 @@ class _Cohort:
             self.labels.append(labels.contiguous())
         self.K, self.P = len(batches), self.C * self.D + self.C
         self.B = [x.shape[0] for x in self.x]
+        self.split, self.workspace = bool(split), None
+        if split:
+            if slices_per_group is None:
+                slices_per_group = cosplit_default_slices(self.B, self.D)
+            if not (isinstance(slices_per_group, int) and slices_per_group >= 1):
+                raise ValueError(f"slices_per_group must be an int >= 1, not {slices_per_group!r}")
+            self.q = slices_per_group
 
     def _buffers(self, iters):
         held = self._pinned.get(self.device)
@@ -359,13 +369,60 @@ class _Cohort:
         st = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.no_grad():
             model = torch.cat([self.w.detach().reshape(-1), self.b.detach()])
-            rc = _lib.load_clientcohort().fedavg_client_cohort_f32(
-                model.data_ptr(), rows.data_ptr(), rows.stride(0), table.data_ptr(), self.K, self.D, self.C, iters,
-                activation, 1 if adam else 0, float(lr), float(lr_ratio), self.form,
-                coef.data_ptr() if adam else None, rec.data_ptr(), st.cuda_stream)
-        _lib.check_clientcohort(rc, "fedavg_client_cohort_f32")
+            args = (model.data_ptr(), rows.data_ptr(), rows.stride(0), table.data_ptr(), self.K, self.D, self.C, iters,
+                    activation, 1 if adam else 0, float(lr), float(lr_ratio), self.form,
+                    coef.data_ptr() if adam else None, rec.data_ptr())
+            if self.split:
+                nbytes = cosplit_workspace_bytes([self.B[k] for k in order], self.D, self.C, self.q, bool(adam))
+                if self.workspace is None or self.workspace.numel() < nbytes:
+                    self.workspace = None  # the old one first
+                    _fits(nbytes, self.device)
+                    self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                name, check = "fedavg_client_cohort_split_f32", _lib.check_clientcosplit
+                rc = _lib.load_clientcosplit().fedavg_client_cohort_split_f32(
+                    *args, self.q, self.workspace.data_ptr(), self.workspace.numel(), st.cuda_stream)
+            else:
+                name, check = "fedavg_client_cohort_f32", _lib.check_clientcohort
+                rc = _lib.load_clientcohort().fedavg_client_cohort_f32(*args, st.cuda_stream)
+        check(rc, name)
         st.synchronize()
         return rec[:self.K].tolist()
+
+
+COSPLIT_MANY_GROUPS, COSPLIT_MANY_SLICES = 1024, 4  # the default slices_per_group (the sweep behind it)
+
+
+def cosplit_groups(B, D, slices_per_group):
+    """The workgroups of the batch-split cohort's gradient launch for clients of ``B`` rows of ``D`` columns: with
+    ``R = split_slice_rows(D)``, ``sum_k ceil(ceil(B_k / R) / slices_per_group)``."""
+    R = split_slice_rows(D)
+    return sum(-(-(-(-b // R)) // slices_per_group) for b in B)
+
+
+def cosplit_default_slices(B, D):
+    """The ``slices_per_group`` of ``cohort_train(split=True)`` when none is given: 1 while one slice a workgroup
+    keeps the gradient launch at or below ``COSPLIT_MANY_GROUPS`` workgroups, else ``COSPLIT_MANY_SLICES``."""
+    return 1 if cosplit_groups(B, D, 1) <= COSPLIT_MANY_GROUPS else COSPLIT_MANY_SLICES
+
+
+def cosplit_workspace_bytes(B, D, C, slices_per_group, adam):
+    """``fedavg_client_cosplit_workspace_bytes`` for clients of ``B`` rows; ``ValueError`` outside its ranges."""
+    sizes = np.ascontiguousarray(B, dtype=np.int64)
+    nbytes = _lib.load_clientcosplit().fedavg_client_cosplit_workspace_bytes(
+        sizes.ctypes.data, len(sizes), D, C, slices_per_group, 1 if adam else 0)
+    if nbytes <= 0:
+        raise ValueError(f"no workspace for {len(sizes)} clients, D = {D}, C = {C}, slices_per_group = "
+                         f"{slices_per_group}: outside the ranges of fedavg_client_cohort_split_f32")
+    return nbytes
+
+
+def _fits(nbytes, device):
+    """Refuse, before any launch, a workspace that ``torch.cuda.mem_get_info`` says cannot fit (memory torch holds
+    cached and unused counts as free)."""
+    free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+    if nbytes > free:
+        raise ValueError(f"the batch-split cohort needs a workspace of {nbytes} bytes and {device} has {free} free: "
+                         "raise slices_per_group, or train without split=True")
 
 
 # ------------------------------------------------------------------ central_train's chain of steps, one launch

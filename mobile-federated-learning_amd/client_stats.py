@@ -618,7 +618,7 @@ class CohortResult:
         return {self._names[0]: row[:C * D].view(C, D), self._names[1]: row[C * D:self.P]}
 
 
-def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None):
+def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None, split=False, slices_per_group=None):
     """A round's clients (fedavg_trainer.py:172-199: each trained from the same global model ``net``) under
     ``loop="linear"`` / ``"linear_sigmoid"`` as ONE launch of ``fedavg_client_cohort_f32``, one workgroup per client,
     one host sync and one read of the ``[K, 8]`` records.  ``clients`` are reference ``Client`` objects that share
@@ -628,7 +628,13 @@ def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None):
     ``reduce_with_sqdist(res.rows, weights_tensor(sample_weights(res.sample_numbers), torch.float32, device), res.P)``.
     The rules of ``client_train(loop="linear")`` hold for the model and for every batch (``TypeError`` before anything
     runs); a label outside ``[0, C)`` raises ``IndexError`` naming the client's position after the launch, with
-    ``net`` untouched.  Returns a :class:`CohortResult`."""
+    ``net`` untouched.  Returns a :class:`CohortResult`.
+
+    ``split=True``: the same round as ``1 + 2 * local_iteration`` launches of ``fedavg_client_cohort_split_f32``,
+    every client's batch split across workgroups of ``slices_per_group`` slices of rows each (``None``: 1 while
+    that keeps a launch at or below 1024 workgroups, else 4), for rounds of few clients with long batches.  Same checks,
+    same result type, a client's bits independent of the other clients but not those of ``split=False`` (its gradient
+    is summed slice by slice); a ``ValueError`` naming the bytes, before any launch, if the workspace cannot fit."""
     from .reduce import ALIGN_ELEMS
 
     if loop not in LINEAR_LOOPS:
@@ -650,7 +656,10 @@ def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None):
         batches.append((x.to(c.device), labels.to(c.device)))
     form_of = (lambda dev: sgd_form(dev, torch.float32)) if sgd else (lambda dev: adam_form(dev, torch.float32))
     names = [n for n, _ in net.named_parameters()]
-    plan = _Cohort(net.parameters(), batches, clients[0].criterion, form_of)  # refused, if it is, before anything runs
+    if slices_per_group is not None and not split:
+        raise ValueError("slices_per_group needs split=True")
+    # refused, if it is, before anything runs
+    plan = _Cohort(net.parameters(), batches, clients[0].criterion, form_of, split=split, slices_per_group=slices_per_group)
     ld = -(-plan.P // ALIGN_ELEMS) * ALIGN_ELEMS
     if rows is None:
         rows = torch.empty(plan.K, ld, dtype=torch.float32, device=plan.device)
