@@ -12,7 +12,7 @@ import threading
 from pathlib import Path
 
 from .build import (BY_KEY, CHAIN_BY_KEY, CLIENTADAM_LIB_PATH, CLIENTCHAIN_LIB_PATH, CLIENTCOHORT_LIB_PATH,
-                    CLIENTCOSPLIT_LIB_PATH, COSPLIT_BY_KEY, CLIENTEVAL_LIB_PATH, CLIENTSPLIT_LIB_PATH, COHORT_BY_KEY, EVAL_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
+                    CLIENTCOSPLIT_LIB_PATH, COSPLIT_BY_KEY, CLIENTWIDE_LIB_PATH, WIDE_BY_KEY, CLIENTEVAL_LIB_PATH, CLIENTSPLIT_LIB_PATH, COHORT_BY_KEY, EVAL_BY_KEY, CLIENTLINEAR_LIB_PATH, CLIENTLOOP_LIB_PATH, CLIENTSTEP_LIB_PATH, CLIENTSTREAM_LIB_PATH,
                     CLIENTVEC_LIB_PATH, DESCRIBED, EXTRA_BY_KEY, FUSEDVEC_LIB_PATH, LIB_PATH, LINEAR_BY_KEY, PROBE_LIB_PATH,
                     SEGVEC_LIB_PATH, STREAM_BY_KEY, NativeLib)
 
@@ -271,6 +271,18 @@ CLIENTCOSPLIT_SIGNATURES = {
                                        + [_c_i64, _vp, _c_i64, _vp]),
 }
 
+# libfedavg_amd_clientwide.so (include/fedavg_amd_clientwide.h): the limits and the slice queries, then the split cohort's
+# arguments
+CLIENTWIDE_SIGNATURES = {
+    "fedavg_clientwide_abi_version": (_c_int, []),
+    "fedavg_clientwide_last_error": (ctypes.c_char_p, []),
+    "fedavg_client_wide_limits": (None, [_vp, _vp, _vp, _vp, _vp]),
+    "fedavg_client_wide_slice_rows": (_c_i64, []),
+    "fedavg_client_wide_max_slices": (_c_i64, [_c_i64]),
+    "fedavg_client_wide_workspace_bytes": (_c_i64, [_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
+    "fedavg_client_cohort_wide_f32": (_c_int, list(CLIENTCOSPLIT_SIGNATURES["fedavg_client_cohort_split_f32"][1])),
+}
+
 ABI_VERSION = BY_KEY["product"].abi[1]
 FUSEDVEC_ABI_VERSION = BY_KEY["fusedvec"].abi[1]
 SEGVEC_ABI_VERSION = BY_KEY["segvec"].abi[1]
@@ -285,6 +297,7 @@ CLIENTEVAL_ABI_VERSION = EVAL_BY_KEY["clienteval"].abi[1]
 CLIENTCHAIN_ABI_VERSION = CHAIN_BY_KEY["clientchain"].abi[1]
 CLIENTSPLIT_ABI_VERSION = CHAIN_BY_KEY["clientsplit"].abi[1]
 CLIENTCOSPLIT_ABI_VERSION = COSPLIT_BY_KEY["clientcosplit"].abi[1]
+CLIENTWIDE_ABI_VERSION = WIDE_BY_KEY["clientwide"].abi[1]
 
 FEDAVG_EINVAL = -10001
 FEDAVG_EALIGN = -10002
@@ -343,6 +356,10 @@ _CHAIN_BINDING = {
 _COSPLIT_BINDING = {
     "clientcosplit": ((CLIENTCOSPLIT_SIGNATURES,), "CLIENTCOSPLIT_LIB_PATH", "_clientcosplit"),
 }
+# the same for the libraries of build.WIDE_BY_KEY (a new one goes here)
+_WIDE_BINDING = {
+    "clientwide": ((CLIENTWIDE_SIGNATURES,), "CLIENTWIDE_LIB_PATH", "_clientwide"),
+}
 
 _lock = threading.Lock()
 _lib = None
@@ -360,6 +377,7 @@ _clienteval = None
 _clientchain = None
 _clientsplit = None
 _clientcosplit = None
+_clientwide = None
 
 
 def library_path() -> Path:
@@ -370,14 +388,15 @@ def _load(d: NativeLib) -> ctypes.CDLL:
     """Load (once), type and version-check the library ``d`` describes.  No
     fallback: a missing, unloadable or stale library raises ``FedAvgLibraryError``."""
     tables, path_name, slot = next(t[d.key] for t in (_BINDING, _EXTRA_BINDING, _LINEAR_BINDING, _STREAM_BINDING,
-                                                      _COHORT_BINDING, _EVAL_BINDING, _CHAIN_BINDING, _COSPLIT_BINDING)
+                                                      _COHORT_BINDING, _EVAL_BINDING, _CHAIN_BINDING, _COSPLIT_BINDING,
+                                                      _WIDE_BINDING)
                                    if d.key in t)
     g = globals()
     if g[slot] is not None:
         return g[slot]
     if d.needs:
         _load(next(t[d.needs] for t in (DESCRIBED, EXTRA_BY_KEY, LINEAR_BY_KEY, STREAM_BY_KEY, COHORT_BY_KEY, EVAL_BY_KEY,
-                                          CHAIN_BY_KEY, COSPLIT_BY_KEY) if d.needs in t))
+                                          CHAIN_BY_KEY, COSPLIT_BY_KEY, WIDE_BY_KEY) if d.needs in t))
     with _lock:
         if g[slot] is not None:
             return g[slot]
@@ -490,6 +509,12 @@ def load_clientcosplit() -> ctypes.CDLL:
     return _clientcosplit if _clientcosplit is not None else _load(COSPLIT_BY_KEY["clientcosplit"])
 
 
+def load_clientwide() -> ctypes.CDLL:
+    """The cohort of linear softmax clients of up to 128 classes and 4096 columns, fp32
+    (include/fedavg_amd_clientwide.h)."""
+    return _clientwide if _clientwide is not None else _load(WIDE_BY_KEY["clientwide"])
+
+
 check_fusedvec = functools.partial(_check, BY_KEY["fusedvec"])
 check_segvec = functools.partial(_check, BY_KEY["segvec"])
 check_clientvec = functools.partial(_check, BY_KEY["clientvec"])
@@ -539,6 +564,11 @@ def check_clientsplit(rc: int, what: str) -> None:
 def check_clientcosplit(rc: int, what: str) -> None:
     """``_check`` for the batch-split cohort library (its description read at call time)."""
     _check(COSPLIT_BY_KEY["clientcosplit"], rc, what)
+
+
+def check_clientwide(rc: int, what: str) -> None:
+    """``_check`` for the wide cohort library (its description read at call time)."""
+    _check(WIDE_BY_KEY["clientwide"], rc, what)
 
 
 def check(rc: int, what: str, lib: ctypes.CDLL = None) -> None:

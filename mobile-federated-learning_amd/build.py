@@ -23,8 +23,10 @@ any after it (the fourteenth, ``clientsplit``), is described in ``CHAIN_LIBS`` /
 The fifteenth, and any after it, is described in ``COSPLIT_LIBS`` /
 ``COSPLIT_BY_KEY``, which tests/test_clientcosplit_abi.py pins to that one key;
 ``BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS + CHAIN_LIBS + COSPLIT_LIBS``
-(``described_libs()``) is what ``sources()``, the up-to-date rule and ``build()`` cover, and ``_lib`` loads a library from
-the by-key table that holds it.
+(``described_libs()``) is the fifteen that test pins as well.  The sixteenth, and any after it, is described in
+``WIDE_LIBS`` / ``WIDE_BY_KEY``, which tests/test_clientwide_abi.py pins to that one key;
+``described_libs() + WIDE_LIBS`` (``every_described_lib()``) is what ``sources()``, the up-to-date rule and ``build()``
+cover, and ``_lib`` loads a library from the by-key table that holds it.
 
 Every translation unit of ``BUILT_LIBS`` is compiled in parallel with hipcc for
 ``--offload-arch=gfx950`` and each library is linked into ``lib/`` inside the
@@ -231,9 +233,32 @@ COSPLIT_BY_KEY = {lib.key: lib for lib in COSPLIT_LIBS}
 CLIENTCOSPLIT_LIB_PATH = COSPLIT_BY_KEY["clientcosplit"].path
 
 
+# libraries added after those fifteen (a new one goes here: see the module docstring)
+WIDE_LIBS = (
+    # the cohort for models of up to 128 classes and 4096 columns: per local iteration a gradient launch tiled over
+    # classes and columns, x streamed through LDS in units of 64 rows x 128 columns, then a sum, a step and a track
+    # launch that spread the client's step over workgroups, fp32; calls no other library.  Compiled without packed
+    # fp32 instructions.
+    NativeLib("clientwide", "libfedavg_amd_clientwide.so", "fedavg_amd_clientwide.h",
+              ("fedavg_client_wide.hip",), abi=("fedavg_clientwide_abi_version", 1),
+              last_error="fedavg_clientwide_last_error",
+              no_fallback="; there is no fallback for the cohort of wide linear clients",
+              defines=("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")),
+)
+WIDE_BY_KEY = {lib.key: lib for lib in WIDE_LIBS}
+CLIENTWIDE_LIB_PATH = WIDE_BY_KEY["clientwide"].path
+
+
 def described_libs():
-    """Every described library, in link order (the tuples are read when called, so a test that patches one is served)."""
+    """The fifteen libraries described before ``WIDE_LIBS``, in link order (the tuples are read when called, so a test
+    that patches one is served)."""
     return BUILT_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS + CHAIN_LIBS + COSPLIT_LIBS
+
+
+def every_described_lib():
+    """Every described library, in link order: ``described_libs()`` and ``WIDE_LIBS``."""
+    return described_libs() + WIDE_LIBS
+
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",
@@ -261,7 +286,7 @@ def hipcc_path() -> str:
 def sources():
     """Everything a library can depend on: every translation unit, every
     header in csrc/ and include/ (found, not listed) and this recipe."""
-    units = dict.fromkeys(src for lib in described_libs() for src in lib.sources)
+    units = dict.fromkeys(src for lib in every_described_lib() for src in lib.sources)
     return [*units, *sorted(CSRC_DIR.glob("*.hpp")), *sorted(INCLUDE.glob("*.h")), Path(__file__)]
 
 
@@ -272,11 +297,12 @@ def up_to_date() -> bool:
 
 def later_up_to_date() -> bool:
     """The same rule for ``LATER_LIBS``, ``NEWER_LIBS``, ``EXTRA_LIBS``, ``LINEAR_LIBS``, ``STREAM_LIBS``,
-    ``COHORT_LIBS``, ``EVAL_LIBS``, ``CHAIN_LIBS`` and ``COSPLIT_LIBS``: each built and no older than the newest source."""
+    ``COHORT_LIBS``, ``EVAL_LIBS``, ``CHAIN_LIBS``, ``COSPLIT_LIBS`` and ``WIDE_LIBS``: each built and no older than the
+    newest source."""
     newest = max(p.stat().st_mtime for p in sources())
     return all(lib.path.exists() and lib.path.stat().st_mtime >= newest
                for lib in LATER_LIBS + NEWER_LIBS + EXTRA_LIBS + LINEAR_LIBS + STREAM_LIBS + COHORT_LIBS + EVAL_LIBS
-               + CHAIN_LIBS + COSPLIT_LIBS)
+               + CHAIN_LIBS + COSPLIT_LIBS + WIDE_LIBS)
 
 
 def collect_ext_path() -> Path:
@@ -331,15 +357,15 @@ def _link(objs, lib_path, verbose, extra=()):
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
-    """Build every library of ``described_libs()``; returns the product library's path."""
+    """Build every library of ``every_described_lib()``; returns the product library's path."""
     if not force and up_to_date() and later_up_to_date():
         return LIB_PATH
-    libs = described_libs()
+    libs = every_described_lib()
     for lib in libs:
         (LIB_DIR / lib.obj_dir).mkdir(parents=True, exist_ok=True)
     _compile_all([(CSRC_DIR / u, lib.obj(u), list(lib.defines)) for lib in libs for u in lib.units], verbose)
     by_key = {**DESCRIBED, **EXTRA_BY_KEY, **LINEAR_BY_KEY, **STREAM_BY_KEY, **COHORT_BY_KEY, **EVAL_BY_KEY,
-              **CHAIN_BY_KEY, **COSPLIT_BY_KEY}
+              **CHAIN_BY_KEY, **COSPLIT_BY_KEY, **WIDE_BY_KEY}
     for lib in libs:  # in order: a library links after the one its link arguments name
         objs = [lib.obj(u) for u in lib.units] + [by_key[key].obj(u) for key, u in lib.reuse]
         _link(objs, lib.path, verbose, extra=lib.link)

@@ -230,8 +230,9 @@ class _LinearLoop:
 
     _pinned = {}  # device -> [record of 8 doubles, coefficient table [rows, 7]]
 
-    def __init__(self, params, x, labels, criterion, form_of):
-        """``form_of(device)``: the step form for fp32 on ``device``, or ``None``."""
+    def __init__(self, params, x, labels, criterion, form_of, wide=False):
+        """``form_of(device)``: the step form for fp32 on ``device``, or ``None``.  ``wide``: the sizes are held to
+        :func:`wide_limits` (the plan is then :class:`_Cohort`'s, which alone may run it)."""
         def refuse(why):
             raise TypeError(f"{why}: {_LINEAR_RULE}")
 
@@ -256,7 +257,12 @@ class _LinearLoop:
             refuse("the criterion is no default nn.CrossEntropyLoss")
         self.resident_b = linear_limits()[0]
         max_b, max_d, max_c, _ = linear_stream_limits()
-        if not (1 <= B <= max_b and 1 <= D <= max_d and 2 <= C <= max_c):
+        if wide:
+            _, max_b, max_d, max_c, _ = wide_limits()
+            if not (1 <= B <= max_b and 1 <= D <= max_d and 2 <= C <= max_c):
+                refuse(f"B = {B}, D = {D}, C = {C} lie outside the wide cohort's B <= {max_b}, D <= {max_d}, "
+                       f"2 <= C <= {max_c}")
+        elif not (1 <= B <= max_b and 1 <= D <= max_d and 2 <= C <= max_c):
             refuse(f"B = {B}, D = {D}, C = {C} lie outside B <= {max_b} (resident up to {self.resident_b}, streamed "
                    f"above), D <= {max_d}, 2 <= C <= {max_c}")
         if not (w.is_cuda and b.device == w.device and x.device == w.device and labels.device == w.device):
@@ -316,14 +322,18 @@ class _Cohort:
     passed the launch, so the next call may reuse them.  ``split``: the call is ``fedavg_client_cohort_split_f32``'s,
     each client's batch split across workgroups that walk ``slices_per_group`` slices each (``None``:
     :func:`cosplit_default_slices`), and the plan owns that entry's workspace, allocated by ``run`` after
-    :func:`_fits` has let its size pass."""
+    :func:`_fits` has let its size pass.  ``wide``: the call is ``fedavg_client_cohort_wide_f32``'s, with the sizes
+    held to :func:`wide_limits` instead, ``slices_per_group`` at most :func:`wide_max_slices` (``None``:
+    :func:`wide_default_slices`) and a workspace kept the same way."""
 
     _pinned = {}  # device -> [client table [K, 4] int64, records [K, 8], coefficient table [rows, 7]]
 
-    def __init__(self, params, batches, criterion, form_of, split=False, slices_per_group=None):
-        first = _LinearLoop(params, *batches[0], criterion, form_of)
+    def __init__(self, params, batches, criterion, form_of, split=False, slices_per_group=None, wide=False):
+        if wide and split:
+            raise ValueError("wide=True and split=True are two entries: choose one")
+        first = _LinearLoop(params, *batches[0], criterion, form_of, wide=wide)
         self.w, self.b, self.form, self.D, self.C, self.device = first.w, first.b, first.form, first.D, first.C, first.device
-        max_k, max_b, _, _ = cohort_limits()
+        max_k, max_b = wide_limits()[:2] if wide else cohort_limits()[:2]
         if len(batches) > max_k:
             raise TypeError(f"a cohort of {len(batches)} clients exceeds {max_k}: {_LINEAR_RULE}")
         self.x, self.labels = [first.x], [first.labels]
@@ -338,12 +348,19 @@ class _Cohort:
             self.labels.append(labels.contiguous())
         self.K, self.P = len(batches), self.C * self.D + self.C
         self.B = [x.shape[0] for x in self.x]
-        self.split, self.workspace = bool(split), None
+        self.split, self.wide, self.workspace = bool(split), bool(wide), None
         if split:
             if slices_per_group is None:
                 slices_per_group = cosplit_default_slices(self.B, self.D)
             if not (isinstance(slices_per_group, int) and slices_per_group >= 1):
                 raise ValueError(f"slices_per_group must be an int >= 1, not {slices_per_group!r}")
+            self.q = slices_per_group
+        if wide:
+            most = wide_max_slices(self.C)
+            if slices_per_group is None:
+                slices_per_group = wide_default_slices(self.B, self.C)
+            if not (isinstance(slices_per_group, int) and 1 <= slices_per_group <= most):
+                raise ValueError(f"slices_per_group must be an int in [1, {most}] at C = {self.C}, not {slices_per_group!r}")
             self.q = slices_per_group
 
     def _buffers(self, iters):
@@ -372,15 +389,19 @@ class _Cohort:
             args = (model.data_ptr(), rows.data_ptr(), rows.stride(0), table.data_ptr(), self.K, self.D, self.C, iters,
                     activation, 1 if adam else 0, float(lr), float(lr_ratio), self.form,
                     coef.data_ptr() if adam else None, rec.data_ptr())
-            if self.split:
-                nbytes = cosplit_workspace_bytes([self.B[k] for k in order], self.D, self.C, self.q, bool(adam))
+            if self.split or self.wide:
+                sizes = [self.B[k] for k in order]
+                nbytes = (wide_workspace_bytes if self.wide else cosplit_workspace_bytes)(sizes, self.D, self.C, self.q,
+                                                                                         bool(adam))
                 if self.workspace is None or self.workspace.numel() < nbytes:
                     self.workspace = None  # the old one first
-                    _fits(nbytes, self.device)
+                    _fits(nbytes, self.device, "wide" if self.wide else "batch-split")
                     self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                name, check = "fedavg_client_cohort_split_f32", _lib.check_clientcosplit
-                rc = _lib.load_clientcosplit().fedavg_client_cohort_split_f32(
-                    *args, self.q, self.workspace.data_ptr(), self.workspace.numel(), st.cuda_stream)
+                if self.wide:
+                    name, check, load = "fedavg_client_cohort_wide_f32", _lib.check_clientwide, _lib.load_clientwide
+                else:
+                    name, check, load = "fedavg_client_cohort_split_f32", _lib.check_clientcosplit, _lib.load_clientcosplit
+                rc = getattr(load(), name)(*args, self.q, self.workspace.data_ptr(), self.workspace.numel(), st.cuda_stream)
             else:
                 name, check = "fedavg_client_cohort_f32", _lib.check_clientcohort
                 rc = _lib.load_clientcohort().fedavg_client_cohort_f32(*args, st.cuda_stream)
@@ -416,13 +437,52 @@ def cosplit_workspace_bytes(B, D, C, slices_per_group, adam):
     return nbytes
 
 
-def _fits(nbytes, device):
+def _fits(nbytes, device, kind="batch-split"):
     """Refuse, before any launch, a workspace that ``torch.cuda.mem_get_info`` says cannot fit (memory torch holds
     cached and unused counts as free)."""
     free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
     if nbytes > free:
-        raise ValueError(f"the batch-split cohort needs a workspace of {nbytes} bytes and {device} has {free} free: "
-                         "raise slices_per_group, or train without split=True")
+        raise ValueError(f"the {kind} cohort needs a workspace of {nbytes} bytes and {device} has {free} free: "
+                         f"raise slices_per_group, or train without {'wide' if kind == 'wide' else 'split'}=True")
+
+
+# ------------------------------------------------------------------ the cohort at up to 128 classes and 4096 columns
+def wide_limits():
+    """``(max K, max B, max D, max C, max P)`` of ``fedavg_client_wide_limits``."""
+    out = [ctypes.c_int64() for _ in range(5)]
+    _lib.load_clientwide().fedavg_client_wide_limits(*[ctypes.byref(v) for v in out])
+    return tuple(v.value for v in out)
+
+
+def wide_slice_rows():
+    """The rows of one slice of ``fedavg_client_cohort_wide_f32``, at every shape."""
+    return _lib.load_clientwide().fedavg_client_wide_slice_rows()
+
+
+def wide_max_slices(C):
+    """The largest ``slices_per_group`` of ``fedavg_client_cohort_wide_f32`` at ``C`` classes (0 outside its range)."""
+    return _lib.load_clientwide().fedavg_client_wide_max_slices(C)
+
+
+def wide_default_slices(B, C):
+    """The ``slices_per_group`` of ``cohort_train(wide=True)`` when none is given: 1 while one slice a workgroup keeps
+    the gradient launch at or below ``COSPLIT_MANY_GROUPS`` workgroups, else ``COSPLIT_MANY_SLICES`` or the most
+    ``C`` allows."""
+    R = wide_slice_rows()
+    if sum(-(-b // R) for b in B) <= COSPLIT_MANY_GROUPS:
+        return 1
+    return min(COSPLIT_MANY_SLICES, wide_max_slices(C))
+
+
+def wide_workspace_bytes(B, D, C, slices_per_group, adam):
+    """``fedavg_client_wide_workspace_bytes`` for clients of ``B`` rows; ``ValueError`` outside its ranges."""
+    sizes = np.ascontiguousarray(B, dtype=np.int64)
+    nbytes = _lib.load_clientwide().fedavg_client_wide_workspace_bytes(
+        sizes.ctypes.data, len(sizes), D, C, slices_per_group, 1 if adam else 0)
+    if nbytes <= 0:
+        raise ValueError(f"no workspace for {len(sizes)} clients, D = {D}, C = {C}, slices_per_group = "
+                         f"{slices_per_group}: outside the ranges of fedavg_client_cohort_wide_f32")
+    return nbytes
 
 
 # ------------------------------------------------------------------ central_train's chain of steps, one launch

@@ -618,7 +618,8 @@ class CohortResult:
         return {self._names[0]: row[:C * D].view(C, D), self._names[1]: row[C * D:self.P]}
 
 
-def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None, split=False, slices_per_group=None):
+def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None, split=False, slices_per_group=None,
+                 wide=False):
     """A round's clients (fedavg_trainer.py:172-199: each trained from the same global model ``net``) under
     ``loop="linear"`` / ``"linear_sigmoid"`` as ONE launch of ``fedavg_client_cohort_f32``, one workgroup per client,
     one host sync and one read of the ``[K, 8]`` records.  ``clients`` are reference ``Client`` objects that share
@@ -634,13 +635,22 @@ def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None, spl
     every client's batch split across workgroups of ``slices_per_group`` slices of rows each (``None``: 1 while
     that keeps a launch at or below 1024 workgroups, else 4), for rounds of few clients with long batches.  Same checks,
     same result type, a client's bits independent of the other clients but not those of ``split=False`` (its gradient
-    is summed slice by slice); a ``ValueError`` naming the bytes, before any launch, if the workspace cannot fit."""
+    is summed slice by slice); a ``ValueError`` naming the bytes, before any launch, if the workspace cannot fit.
+
+    ``wide=True``: the round as ``1 + 4 * local_iteration`` launches of ``fedavg_client_cohort_wide_f32``, for models
+    of up to 128 classes and 4096 columns (FEMNIST 784 x 62, CIFAR 3072 x 10 / x 100): tiled over classes and
+    columns, the step spread over workgroups.  ``slices_per_group`` is at most ``wide_max_slices(C)`` (``None``: 1
+    while the gradient launch stays at or below 1024 workgroups, else ``min(4, wide_max_slices(C))``).  Same checks
+    with the wider limits in the ``TypeError``, same result type, same ``IndexError``; bits of its own.  Never chosen
+    automatically, and not together with ``split=True`` (``ValueError``)."""
     from .reduce import ALIGN_ELEMS
 
     if loop not in LINEAR_LOOPS:
         raise ValueError(f"loop must be 'linear' or 'linear_sigmoid', not {loop!r}")
     if local_iteration <= 0:
         raise ValueError("cohort_train needs local_iteration >= 1")
+    if wide and split:
+        raise ValueError("wide=True and split=True are two entries: choose one")
     clients = list(clients)
     if not clients:
         raise ValueError("cohort_train needs at least one client")
@@ -656,10 +666,11 @@ def cohort_train(clients, net, local_iteration, *, loop="linear", rows=None, spl
         batches.append((x.to(c.device), labels.to(c.device)))
     form_of = (lambda dev: sgd_form(dev, torch.float32)) if sgd else (lambda dev: adam_form(dev, torch.float32))
     names = [n for n, _ in net.named_parameters()]
-    if slices_per_group is not None and not split:
+    if slices_per_group is not None and not (split or wide):
         raise ValueError("slices_per_group needs split=True")
     # refused, if it is, before anything runs
-    plan = _Cohort(net.parameters(), batches, clients[0].criterion, form_of, split=split, slices_per_group=slices_per_group)
+    plan = _Cohort(net.parameters(), batches, clients[0].criterion, form_of, split=split, slices_per_group=slices_per_group,
+                   wide=wide)
     ld = -(-plan.P // ALIGN_ELEMS) * ALIGN_ELEMS
     if rows is None:
         rows = torch.empty(plan.K, ld, dtype=torch.float32, device=plan.device)
